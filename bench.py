@@ -13,6 +13,8 @@ exactly K steps (barrier + device sync on both sides).  `roofline`: the step is 
 average step duration measured with HIP events on the launch stream; peak = 8.0 TB/s.
 `cpu_baseline`: the CPU oracle (oracle/torchok_ref.py, fp32, same step) timed on this box's host
 cores on a bounded sample (rank 0, N = 1 only).
+`--dump-outputs DIR`: what the last timed step computed, as .npy files (dump_outputs); the inputs are seeded, so two
+builds run with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -341,6 +343,40 @@ def cpu_baseline(backbone: str, num_classes: int, res: int, width: int = 0, batc
                       f'{batch}, oracle/ on torch {torch.__version__} CPU, {threads} threads'}
 
 
+def dump_outputs(outdir: str, out: dict, task, limit: int = 60_000_000):
+    """--dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy per tensor (float32; float64 stays
+    float64): the tensors of the dict the step returns (`loss`, the tagged loss terms), the module state the step updated
+    (`state.<key>`: parameters and BatchNorm statistics) and that step's gradients (`grad.<name>`).  A tensor above a
+    per-tensor cap, chosen so that the files stay under `limit` bytes in all, is stored as a sample of its flattened (logical)
+    order at positions seeded by its name: the same positions in every run, so two builds compare element for element."""
+    import zlib
+    import numpy as np
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    for k, v in task.state_dict().items():
+        if v.is_floating_point() and not k.startswith('input_tensors'):      # (input_tensors_*: the task's example inputs)
+            arrays['state.' + k] = v
+    for k, p in task.named_parameters():
+        if p.grad is not None:
+            arrays['grad.' + k] = p.grad
+    item = {k: 8 if v.dtype == torch.float64 else 4 for k, v in arrays.items()}
+
+    def total(cap):
+        return sum(min(v.numel(), cap) * item[k] + 128 for k, v in arrays.items())      # + the .npy header
+    lo, hi = 1, max(v.numel() for v in arrays.values())
+    while lo < hi:                      # the largest cap that fits
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if total(mid) <= limit else (lo, mid - 1)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrays.items():
+        flat = v.detach().reshape(-1)
+        if flat.numel() > lo:
+            g = torch.Generator().manual_seed(zlib.crc32(k.encode()))
+            flat = flat[torch.randperm(flat.numel(), generator=g)[:lo].sort().values.to(flat.device)]
+        a = flat.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy().reshape(v.shape if v.numel() <= lo else -1)
+        np.save(os.path.join(outdir, k.replace(os.sep, '_') + '.npy'), a)
+    return len(arrays), lo
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -355,7 +391,11 @@ def main():
     ap.add_argument('--no-secondary', action='store_true', help='skip the bounded secondary-workload block of the default line')
     ap.add_argument('--graph', type=int, default=-1, help='1: replay the step as one hipGraph, 0: eager launches '
                     '(default: graph only where the step is host-launch-bound: HRNet below batch 16)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (at most 64 MB)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     # stdout carries exactly ONE line (the JSON result): native libraries that chat on file descriptor 1 (RCCL's
     # version banner at communicator creation) are sent to stderr until that line is printed
@@ -465,11 +505,11 @@ def main():
         # ONE function for every caller (engine/step.py): training_step -> backward (+ bucketed exchange) -> optimizer ->
         # on_train_batch_end (the per-step loss mean of reference tasks/base.py:163-173, on the comm stream for N > 1)
         if graphed is not None:
-            return graphed(batch)['loss']
-        return train_step(task, opt, batch, i, reducer)['loss']
+            return graphed(batch)
+        return train_step(task, opt, batch, i, reducer)
 
     for i in range(args.warmup):
-        loss = step(i)
+        step(i)
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
@@ -480,7 +520,7 @@ def main():
     evs[0].record()
     host_done = []
     for i in range(args.steps):
-        loss = step(args.warmup + i)
+        out = step(args.warmup + i)
         evs[i + 1].record()
         host_done.append(time.perf_counter())
     torch.cuda.synchronize()
@@ -492,7 +532,7 @@ def main():
     # how far the launch thread runs ahead of the GPU: evs[0] was recorded on an idle device at host time t0, so step i's
     # kernels finish at about t0 + elapsed(evs[0], evs[i + 1]); the host finished enqueuing that step at host_done[i]
     host_lead_ms = [evs[0].elapsed_time(evs[i + 1]) - (host_done[i] - t0) * 1e3 for i in range(args.steps)]
-    final_loss = float(loss.detach())
+    final_loss = float(out['loss'].detach())
     in_sync = replicas_in_sync(reducer)      # N > 1: every rank must hold bit-identical parameters after the run
     per_rank = None
     if dist_on:
@@ -506,6 +546,8 @@ def main():
         rows = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
         dist.all_gather(rows, mine)
         per_rank = [[round(float(v), 3) for v in r.tolist()] for r in rows]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, task)
 
     if rank == 0:
         value = args.batch * world * args.steps / dt
@@ -587,7 +629,7 @@ def main():
                                               f"{sum(len(b) for b in reducer.buckets)} buckets + buffer broadcast"
         if world == 1 and not dist_on and not args.no_secondary and args.backbone == 'resnet50' and args.batch == 256:
             # free the headline workload first: the secondary ones need the memory, and their numbers must not depend on it
-            del task, opt, batch, image, target, loss
+            del task, opt, batch, image, target, out
             import gc
             gc.collect()
             torch.cuda.empty_cache()

@@ -10,6 +10,9 @@ from torchok_amd.constructor import registry as reg_mod
 from torchok_amd.constructor.config import load_config
 from torchok_amd.constructor.registry import Registry
 
+# build-authored recipes with the component sets of the reference's examples/configs/*.yaml of the same names
+RECIPES = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'recipes')
+
 
 def test_fourteen_registries_exist():
     import torchok_amd.constructor as C
@@ -178,17 +181,16 @@ def test_paramwise_cfg_groups():
     assert abs(by_name['layer4.0.conv1.weight']['lr'] - 0.01) < 1e-12 and by_name['layer3.0.conv1.weight']['lr'] == 0.1
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/examples/configs/classification_cifar10.yaml'),
-                    reason='the reference checkout exists only in the build container')
 def test_reference_cifar10_recipe_runs_a_step(fake_backend):
-    """BASELINE.json configs[0]: the reference's own examples/configs/classification_cifar10.yaml (ResNet-18,
-    ClassificationTask, CrossEntropyLoss, Adam, Accuracy + F1Score) loads unchanged and runs a training step, an optimizer
-    step and the epoch-end metric summary (datasets / trainer sections are parsed and ignored: no data pipeline here)."""
+    """BASELINE.json configs[0]: a recipe with the components of the reference's examples/configs/classification_cifar10.yaml
+    (tests/recipes/classification_cifar10.yaml: ResNet-18, ClassificationTask, CrossEntropyLoss, Adam, Accuracy + F1Score)
+    loads and runs a training step, an optimizer step and the epoch-end metric summary (datasets / trainer sections are
+    parsed and ignored: no data pipeline here)."""
     import torch
     import torchok_amd as T
     os.environ.setdefault('HOME', '/root')
     # the recipe asks for pretrained weights (a download): overridden the way the launcher overrides keys
-    cfg = T.load_config('/root/reference/examples/configs/classification_cifar10.yaml',
+    cfg = T.load_config(os.path.join(RECIPES, 'classification_cifar10.yaml'),
                         overrides={'task.params.backbone_params.pretrained': False})
     task = T.TASKS.get(cfg.task.name)(cfg, **cfg.task.params).train()
     assert type(task.backbone).__name__ == 'ResNet' and len(task.metrics_manager.phase2metrics['TRAIN']) >= 1
@@ -221,15 +223,15 @@ _RECIPES = [
 ]
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/examples/configs'), reason='reference checkout: build container only')
 @pytest.mark.parametrize('name,extra,make_batch,make_val', _RECIPES, ids=[r[0] for r in _RECIPES])
 def test_shipped_recipes_drive_a_training_step(fake_backend, name, extra, make_batch, make_val):
-    """The reference's own examples/configs/*.yaml (task, losses, optimizer, scheduler, metrics sections) build the task and
-    run step + backward + optimizer + scheduler + epoch-end metrics without edits (only `pretrained: true` -> false);
+    """Recipes with the components of the reference's examples/configs/*.yaml (tests/recipes/: task, losses, optimizer,
+    scheduler, metrics sections) build the task and run step + backward + optimizer + scheduler + epoch-end metrics
+    without edits (only `pretrained: true` -> false);
     the metric-learning recipes also run a validation step and their HitAtKMeter at validation epoch end."""
     import torch
     os.environ.setdefault('HOME', '/root')
-    cfg = T.load_config(f'/root/reference/examples/configs/{name}.yaml',
+    cfg = T.load_config(os.path.join(RECIPES, f'{name}.yaml'),
                         overrides=dict({'task.params.backbone_params.pretrained': False}, **extra))
     task = T.TASKS.get(cfg.task.name)(cfg, **cfg.task.params).train()
     conf = task.configure_optimizers()[0]
@@ -274,21 +276,20 @@ def test_trainer_precision_is_honoured_or_refused():
         resolve_strategy({'sync_batchnorm': True})
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/examples/configs'), reason='reference checkout: build container only')
 @pytest.mark.parametrize('name,extra,make_batch,make_val', _RECIPES, ids=[r[0] for r in _RECIPES])
 def test_shipped_recipes_run_through_the_fit_loop(fake_backend, name, extra, make_batch, make_val):
-    """Every shipped recipe, unchanged except `pretrained` and `trainer.precision=bf16`, through run.fit for 2 steps
+    """Every recipe above, unchanged except `pretrained` and `trainer.precision=bf16`, through run.fit for 2 steps
     (task -> optimizer / scheduler -> steps -> epoch-end hooks); with its own precision (32 by default) it is refused."""
     import torch
     from torchok_amd.run import fit
     os.environ.setdefault('HOME', '/root')
     ov = dict({'task.params.backbone_params.pretrained': False}, **extra)
-    asked = T.load_config(f'/root/reference/examples/configs/{name}.yaml', overrides=ov)
+    asked = T.load_config(os.path.join(RECIPES, f'{name}.yaml'), overrides=ov)
     wants = str((asked.trainer or {}).get('precision', 32))
     if wants in ('32', '64'):
         with pytest.raises(ValueError, match='precision'):
             fit(asked, batches=[], max_steps=0, device='cpu')
-    cfg = T.load_config(f'/root/reference/examples/configs/{name}.yaml',
+    cfg = T.load_config(os.path.join(RECIPES, f'{name}.yaml'),
                         overrides=dict(ov, **{'trainer.precision': 'bf16', 'trainer.devices': 1}))
     torch.manual_seed(0)
     seen = []

@@ -1,5 +1,5 @@
 import ctypes, sys, os, torch
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from torchok_amd import _C
 lib = _C.load_library()
 st = torch.cuda.current_stream().cuda_stream

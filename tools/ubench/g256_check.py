@@ -3,6 +3,7 @@ with BatchNorm-backward sums / ReLU-masked store) and per-call time.   python to
 import os
 import subprocess
 import sys
+import tempfile
 
 import torch
 
@@ -12,7 +13,7 @@ SHAPES = [(50176, 1024, 256), (50176, 256, 1024), (50176, 512, 1024), (12544, 20
           (200704, 712, 512)]
 
 
-def run(tag):
+def run(tag, outdir):
     from torchok_amd import _C
     lib = _C.load_library()
     st = torch.cuda.current_stream().cuda_stream
@@ -66,16 +67,18 @@ def run(tag):
         print(f'[{tag}] M={m} K={k} N={n}: fwd+stats {tf:6.1f} us ({fl / tf / 1e6:5.0f} TF/s)  dgrad {td:6.1f} us ({fl / td / 1e6:5.0f} TF/s)  fwd+gelu {tfa:6.1f} us  dgrad*dgelu {tda:6.1f} us  rows {rows}/{rows_d}', flush=True)
         out[(m, k, n)] = dict(y=y.float().cpu(), s=stats.sum(1).cpu(), dx=dx.float().cpu(), dxa=dxa.float().cpu(), dxs=dxs.float().cpu(),
                               p=part.sum(1).cpu(), dxm=dxm.float().cpu(), pm=partm.sum(1).cpu(), ya=ya.float().cpu(), yact=yact.float().cpu(), dxg=dxg.float().cpu(), ref_y=(x.float() @ w.float().t()).cpu() if m * n < 1.2e8 else None)
-    torch.save(out, f'/tmp/g256_{tag}.pt')
+    torch.save(out, os.path.join(outdir, f'g256_{tag}.pt'))
 
 
 if __name__ == '__main__':
     if len(sys.argv) > 1:
-        run(sys.argv[1])
+        run(sys.argv[1], sys.argv[2])
         sys.exit(0)
+    tmp = tempfile.TemporaryDirectory()        # private to this run: the arms' tensors are large, and /tmp is shared
     for tag, v in (('new', '2'), ('old', '0')):
-        subprocess.run([sys.executable, __file__, tag], env=dict(os.environ, TOK_GEMM256=v, TOK_GEMM256_ACT='1'), check=True)    # (fused activation on the 256 tiles is off by default: switched on for the comparison)
-    a, b = torch.load('/tmp/g256_new.pt'), torch.load('/tmp/g256_old.pt')
+        subprocess.run([sys.executable, __file__, tag, tmp.name], env=dict(os.environ, TOK_GEMM256=v, TOK_GEMM256_ACT='1'), check=True)    # (fused activation on the 256 tiles is off by default: switched on for the comparison)
+    a, b = (torch.load(os.path.join(tmp.name, f'g256_{t}.pt')) for t in ('new', 'old'))
+    tmp.cleanup()
 
     def rel(u, v):
         return float((u.double() - v.double()).norm() / (v.double().norm() + 1e-30))

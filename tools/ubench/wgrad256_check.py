@@ -3,6 +3,7 @@
 import os
 import subprocess
 import sys
+import tempfile
 
 import torch
 
@@ -13,7 +14,7 @@ SHAPES = [(50176, 1024, 256), (50176, 256, 1024), (50176, 512, 1024), (12544, 20
           (12544, 3072, 768), (786432, 720, 720), (9000, 520, 264)]
 
 
-def run(tag):
+def run(tag, outdir):
     from torchok_amd import _C
     lib = _C.load_library()
     st = torch.cuda.current_stream().cuda_stream
@@ -50,16 +51,18 @@ def run(tag):
         print(f'[{tag}] M={m} Ktot={c} k={k}: wgrad+bias {t:7.1f} us ({fl / t / 1e6:5.0f} TF/s)  workspace {wsb / 1e6:6.1f} MB', flush=True)
         ref = (dy.float().t() @ x.float()).cpu() if m <= 60000 else None
         out[(m, c, k)] = dict(dw=dw.cpu(), db=db.cpu(), dwa=(dwa - base).cpu(), ref=ref, refb=dy.float().sum(0).cpu())
-    torch.save(out, f'/tmp/w256_{tag}.pt')
+    torch.save(out, os.path.join(outdir, f'w256_{tag}.pt'))
 
 
 if __name__ == '__main__':
     if len(sys.argv) > 1:
-        run(sys.argv[1])
+        run(sys.argv[1], sys.argv[2])
         sys.exit(0)
+    tmp = tempfile.TemporaryDirectory()        # private to this run: the arms' tensors are large, and /tmp is shared
     for tag, v in (('new', '2'), ('old', '0')):
-        subprocess.run([sys.executable, __file__, tag], env=dict(os.environ, TOK_WGRAD_256=v), check=True)
-    a, b = torch.load('/tmp/w256_new.pt'), torch.load('/tmp/w256_old.pt')
+        subprocess.run([sys.executable, __file__, tag, tmp.name], env=dict(os.environ, TOK_WGRAD_256=v), check=True)
+    a, b = (torch.load(os.path.join(tmp.name, f'w256_{t}.pt')) for t in ('new', 'old'))
+    tmp.cleanup()
 
     def rel(u, v):
         return float((u.double() - v.double()).norm() / (v.double().norm() + 1e-30))
