@@ -289,7 +289,12 @@ int tok_bn_bwd_finalize(const float* partial, int rows, int64_t m, int c, int c_
                         const float* gamma, const float* mean, const float* rstd,
                         float* dgamma, float* dbeta, float* coef, int accumulate, int dzy_form,
                         void* stream);
-/* dy = a1*dz + a2*y + a3;  if dshortcut != NULL: dshortcut (=|+=) dz                       */
+/* dy = a1*dz + a2*y + a3;  if dshortcut != NULL: dshortcut (=|+=) dz
+ * relu != 0 with mask == NULL: the ReLU pattern is recomputed as y*scale + shift > 0, which is
+ * only the forward's pattern when no shortcut was added before the activation.  A unit with a
+ * shortcut must pass the mask tok_bn_act_fwd wrote; relu && !mask && dshortcut is refused
+ * (TOK_ERR_INVALID).  The refusal is partial: a shortcut that needs no gradient passes
+ * dshortcut == NULL and cannot be told apart from a unit without one.                       */
 int tok_bn_bwd_apply(const void* dout, const void* y, const uint8_t* mask,
                      const float* scale, const float* shift, const float* coef, int relu,
                      void* dy, void* dshortcut, int dshortcut_accumulate,

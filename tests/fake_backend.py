@@ -132,6 +132,8 @@ class FakeTok:
 
     def tok_conv_dgrad(self, d, dy, wd, dx, accumulate, st):
         d = _desc(d)
+        if d.c % 8:
+            return -1     # TOK_ERR_INVALID: the c4 stem input has no data gradient (conv_igemm.hip)
         self.calls.append('conv_dgrad')
         g = _t(dy, (d.n, d.p, d.q, d.k), BF16).float().permute(0, 3, 1, 2)
         pack = _t(wd, (d.c, d.r, d.s, d.k), BF16).float()
@@ -561,6 +563,8 @@ class FakeTok:
 
     def tok_bn_bwd_apply(self, dout, y, out, scale, shift, coef, relu, dy, dshortcut, ds_acc, m, c, st):
         self.calls.append('bn_bwd_apply')
+        if relu and out is None and dshortcut is not None:
+            return -1     # TOK_ERR_INVALID: the recomputed ReLU pattern would leave out the shortcut
         dz = self._dz(dout, y, out, scale, shift, relu, m, c)
         co = _t(coef, (3, c), torch.float32)
         res = co[0] * dz + co[1] * _t(y, (m, c), BF16).float() + co[2]

@@ -474,6 +474,78 @@ def test_bn_chain(libs, m, c, relu, with_sc):
     assert relerr(dy_h.float(), yy.grad) < 2e-2
 
 
+@pytest.mark.parametrize('m,c,c_real', [(1000, 64, 64), (4096 + 17, 256, 256), (777, 48, 42), (300, 152, 144)])
+@pytest.mark.parametrize('with_sc,ds_acc', [(0, 0), (1, 0), (1, 1)])
+def test_bn_eval_bwd_apply(libs, m, c, c_real, with_sc, ds_acc):
+    """Eval-mode BatchNorm backward: tok_bn_eval_coeffs (running statistics, padded channels zeroed) -> tok_bn_act_fwd with
+    the ReLU mask -> tok_bn_bwd_apply with the eval coefficients (dy = scale * dz), with and without a shortcut added
+    before the ReLU, against an fp64 torch restatement.  Without a shortcut the mask-less recompute (y*scale + shift > 0)
+    is bit-equal to the masked path; with one, the mask-less call is refused."""
+    lib, _ = libs
+    P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    st = torch.cuda.current_stream().cuda_stream
+    gamma, beta = rnd(c_real, seed=1) * 0.5 + 1, rnd(c_real, seed=2) * 0.2
+    rm, rv = rnd(c_real, seed=3) * 0.5, rnd(c_real, seed=4).abs() + 0.5
+    eps = 1e-5
+    scale = torch.full((c,), 7.0, device=DEV)
+    shift = torch.full((c,), 7.0, device=DEV)
+    params = [t.to(DEV) for t in (gamma, beta, rm, rv)]
+    assert lib.tok_bn_eval_coeffs(*(P(t) for t in params), eps, c, c_real, P(scale), P(shift), st) == 0, lib.tok_last_error()
+    torch.cuda.synchronize()
+    sc64 = torch.zeros(c, dtype=torch.float64)
+    sh64 = torch.zeros(c, dtype=torch.float64)
+    sc64[:c_real] = gamma.double() / torch.sqrt(rv.double() + eps)
+    sh64[:c_real] = beta.double() - rm.double() * sc64[:c_real]
+    assert maxrel(scale, sc64, 1e-6) < 1e-5 and maxrel(shift, sh64, 0.1) < 1e-5
+    assert not scale[c_real:].any() and not shift[c_real:].any()
+
+    pad = torch.zeros(c)
+    pad[:c_real] = 1
+    y = ((rnd(m, c, seed=5) * 1.5 + 0.3) * pad).to(BF16).to(DEV)
+    sc = (rnd(m, c, seed=6) * pad).to(BF16).to(DEV) if with_sc else None
+    dout = rnd(m, c, seed=7).to(BF16).to(DEV)
+    out = torch.empty(m, c, dtype=BF16, device=DEV)
+    mask = torch.empty(m, c // 8, dtype=torch.uint8, device=DEV)
+    assert lib.tok_bn_act_fwd(P(y), P(scale), P(shift), P(sc), 1, P(out), P(mask), m, c, st) == 0, lib.tok_last_error()
+    coef = torch.zeros(3, c, device=DEV)
+    coef[0] = scale                      # eval-mode BatchNorm: y -> out is a fixed affine map (engine/functional.py)
+    old = rnd(m, c, seed=8).to(BF16).to(DEV)
+    dy = torch.empty(m, c, dtype=BF16, device=DEV)
+    ds = old.clone() if with_sc else None
+    assert lib.tok_bn_bwd_apply(P(dout), P(y), P(mask), P(scale), P(shift), P(coef), 1, P(dy), P(ds), ds_acc, m, c,
+                                st) == 0, lib.tok_last_error()
+    torch.cuda.synchronize()
+
+    # fp64 restatement: z = y*scale + shift (+ shortcut), out = relu(z), dz = dout * (z > 0), dy = scale * dz
+    pre = y.double().cpu() * sc64 + sh64 + (sc.double().cpu() if with_sc else 0)
+    live = pre > 0
+    bits = ((mask.cpu().long().unsqueeze(-1) >> torch.arange(8)) & 1).reshape(m, c).bool()
+    assert torch.equal(bits, out.float().cpu() > 0)
+    assert (bits != live).double().mean() < 1e-4          # only bf16 rounding at z ~ 0 may disagree
+    assert relerr(out.cpu(), pre.clamp_min(0)) < 5e-3
+    dz64 = dout.double().cpu() * live
+    assert relerr(dy.cpu(), sc64 * dz64) < 1e-2
+    assert not dy.cpu()[:, c_real:].any()
+    if with_sc:
+        want = dz64 + (old.double().cpu() if ds_acc else 0)
+        assert relerr(ds.cpu(), want) < 1e-2
+        # the shortcut's gradient is the masked incoming gradient (+ old): exact up to the one bf16 rounding of the sum
+        exact = (dout.float() * bits.to(DEV)) + (old.float() if ds_acc else 0)
+        assert torch.equal(ds, exact.to(BF16))
+        # refusal: the mask-less recompute leaves out the shortcut; nothing is written
+        dy2, ds2 = torch.full_like(dy, 3.0), old.clone()
+        rc = lib.tok_bn_bwd_apply(P(dout), P(y), None, P(scale), P(shift), P(coef), 1, P(dy2), P(ds2), ds_acc, m, c, st)
+        assert rc == -1 and b'mask' in lib.tok_last_error()
+        torch.cuda.synchronize()
+        assert bool((dy2 == 3.0).all()) and torch.equal(ds2, old)
+    else:
+        dy2 = torch.empty_like(dy)
+        assert lib.tok_bn_bwd_apply(P(dout), P(y), None, P(scale), P(shift), P(coef), 1, P(dy2), None, 0, m, c,
+                                    st) == 0, lib.tok_last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(dy2, dy)
+
+
 @pytest.mark.parametrize('shape', [(2, 16, 16, 64), (1, 15, 17, 8), (3, 7, 9, 128)])
 def test_maxpool_exact(libs, shape):
     n, h, w, c = shape

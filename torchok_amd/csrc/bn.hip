@@ -800,6 +800,12 @@ extern "C" int tok_bn_bwd_apply(const void* dout, const void* y, const uint8_t* 
                                 void* stream) {
   TOK_CHECK_ARG(dout && y && scale && shift && coef && dy, "tok_bn_bwd_apply: null pointer");
   TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "tok_bn_bwd_apply: bad sizes");
+  if (relu && mask == nullptr && dshortcut != nullptr) {
+    // the recomputed pattern y*scale + shift > 0 leaves out the shortcut the forward added before the ReLU
+    t_done_event = nullptr;
+    tok_set_error("tok_bn_bwd_apply: relu with a shortcut needs the forward's ReLU mask (mask == NULL)");
+    return TOK_ERR_INVALID;
+  }
   if (tok_dbg_skip(8)) { t_done_event = nullptr; return TOK_OK; }
   const Geo g = make_geo(c);
   if (t_done_event != nullptr) {

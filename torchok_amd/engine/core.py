@@ -161,15 +161,27 @@ def _await(events):
             cur.wait_event(ev)
 
 
-def await_ready(*tensors):
+def await_ready(*tensors, affine_ok: bool = False):
     """Forward: make the current stream wait for tensors that were produced on a branch stream, and tell the caching
     allocator about the new reader: the buffers belong to the branch stream's pool, and without `record_stream` a buffer
     whose last reference dies on the launch thread (no-grad mode; operands no unit keeps for its backward, like a bias
     vector) is handed to the branch stream's NEXT allocation while the consumer's kernel is still queued.
-    Arguments: TTensors, or objects with `ready` and a `tensors` tuple (Region.branch's publish)."""
+    The same holds the other way round: inside a live branch a tensor without `ready` comes from the main stream (an HRNet
+    fuse row reading x[0], a branch reading a transition output), and the main stream joins the branch only in
+    Region.output — with no tape node holding it (no-grad, frozen backbone) its block could go back to the main pool while
+    the branch's kernels are still queued.  So it is `record_stream`ed on the branch stream (a no-op for a buffer the branch
+    allocated itself).
+    Arguments: TTensors, or objects with `ready` and a `tensors` tuple (Region.branch's publish).  A TTensor that carries
+    `.affine` (a raw conv output whose BatchNorm apply is deferred) is refused unless the consumer applies it (affine_ok)."""
     cur = None
+    branch = getattr(_tls, 'branch', None)
     for t in tensors:
-        if t is not None and t.ready is not None:
+        if t is None:
+            continue
+        if not affine_ok and getattr(t, 'affine', None) is not None:
+            raise RuntimeError('torchok_amd: a tensor with a deferred BatchNorm apply (conv_bn_act defer_apply) reached a '
+                               'consumer that does not apply it; only resample.fuse_sum_relu does')
+        if t.ready is not None:
             _await((t.ready,))
             if cur is None:
                 cur = cur_stream()
@@ -177,6 +189,10 @@ def await_ready(*tensors):
                 for d in (t.tensors if hasattr(t, 'tensors') else (t.data,)):
                     if d is not None and d.is_cuda:
                         d.record_stream(cur)
+        elif branch is not None:
+            for d in (t.tensors if hasattr(t, 'tensors') else (t.data,)):
+                if d is not None and d.is_cuda:
+                    d.record_stream(branch)
 
 
 def _sync_writers(writers, cur):
@@ -450,6 +466,7 @@ class _Branch:
                 b.wait_event(ev)
             r._streams[self.idx] = b
             self.prev, r._tag = r._tag, self.idx
+            self.prev_branch, _tls.branch = getattr(_tls, 'branch', None), b     # await_ready: readers on this stream
             self.ctx = _StreamCtx(b)
             self.ctx.__enter__()
             self.stream = b
@@ -458,6 +475,7 @@ class _Branch:
     def __exit__(self, *exc):
         if self.live:
             self.ctx.__exit__(*exc)
+            _tls.branch = self.prev_branch
             r = self.region
             r._tag = self.prev
             done = torch.cuda.Event()
@@ -607,6 +625,8 @@ class Region:
     # -- exit ----------------------------------------------------------------------------------
     def output(self, *outs: TTensor):
         self._join_forward()
+        if any(o.affine is not None for o in outs):
+            raise RuntimeError('torchok_amd: a region output with a deferred BatchNorm apply (conv_bn_act defer_apply)')
         need = self.grad_mode and any(o.requires_grad for o in outs)
         if not need:
             for n in self.nodes:

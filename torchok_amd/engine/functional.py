@@ -863,8 +863,10 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
                                                  ptr(node.pool), ptr(node.ypool), st), 'tok_bn_relu_maxpool_fwd')
         else:
             out_data = torch.empty_like(y)
-            if relu and region.grad_mode and batch_stats:
-                mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=dev)   # ReLU bits for the backward pass
+            if relu and region.grad_mode:
+                # ReLU bits for the backward pass, running statistics included: the apply kernel's mask-less fallback
+                # recomputes the pattern from y alone and would leave out a shortcut added before the activation
+                mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=dev)
             # a 3x3 unit of a bottleneck feeds the fused residual unit, which wants colsum(z) of its input: the activation pass
             # has z in registers (saves that unit a stand-alone pass over z)
             want_cs = (FUSE_UNIT3 and COLSUM_IN_ACT and r == 3 and relu and shortcut is None and m >= UNIT3_MIN_ROWS
@@ -1025,6 +1027,7 @@ class _AvgPool2Node(Node):
 
 def avg_pool_2x2(region: Region, x: TTensor) -> TTensor:
     """AvgPool2d(2, stride 2, ceil_mode=True, count_include_pad=False) ([timm] downsample_avg)."""
+    await_ready(x)       # a projection shortcut on a branch stream (resnet.py, TOK_SHORTCUT_BRANCH=1) reads x here
     n, h, w, c = x.shape
     y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=BF16, device=x.data.device)
     _C.check(_C.lib().tok_avgpool2x2_fwd(ptr(x.data), ptr(y), n, h, w, c, stream_ptr()), 'tok_avgpool2x2_fwd')

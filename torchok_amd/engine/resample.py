@@ -43,7 +43,7 @@ def fuse_sum_relu(region: Region, terms: Sequence[Tuple[TTensor, int]], relu: bo
     """out = relu(sum_j upsample_nearest(t_j, 2**shift_j)); the first term fixes the output shape (shift 0)."""
     if not 1 <= len(terms) <= 4:
         raise NotImplementedError('fuse_sum_relu: 1..4 terms')
-    await_ready(*(t for t, _ in terms))
+    await_ready(*(t for t, _ in terms), affine_ok=True)
     ref, sh0 = terms[0]
     n, h, w, cp = ref.shape
     h, w = h << sh0, w << sh0
