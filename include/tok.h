@@ -705,6 +705,30 @@ int tok_rmsprop_step(float* param, const float* grad, float* square_avg, float* 
 int tok_fill_f32(float* dst, float value, size_t count, void* stream);
 int tok_scale_f32(float* dst, float factor, size_t count, void* stream);
 
+/* ---- gradient clipping over the arenas of one optimizer --------------------------------------
+ * torch.nn.utils.clip_grad_norm_ / clip_grad_value_ as Lightning's `clip_gradients` calls them between the gradient exchange
+ * and optimizer.step() (trainer.gradient_clip_val / gradient_clip_algorithm, constructor/config_structure.py:161-162).
+ * A span table (device memory, `n_spans` entries) lists every parameter that HAS a gradient this step: its fp32 gradient slot
+ * (16-B aligned), its numel (>= 1) and the exclusive prefix sum of the numels before it; `total` = the sum of all numels.  Only
+ * [grad, grad + numel) of each span is read or written — never the arena padding or a slot whose .grad is None.  The grid of
+ * every launch depends on `total` alone: results are bit-reproducible (no float atomics).                                 */
+typedef struct tok_grad_span {
+  float* grad;
+  int64_t numel;
+  int64_t start;        /* exclusive prefix sum of the numels of the spans before this one */
+} tok_grad_span;
+#define TOK_GRAD_CLIP_MAX_PARTIALS 1024   /* fp64 partials tok_grad_sqnorm_partial writes at most (= its grid cap) */
+/* per block: the fp64 sum of squares of a fixed contiguous slice of the span space -> partials[block] (the norm pass of
+ * clip_grad_norm_: torch.linalg.vector_norm of every gradient, then of the stacked norms) */
+int tok_grad_sqnorm_partial(const tok_grad_span* spans, int n_spans, int64_t total, double* partials, void* stream);
+/* one block folds the partials of the same `total` in a fixed order: *total_norm = (float)sqrt(sum),
+ * *coef = clamp(max_norm / (*total_norm + 1e-6f), max=1) in fp32 — NaN propagates, as torch.clamp */
+int tok_grad_clip_coef(const double* partials, int64_t total, float max_norm, float* total_norm, float* coef, void* stream);
+/* every span *= *coef (device scalar: the launch can be recorded into a hipGraph); no store at all when *coef == 1 */
+int tok_grad_scale(const tok_grad_span* spans, int n_spans, int64_t total, const float* coef, void* stream);
+/* clip_grad_value_: every span = clamp(g, -clip_value, clip_value), NaN preserved (torch.clamp_) */
+int tok_grad_clamp(const tok_grad_span* spans, int n_spans, int64_t total, float clip_value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,8 @@ class BnFused(Structure):
                 ('dbeta', c_void_p), ('coef', c_void_p)]
 
 
+TOK_GRAD_CLIP_MAX_PARTIALS = 1024     # include/tok.h; a ``tok_grad_span`` table is an int64 [n, 3] device tensor (grad, numel, start)
+
 _P = c_void_p
 _PD = POINTER(ConvDesc)
 
@@ -197,6 +199,10 @@ PROTOTYPES = {
     'tok_step_advance': (c_int, [_P, _P]),
     'tok_fill_f32': (c_int, [_P, c_float, c_size_t, _P]),
     'tok_scale_f32': (c_int, [_P, c_float, c_size_t, _P]),
+    'tok_grad_sqnorm_partial': (c_int, [_P, c_int, c_int64, _P, _P]),
+    'tok_grad_clip_coef': (c_int, [_P, c_int64, c_float, _P, _P, _P]),
+    'tok_grad_scale': (c_int, [_P, c_int, c_int64, _P, _P]),
+    'tok_grad_clamp': (c_int, [_P, c_int, c_int64, c_float, _P]),
 }
 
 

@@ -101,6 +101,17 @@ class ParamArena:
         behind: the common case of a training step, recognised without a data_ptr() call), 2 some other tensor."""
         return [0 if p.grad is None else (1 if p.grad is g else 2) for p, g in zip(self.params, self.gviews)]
 
+    def adopt_grads(self):
+        """grad_flags() after every gradient held in some other tensor (flag 2) has been copied into its slot (adopt_grad):
+        the walk runs only when such a tensor exists, the common step costs the one grad_flags() pass."""
+        flags = self.grad_flags()
+        if 2 in flags:
+            for i, f in enumerate(flags):
+                if f == 2:
+                    self.adopt_grad(i)
+            flags = self.grad_flags()
+        return flags
+
     def adopt_grad(self, i: int) -> bool:
         """Make sure params[i].grad (if any) lives in the arena.  Returns False for grad None."""
         p = self.params[i]

@@ -8,20 +8,24 @@ MI355X-native answer to its per-op launch overhead — streams and graphs instea
 
 Constraints (checked where possible): static shapes; no host synchronisation inside `training_step`; scalar
 hyper-parameters are baked into the recording, so call `recapture()` after changing the learning rate; SGD, or
-Adam / AdamW built with capturable=True (device-side step count, tok_adam_step_capturable)."""
-from typing import Dict, Optional
+Adam / AdamW built with capturable=True (device-side step count, tok_adam_step_capturable).  Gradient clipping
+(`clip`, as engine.step.train_step takes it) is recorded with the step: the norm and the clip coefficient stay on the
+device, and the clip threshold (`max_norm` / `clip_value`) is baked in like the learning rate — `recapture()` after
+changing it."""
+from typing import Dict, Optional, Tuple
 
 import torch
 
 
 class GraphedTrainingStep:
-    def __init__(self, task, optimizer, example_batch: Dict[str, torch.Tensor], reducer=None, warmup: int = 3):
+    def __init__(self, task, optimizer, example_batch: Dict[str, torch.Tensor], reducer=None, warmup: int = 3,
+                 clip: Optional[Tuple[str, float]] = None):
         from ..optim.optimizers import SGD, _AdamBase
         capt = isinstance(optimizer, _AdamBase) and all(g.get('capturable', False) for g in optimizer.param_groups)
         if not isinstance(optimizer, SGD) and not capt:
             raise NotImplementedError('GraphedTrainingStep: fused SGD, or Adam / AdamW with capturable=True (the plain Adam step '
                                       'takes its step count as a host scalar, which a recording would freeze)')
-        self.task, self.optimizer, self.reducer = task, optimizer, reducer
+        self.task, self.optimizer, self.reducer, self.clip = task, optimizer, reducer, clip
         self.static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.out: Optional[Dict[str, torch.Tensor]] = None
@@ -32,7 +36,8 @@ class GraphedTrainingStep:
     def _eager(self):
         from .step import train_step
         # (on_train_batch_end's bookkeeping is host-side state: it runs outside the recording, see __call__)
-        out = train_step(self.task, self.optimizer, self.static, self._step_idx, self.reducer, batch_end_hook=False)
+        out = train_step(self.task, self.optimizer, self.static, self._step_idx, self.reducer, batch_end_hook=False,
+                         clip=self.clip)
         self._step_idx += 1
         return out
 

@@ -13,14 +13,18 @@ What of ``trainer`` (config_structure.py:136-171) is CONSUMED here, and how:
   * ``strategy: ddp`` (+ ``devices: N``): one process per GPU, `GradientAllReducer` (bucketed RCCL all-reduce overlapped
     with backward, rank-0 buffer broadcast, per-step loss mean on the comm stream).  Under torchrun the ranks already
     exist (RANK / WORLD_SIZE); otherwise ``devices: N > 1`` spawns them.  Other strategies raise.
-  * ``max_steps`` / ``max_epochs`` / ``limit_train_batches`` bound the loop; ``accumulate_grad_batches != 1``,
-    ``gradient_clip_val`` and ``sync_batchnorm: true`` raise (not built); everything else is orchestration and ignored.
+  * ``gradient_clip_val`` / ``gradient_clip_algorithm`` (``norm`` when unset, case-insensitive, or ``value``): the
+    gradients are clipped after the exchange and before ``optimizer.step()``, as Lightning's ``clip_gradients`` does
+    (torchok_amd.optim.clip_grad_norm_ / clip_grad_value_ over the optimizer's arenas).  A value of None or <= 0 turns
+    clipping off; another algorithm raises ``ValueError``.
+  * ``max_steps`` / ``max_epochs`` / ``limit_train_batches`` bound the loop; ``accumulate_grad_batches != 1`` and
+    ``sync_batchnorm: true`` raise (not built); everything else is orchestration and ignored.
 ``LitTask`` wraps a Task as a ``pytorch_lightning.LightningModule`` iff lightning is importable (it is not here)."""
 import argparse
 import logging
 import os
 import sys
-from typing import Any, Callable, Dict, Iterable, Optional
+from typing import Any, Callable, Dict, Iterable, Optional, Tuple
 
 import torch
 
@@ -62,11 +66,23 @@ def resolve_strategy(trainer: Dict[str, Any]):
         n = world_env if world_env > 1 else 1
     else:
         n = int(dev)
-    for key, bad in (('accumulate_grad_batches', lambda v: v not in (None, 1)), ('gradient_clip_val', lambda v: v),
-                     ('sync_batchnorm', lambda v: bool(v))):
+    for key, bad in (('accumulate_grad_batches', lambda v: v not in (None, 1)), ('sync_batchnorm', lambda v: bool(v))):
         if bad(trainer.get(key)):
             raise NotImplementedError(f'trainer.{key}={trainer.get(key)!r} is not built on the hot path')
     return (n > 1 or world_env > 1), n, strat == 'ddp_find_unused_parameters_true'
+
+
+def resolve_gradient_clip(trainer: Dict[str, Any]) -> Optional[Tuple[str, float]]:
+    """trainer.gradient_clip_val / gradient_clip_algorithm -> ('norm' | 'value', threshold) for engine.step.train_step, or None
+    (no clipping: the value is unset or <= 0, Lightning's early return).  An unknown algorithm raises ValueError."""
+    algo = trainer.get('gradient_clip_algorithm')
+    algo = 'norm' if algo is None else str(algo).lower()
+    if algo not in ('norm', 'value'):
+        raise ValueError(f'trainer.gradient_clip_algorithm={trainer.get("gradient_clip_algorithm")!r}: "norm" or "value"')
+    val = trainer.get('gradient_clip_val')
+    if val is None or float(val) <= 0:
+        return None
+    return algo, float(val)
 
 
 def synthetic_batches(cfg: ConfigDict, batch_size: int, device, seed: int = 0):
@@ -97,6 +113,7 @@ def fit(cfg: ConfigDict, batches: Optional[Iterable[Dict[str, torch.Tensor]]] = 
     trainer = cfg.get('trainer') or {}
     resolve_precision(trainer)
     distributed, devices, find_unused = resolve_strategy(trainer)
+    clip = resolve_gradient_clip(trainer)
     if cfg.get('seed_params'):
         torch.manual_seed(int(cfg.seed_params.get('seed', 0)))
     rank = int(os.environ.get('RANK', '0'))
@@ -135,7 +152,7 @@ def fit(cfg: ConfigDict, batches: Optional[Iterable[Dict[str, torch.Tensor]]] = 
             batch = next(it)
         except StopIteration:
             break
-        out = train_step(task, opt, batch, i, reducer)
+        out = train_step(task, opt, batch, i, reducer, clip=clip)
         done += 1
         if sched is not None and sched['interval'] == 'step' and (i + 1) % sched['frequency'] == 0 \
                 and type(sched['scheduler']).__name__ != 'ReduceLROnPlateau':
