@@ -654,6 +654,37 @@ int tok_dwconv3x3_wgrad_blocks(int n, int h);
 int tok_dwconv3x3_wgrad(const void* x, const void* dout, int n, int h, int wd, int c, int ld, float* partial, float* dw,
                         float* db, int accumulate, void* stream);
 
+/* ---- MnasNet depthwise unit and squeeze-excite ([timm] efficientnet_blocks.DepthwiseSeparableConv / InvertedResidual /
+ * SqueezeExcite, reached from efficientnet.py:506-681) ----------------------------------------------------------------------
+ * Depthwise k x k convolution without bias, k in {3, 5}, stride in {1, 2}, symmetric padding k / 2, any h and w.
+ * x / out / dout / dx bf16 NHWC [n][h][w][ld] (c % 8 == 0, ld >= c, ld % 8 == 0; one pitch for every tensor of a call), w the fp32
+ * master [c][k][k] (a (C,1,k,k) tensor in either memory format).  Output size p = (h - 1) / stride + 1, likewise q.
+ * tok_dwconv_fwd: out = conv(x); stats (nullable) = per-channel (sum, sum of squares) of the ROUNDED output, fp32
+ *   [2][tok_dwconv_rows(...)][c] — the partial rows tok_bn_finalize folds (no separate statistics pass).
+ * tok_dwconv_dgrad: dx (=|+=) the transposed correlation of dout (h, wd: the size of dx; stride 2 takes per-parity taps).
+ * tok_dwconv_wgrad: dw fp32 [c][k][k] (=|+=); ws fp32 workspace of tok_dwconv_wgrad_ws_bytes(...) bytes: per-block partial
+ *   sums, folded in a fixed order.  Every reduction is bit-reproducible (no float atomics).                                  */
+int tok_dwconv_rows(int n, int h, int wd, int c, int k, int stride);
+int tok_dwconv_fwd(const void* x, const float* w, int n, int h, int wd, int c, int ld, int k, int stride, void* out,
+                   float* stats, void* stream);
+int tok_dwconv_dgrad(const void* dout, const float* w, int n, int h, int wd, int c, int ld, int k, int stride, void* dx,
+                     int accumulate, void* stream);
+size_t tok_dwconv_wgrad_ws_bytes(int n, int h, int wd, int c, int k, int stride);
+int tok_dwconv_wgrad(const void* x, const void* dout, int n, int h, int wd, int c, int ld, int k, int stride, float* dw,
+                     int accumulate, float* ws, size_t ws_bytes, void* stream);
+/* Squeeze-excite gate s[n][c] = sigmoid(b2 + W2 relu(b1 + W1 mean_hw(x[n]))); the product x * s is tok_channel_scale.
+ * x / dout / dx bf16 [n][hw][ld] (c % 8 == 0, c <= 2048), W1 fp32 [rd][c] (conv_reduce), W2 fp32 [c][rd] (conv_expand),
+ * 1 <= rd <= 256.  tok_se_fwd writes mean fp32 [n][c], hid fp32 [n][rd] (after the ReLU) and gate fp32 [n][c]: what
+ * tok_se_bwd reads.  ws: fp32 scratch of tok_se_ws_floats(...) floats (both directions).
+ * tok_se_bwd (dout = d(x * s)): dW1, db1, dW2, db2 (each nullable; summed over the images in a fixed order; bit 0 / 1 / 2 / 3 of
+ * param_accumulate: += instead of =) and dx (nullable) (=|+=) dout * s + d(mean) / hw.                                    */
+size_t tok_se_ws_floats(int n, int hw, int c, int rd);
+int tok_se_fwd(const void* x, int n, int hw, int c, int ld, int rd, const float* w1, const float* b1, const float* w2,
+               const float* b2, float* mean, float* hid, float* gate, float* ws, void* stream);
+int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, const float* w1, const float* w2,
+               const float* mean, const float* hid, const float* gate, float* dw1, float* db1, float* dw2, float* db2,
+               int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
+
 /* ---- retrieval meters (validation path) -------------------------------------------------------
  * IndexBasedMeter.compute (metrics/index_base_metric.py:170-270) with exact_index=True: the faiss flat index
  * (:523-545) is an exhaustive search = similarity matrix + k best per row; the ranx metric functions bound by

@@ -185,6 +185,15 @@ PROTOTYPES = {
     'tok_dwconv3x3': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'tok_dwconv3x3_wgrad_blocks': (c_int, [c_int, c_int]),
     'tok_dwconv3x3_wgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
+    'tok_dwconv_rows': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    'tok_dwconv_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    'tok_dwconv_dgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    'tok_dwconv_wgrad_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    'tok_dwconv_wgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    'tok_se_ws_floats': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'tok_se_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'tok_se_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int,
+                           _P, _P]),
     'tok_sim_matrix': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P]),
     'tok_topk_rows': (c_int, [_P, c_int, c_int, c_int64, c_int, _P, _P, _P]),
     'tok_retrieval_nrel': (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),

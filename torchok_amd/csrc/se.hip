@@ -1,0 +1,258 @@
+// Squeeze-excite of the MnasNet-A1 blocks ([timm] efficientnet_blocks.SqueezeExcite with ReLU and a sigmoid gate):
+//   s[n][c] = sigmoid(b2 + W2 relu(b1 + W1 mean_hw(x[n])))      out = x * s   (the product: tok_channel_scale)
+// x / dout / dx bf16 [n][hw][ld] (c % 8 == 0), W1 fp32 [rd][c] (conv_reduce), W2 fp32 [c][rd] (conv_expand), 1 <= rd <= 256.
+//
+// Forward : per-(image, chunk) channel sums -> one block per image folds them in chunk order and runs the two 1x1 layers.
+// Backward: per-(image, chunk) sums of dout * x (= d(out)/ds) -> one block per image: ds, d(hidden), d(mean) -> the four
+//           parameter gradients summed over the images in image order -> dx (=|+=) dout * s + d(mean) / hw in one pass.
+// Every sum folds in a fixed order (no float atomics): bit-reproducible run to run.
+#include "tok_common.h"
+
+namespace {
+
+constexpr int kCap = 2048;        // workgroups of the streaming launches
+constexpr int kMaxC = 2048;       // channels one image block keeps in LDS
+constexpr int kMaxRd = 256;
+
+struct SeGeo {
+  int cge, rpb, chunks;
+};
+
+SeGeo se_geo(int n, int hw, int c) {
+  SeGeo g;
+  g.cge = (c >> 3) < 256 ? (c >> 3) : 256;
+  g.rpb = 256 / g.cge;
+  int want = (hw + 4 * g.rpb - 1) / (4 * g.rpb);        // at least 4 rows per lane
+  const int cap = (kCap + n - 1) / n;
+  if (want > cap) want = cap;
+  g.chunks = want < 1 ? 1 : want;
+  return g;
+}
+
+// part[img][chunk][c] = sum over the chunk's pixels of a (* b when b != NULL)
+__global__ __launch_bounds__(256) void se_sum_kernel(const bf16* __restrict__ a, const bf16* __restrict__ b, int hw, int C,
+                                                     int ld, int cge, int rpb, float* __restrict__ part) {
+  __shared__ float red[256][8];
+  const int tid = threadIdx.x, cgl = tid % cge, rl = tid / cge;
+  const int img = blockIdx.y, chunk = blockIdx.x, chunks = gridDim.x;
+  const int len = (hw + chunks - 1) / chunks;
+  const int p0 = chunk * len, p1 = p0 + len < hw ? p0 + len : hw;
+  for (int cg = cgl; cg < (C >> 3); cg += cge) {     // (same trip count in every lane: cge divides the groups or one pass)
+    float s[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = 0.f;
+    if (rl < rpb) {
+      for (int p = p0 + rl; p < p1; p += rpb) {
+        const size_t off = ((size_t)img * hw + p) * ld + cg * 8;
+        const bf16x8 va = ldg16(a + off);
+        if (b != nullptr) {
+          const bf16x8 vb = ldg16(b + off);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s[e] = fmaf(bf2f(va[e]), bf2f(vb[e]), s[e]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s[e] += bf2f(va[e]);
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[tid][e] = s[e];
+    __syncthreads();
+    if (rl == 0) {
+      for (int r = 1; r < rpb; ++r)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] += red[r * cge + cgl][e];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) part[((size_t)img * chunks + chunk) * C + cg * 8 + e] = s[e];
+    }
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + __expf(-v)); }
+
+// one block per image: mean, hidden = relu(W1 mean + b1), gate = sigmoid(W2 hidden + b2)
+__global__ __launch_bounds__(256) void se_fwd_image_kernel(const float* __restrict__ part, int chunks, int hw, int C, int rd,
+                                                           const float* __restrict__ w1, const float* __restrict__ b1,
+                                                           const float* __restrict__ w2, const float* __restrict__ b2,
+                                                           float* __restrict__ mean, float* __restrict__ hid,
+                                                           float* __restrict__ gate) {
+  __shared__ float m[kMaxC];
+  __shared__ float h[kMaxRd];
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float inv = 1.f / (float)hw;
+  for (int c = tid; c < C; c += 256) {
+    float a = 0.f;
+    for (int k = 0; k < chunks; ++k) a += part[((size_t)img * chunks + k) * C + c];
+    m[c] = a * inv;
+    mean[(size_t)img * C + c] = a * inv;
+  }
+  __syncthreads();
+  for (int j = wave; j < rd; j += 4) {
+    float a = 0.f;
+    for (int c = lane; c < C; c += 64) a = fmaf(w1[(size_t)j * C + c], m[c], a);
+    a = wave_sum(a);
+    if (lane == 0) {
+      const float v = fmaxf(a + b1[j], 0.f);
+      h[j] = v;
+      hid[(size_t)img * rd + j] = v;
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float a = b2[c];
+    for (int j = 0; j < rd; ++j) a = fmaf(w2[(size_t)c * rd + j], h[j], a);
+    gate[(size_t)img * C + c] = sigmoid_f(a);
+  }
+}
+
+// one block per image: ds = g s (1 - s), dh = relu'(hidden) W2^T ds, dmean = W1^T dh
+__global__ __launch_bounds__(256) void se_bwd_image_kernel(const float* __restrict__ part, int chunks, int C, int rd,
+                                                           const float* __restrict__ w1, const float* __restrict__ w2,
+                                                           const float* __restrict__ hid, const float* __restrict__ gate,
+                                                           float* __restrict__ ds_out, float* __restrict__ dh_out,
+                                                           float* __restrict__ dmean) {
+  __shared__ float ds[kMaxC];
+  __shared__ float dh[kMaxRd];
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int c = tid; c < C; c += 256) {
+    float a = 0.f;
+    for (int k = 0; k < chunks; ++k) a += part[((size_t)img * chunks + k) * C + c];
+    const float s = gate[(size_t)img * C + c];
+    const float d = a * s * (1.f - s);
+    ds[c] = d;
+    ds_out[(size_t)img * C + c] = d;
+  }
+  __syncthreads();
+  for (int j = wave; j < rd; j += 4) {
+    float a = 0.f;
+    for (int c = lane; c < C; c += 64) a = fmaf(w2[(size_t)c * rd + j], ds[c], a);
+    a = wave_sum(a);
+    if (lane == 0) {
+      const float v = hid[(size_t)img * rd + j] > 0.f ? a : 0.f;
+      dh[j] = v;
+      dh_out[(size_t)img * rd + j] = v;
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float a = 0.f;
+    for (int j = 0; j < rd; ++j) a = fmaf(w1[(size_t)j * C + c], dh[j], a);
+    dmean[(size_t)img * C + c] = a;
+  }
+}
+
+// the four parameter gradients, each element summed over the images in image order:
+//   dw2[c][j] = sum_n ds[n][c] hid[n][j]   db2[c] = sum_n ds[n][c]   dw1[j][c] = sum_n dh[n][j] mean[n][c]   db1[j] = sum_n dh[n][j]
+__global__ __launch_bounds__(256) void se_param_grad_kernel(const float* __restrict__ ds, const float* __restrict__ dh,
+                                                            const float* __restrict__ hid, const float* __restrict__ mean,
+                                                            int N, int C, int rd, float* dw1, float* db1, float* dw2, float* db2,
+                                                            int acc) {
+  const int n_w = C * rd;
+  const int total = 2 * n_w + C + rd;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    float a = 0.f;
+    float* dst;
+    int bit;
+    if (i < n_w) {                        // dw2 [c][j]
+      const int c = i / rd, j = i % rd;
+      for (int n = 0; n < N; ++n) a = fmaf(ds[(size_t)n * C + c], hid[(size_t)n * rd + j], a);
+      dst = dw2 ? dw2 + i : nullptr;
+      bit = 4;
+    } else if (i < 2 * n_w) {             // dw1 [j][c]
+      const int k = i - n_w, j = k / C, c = k % C;
+      for (int n = 0; n < N; ++n) a = fmaf(dh[(size_t)n * rd + j], mean[(size_t)n * C + c], a);
+      dst = dw1 ? dw1 + k : nullptr;
+      bit = 1;
+    } else if (i < 2 * n_w + C) {         // db2 [c]
+      const int c = i - 2 * n_w;
+      for (int n = 0; n < N; ++n) a += ds[(size_t)n * C + c];
+      dst = db2 ? db2 + c : nullptr;
+      bit = 8;
+    } else {                              // db1 [j]
+      const int j = i - 2 * n_w - C;
+      for (int n = 0; n < N; ++n) a += dh[(size_t)n * rd + j];
+      dst = db1 ? db1 + j : nullptr;
+      bit = 2;
+    }
+    if (dst != nullptr) *dst = (acc & bit) ? *dst + a : a;
+  }
+}
+
+// dx (=|+=) dout * s[n][c] + dmean[n][c] / hw
+__global__ __launch_bounds__(256) void se_dx_kernel(const bf16* __restrict__ dout, const float* __restrict__ gate,
+                                                    const float* __restrict__ dmean, int N, int hw, int C, int ld, bf16* dx,
+                                                    int accumulate) {
+  const int cgs = C >> 3;
+  const size_t total = (size_t)N * hw * cgs;
+  const float inv = 1.f / (float)hw;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int cg = (int)(i % cgs);
+    const size_t row = i / cgs;
+    const int img = (int)(row / hw);
+    const size_t off = row * ld + cg * 8;
+    const bf16x8 g = ldg16(dout + off);
+    const bf16x8 old = accumulate ? ldg16(dx + off) : zero8();
+    const float* sv = gate + (size_t)img * C + cg * 8;
+    const float* mv = dmean + (size_t)img * C + cg * 8;
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = f2bf(fmaf(bf2f(g[e]), sv[e], fmaf(mv[e], inv, bf2f(old[e]))));
+    stg16(dx + off, o);
+  }
+}
+
+bool se_args_ok(int n, int hw, int c, int ld, int rd) {
+  return n > 0 && n <= 65535 && hw > 0 && c > 0 && c % 8 == 0 && c <= kMaxC && ld >= c && ld % 8 == 0 && rd >= 1 &&
+         rd <= kMaxRd;
+}
+
+int blocks_for(size_t work) {
+  size_t b = (work + 255) / 256;
+  return (int)(b < (size_t)kCap ? (b < 1 ? 1 : b) : kCap);
+}
+
+}  // namespace
+
+extern "C" size_t tok_se_ws_floats(int n, int hw, int c, int rd) {
+  if (!se_args_ok(n, hw, c, c, rd)) return 0;
+  const SeGeo g = se_geo(n, hw, c);
+  return (size_t)n * g.chunks * c + 2 * (size_t)n * c + (size_t)n * rd;
+}
+
+extern "C" int tok_se_fwd(const void* x, int n, int hw, int c, int ld, int rd, const float* w1, const float* b1, const float* w2,
+                          const float* b2, float* mean, float* hid, float* gate, float* ws, void* stream) {
+  TOK_CHECK_ARG(x && w1 && b1 && w2 && b2 && mean && hid && gate && ws, "tok_se_fwd: null pointer");
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_fwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+  const SeGeo g = se_geo(n, hw, c);
+  hipStream_t st = tok_stream(stream);
+  hipLaunchKernelGGL(se_sum_kernel, dim3(g.chunks, n), dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, hw, c, ld, g.cge,
+                     g.rpb, ws);
+  hipLaunchKernelGGL(se_fwd_image_kernel, dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid, gate);
+  TOK_CHECK_LAUNCH("tok_se_fwd");
+  return TOK_OK;
+}
+
+extern "C" int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, const float* w1,
+                          const float* w2, const float* mean, const float* hid, const float* gate, float* dw1, float* db1,
+                          float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream) {
+  TOK_CHECK_ARG(dout && x && w1 && w2 && mean && hid && gate && ws, "tok_se_bwd: null pointer");
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_bwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+  const SeGeo g = se_geo(n, hw, c);
+  hipStream_t st = tok_stream(stream);
+  float* part = ws;
+  float* ds = part + (size_t)n * g.chunks * c;
+  float* dmean = ds + (size_t)n * c;
+  float* dh = dmean + (size_t)n * c;
+  hipLaunchKernelGGL(se_sum_kernel, dim3(g.chunks, n), dim3(256), 0, st, (const bf16*)dout, (const bf16*)x, hw, c, ld, g.cge,
+                     g.rpb, part);
+  hipLaunchKernelGGL(se_bwd_image_kernel, dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh, dmean);
+  if (dw1 || db1 || dw2 || db2)
+    hipLaunchKernelGGL(se_param_grad_kernel, dim3(blocks_for(2 * (size_t)c * rd + c + rd)), dim3(256), 0, st, ds, dh, hid, mean,
+                       n, c, rd, dw1, db1, dw2, db2, param_accumulate);
+  if (dx != nullptr)
+    hipLaunchKernelGGL(se_dx_kernel, dim3(blocks_for((size_t)n * hw * (c >> 3))), dim3(256), 0, st, (const bf16*)dout, gate,
+                       dmean, n, hw, c, ld, (bf16*)dx, dx_accumulate);
+  TOK_CHECK_LAUNCH("tok_se_bwd");
+  return TOK_OK;
+}

@@ -8,6 +8,8 @@ conv_bn_act               conv2d -> batch_norm -> (+ shortcut) -> relu   ([timm]
 max_pool_3x3_s2           nn.MaxPool2d(3, 2, 1)                          (resnet.py:510)
 global_avg_pool           SelectAdaptivePool2d('avg', flatten=True)      (pooling.py:7-12)
 linear                    nn.Linear                                      (linear_head.py:31)
+dwconv_bn_act             depthwise conv -> batch_norm -> relu           ([timm] DepthwiseSeparableConv / InvertedResidual)
+squeeze_excite            x * sigmoid(expand(relu(reduce(mean(x)))))     ([timm] efficientnet_blocks.SqueezeExcite)
 """
 import weakref
 from typing import Optional
@@ -1118,5 +1120,194 @@ def global_pool(region: Region, x: TTensor, pool_type: str) -> TTensor:
         node.x, node.out, node.argmax, node.mode = x, out, argmax, mode
         out.node = node
         x.uses += 1
+        region.add(node)
+    return out
+
+
+# ---- depthwise conv + bn + relu (MnasNet) --------------------------------------------------------------------------------
+
+def _check_dwconv(conv: nn.Conv2d, x: TTensor):
+    k = conv.kernel_size[0]
+    if (conv.groups != conv.in_channels or conv.out_channels != conv.in_channels or conv.bias is not None
+            or conv.kernel_size != (k, k) or k not in (3, 5) or tuple(conv.stride) not in ((1, 1), (2, 2))
+            or tuple(conv.padding) != (k // 2, k // 2) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != 'zeros'):
+        raise NotImplementedError('torchok_amd depthwise conv: groups == channels, no bias, k in {3, 5}, stride 1 or 2, '
+                                  'padding k // 2, no dilation')
+    if x.data.dim() != 4 or x.c != x.cp or x.c != conv.in_channels:
+        raise NotImplementedError('torchok_amd depthwise conv: a 4-D input whose channel count is a multiple of 8')
+
+
+class _DwConvBnActNode(_ConvBnActNode):
+    """relu(bn(depthwise_conv(x))).  The BatchNorm backward is the one of _ConvBnActNode (tok_bn_bwd_*; a consumer conv's data
+    gradient may reduce its sums, see wants_fused_bwd_stats); then tok_dwconv_wgrad / tok_dwconv_dgrad on dy."""
+
+    def backward(self):
+        lib, st = _C.lib(), stream_ptr()
+        out: TTensor = self.out
+        g = out.grad
+        if g is None:
+            return
+        conv, bn, x = self.conv, self.bn, self.x
+        n, h, w, c = x.shape
+        k, stride = conv.kernel_size[0], conv.stride[0]
+        m, kp = self.y.numel() // self.y.shape[-1], self.y.shape[-1]
+        w_need, x_need = conv.weight.requires_grad, x.requires_grad
+        mask = self.mask if self.relu else None
+        if self.batch_stats:
+            if self.fused_coef is not None:
+                coef = self.fused_coef
+            else:
+                self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
+                coef = self.coef
+        else:
+            if bn.weight.requires_grad or bn.bias.requires_grad:
+                raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')
+            coef = torch.zeros((3, kp), dtype=F32, device=g.device)
+            coef[0] = self.scale
+        out.grad = None
+        if not (w_need or x_need):
+            return
+        dy = torch.empty_like(self.y)
+        _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift), ptr(coef),
+                                      int(self.relu), ptr(dy), None, 0, m, kp, st), 'tok_bn_bwd_apply')
+        if w_need:
+            ws_bytes = lib.tok_dwconv_wgrad_ws_bytes(n, h, w, c, k, stride)
+            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
+            slot, mode = param_grad_target(conv.weight)
+            _C.check(lib.tok_dwconv_wgrad(ptr(x.data), ptr(dy), n, h, w, c, c, k, stride, ptr(slot), 1 if mode == 1 else 0,
+                                          ptr(ws), ws_bytes, st), 'tok_dwconv_wgrad')
+            commit_param_grad(conv.weight, slot, mode)
+        if x_need:
+            tgt, acc = grad_target(x)
+            _C.check(lib.tok_dwconv_dgrad(ptr(dy), ptr(conv.weight), n, h, w, c, c, k, stride, ptr(tgt), acc, st),
+                     'tok_dwconv_dgrad')
+
+
+def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True) -> TTensor:
+    """out = act(bn(conv(x))) for a depthwise `conv` ([timm] create_conv2d(depthwise=True) + BatchNormAct2d of the MnasNet
+    blocks).  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
+    rows tok_bn_finalize folds); eval mode uses the running statistics; track_running_stats=False uses batch statistics."""
+    await_ready(x)
+    _check_dwconv(conv, x)
+    if bn.num_features != conv.out_channels:
+        raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {conv.out_channels}')
+    lib, st = _C.lib(), stream_ptr()
+    n, h, w, c = x.shape
+    k, stride = conv.kernel_size[0], conv.stride[0]
+    p, q = (h - 1) // stride + 1, (w - 1) // stride + 1
+    dev = x.data.device
+    batch_stats = bn.training or bn.running_mean is None
+    y = torch.empty((n, p, q, c), dtype=BF16, device=dev)
+    stats, rows = None, 0
+    if batch_stats:
+        if bn.momentum is None:
+            raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
+        rows = lib.tok_dwconv_rows(n, h, w, c, k, stride)
+        stats = torch.empty((2, rows, c), dtype=F32, device=dev)
+    _C.check(lib.tok_dwconv_fwd(ptr(x.data), ptr(conv.weight), n, h, w, c, c, k, stride, ptr(y), ptr(stats), st),
+             'tok_dwconv_fwd')
+    vec = torch.empty((4, c), dtype=F32, device=dev)
+    scale, shift = vec[0], vec[1]
+    mean = rstd = None
+    m = n * p * q
+    if batch_stats:
+        mean, rstd = vec[2], vec[3]
+        track = bn.training and bn.track_running_stats and bn.running_mean is not None
+        _C.check(lib.tok_bn_finalize(ptr(stats), rows, m, c, c, ptr(bn.weight), ptr(bn.bias),
+                                     ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
+                                     ptr(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps),
+                                     ptr(mean), ptr(rstd), ptr(scale), ptr(shift), st), 'tok_bn_finalize')
+    else:
+        _C.check(lib.tok_bn_eval_coeffs(ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+                                        float(bn.eps), c, c, ptr(scale), ptr(shift), st), 'tok_bn_eval_coeffs')
+    training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad
+                                     or bn.bias.requires_grad)
+    mask = torch.empty((m, c // 8), dtype=torch.uint8, device=dev) if (relu and training) else None
+    out_data = torch.empty_like(y)
+    _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), None, int(relu), ptr(out_data), ptr(mask), m, c, st),
+             'tok_bn_act_fwd')
+    out = TTensor(out_data, c, requires_grad=bool(training))
+    if training:
+        node = _DwConvBnActNode()
+        node.x, node.out, node.y, node.mask = x, out, y, mask
+        node.conv, node.bn, node.relu, node.batch_stats = conv, bn, relu, batch_stats
+        node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
+        out.node = node
+        if x.requires_grad:
+            x.uses += 1
+        region.add(node)
+    return out
+
+
+# ---- squeeze-excite (MnasNet-A1) -----------------------------------------------------------------------------------------
+
+class _SqueezeExciteNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        g = self.out.grad
+        if g is None:
+            return
+        self.out.grad = None
+        se, x = self.se, self.x
+        lib = _C.lib()
+        n, h, w, c = x.shape
+        rd = se.conv_reduce.out_channels
+        prm = (se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias)
+        targets, acc_bits = [], 0
+        for bit, p in enumerate(prm):
+            if p.requires_grad:
+                slot, mode = param_grad_target(p)
+                targets.append((p, slot, mode))
+                acc_bits |= (1 << bit) if mode == 1 else 0
+            else:
+                targets.append((p, None, 0))
+        dx, dx_acc = grad_target(x) if x.requires_grad else (None, 0)
+        ws = torch.empty(lib.tok_se_ws_floats(n, h * w, c, rd), dtype=F32, device=g.device)
+        _C.check(lib.tok_se_bwd(ptr(g), ptr(x.data), n, h * w, c, c, rd, ptr(prm[0]), ptr(prm[2]), ptr(self.mean),
+                                ptr(self.hid), ptr(self.gate), *(ptr(t[1]) for t in targets), acc_bits, ptr(dx), dx_acc,
+                                ptr(ws), stream_ptr()), 'tok_se_bwd')
+        for p, slot, mode in targets:
+            if slot is not None:
+                commit_param_grad(p, slot, mode)
+        if self.region is not None:
+            self.region.keep_until_join(ws)
+
+    def release(self):
+        self.x = self.out = self.mean = self.hid = self.gate = None
+
+
+def squeeze_excite(region: Region, x: TTensor, se: nn.Module) -> TTensor:
+    """x * sigmoid(conv_expand(relu(conv_reduce(mean_hw(x)))))  ([timm] efficientnet_blocks.SqueezeExcite with ReLU and the
+    sigmoid gate).  `se` holds conv_reduce / conv_expand (1x1, with bias) as parameter containers."""
+    await_ready(x)
+    red, exp = se.conv_reduce, se.conv_expand
+    if x.data.dim() != 4 or x.c != x.cp or red.in_channels != x.c or exp.out_channels != x.c \
+            or red.out_channels != exp.in_channels or red.bias is None or exp.bias is None:
+        raise NotImplementedError('torchok_amd squeeze-excite: 1x1 convs with bias around a 4-D input of 8k channels')
+    lib, st = _C.lib(), stream_ptr()
+    n, h, w, c = x.shape
+    rd = red.out_channels
+    dev = x.data.device
+    w1, w2 = red.weight, exp.weight
+    if not (w1.is_contiguous() or w1.permute(0, 2, 3, 1).is_contiguous()) or \
+            not (w2.is_contiguous() or w2.permute(0, 2, 3, 1).is_contiguous()):
+        raise NotImplementedError('torchok_amd squeeze-excite: dense 1x1 weights')
+    mean = torch.empty((n, c), dtype=F32, device=dev)
+    hid = torch.empty((n, rd), dtype=F32, device=dev)
+    gate = torch.empty((n, c), dtype=F32, device=dev)
+    ws = torch.empty(lib.tok_se_ws_floats(n, h * w, c, rd), dtype=F32, device=dev)
+    _C.check(lib.tok_se_fwd(ptr(x.data), n, h * w, c, c, rd, ptr(w1), ptr(red.bias), ptr(w2), ptr(exp.bias), ptr(mean),
+                            ptr(hid), ptr(gate), ptr(ws), st), 'tok_se_fwd')
+    out_data = torch.empty_like(x.data)
+    _C.check(lib.tok_channel_scale(ptr(x.data), ptr(gate), ptr(out_data), 0, n, h * w, c, c, st), 'tok_channel_scale')
+    req = region.grad_mode and (x.requires_grad or any(p.requires_grad for p in se.parameters()))
+    out = TTensor(out_data, c, requires_grad=bool(req))
+    if req:
+        node = _SqueezeExciteNode()
+        node.x, node.out, node.se, node.mean, node.hid, node.gate = x, out, se, mean, hid, gate
+        out.node = node
+        if x.requires_grad:
+            x.uses += 1
         region.add(node)
     return out
