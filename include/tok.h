@@ -685,6 +685,40 @@ int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, in
                const float* mean, const float* hid, const float* gate, float* dw1, float* db1, float* dw2, float* db2,
                int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
 
+/* ---- Vision Transformer: global self-attention and token embedding ([timm 0.6.13] vision_transformer.Attention.forward,
+ * PatchEmbed, VisionTransformer._pos_embed; reached from torchok/models/backbones/vit.py:202-357) -------------------------------
+ * tok_global_attn_fwd: per (image, head) O = softmax(Q K^T * 64^-0.5) V over all n tokens.  qkv bf16 [batch*n][ldq], columns
+ *   (3, heads, 64) as timm's qkv.reshape(B, N, 3, H, 64); out bf16 [batch*n][ldo] at column h*64 + d (timm's
+ *   transpose(1, 2).reshape(B, N, C)); lse fp32 [batch][heads][n] = the natural-log row log-sum-exp of the scaled logits.
+ *   head_dim == 64 only, 1 <= n <= TOK_GLOBAL_ATTN_MAX_TOKENS, ldq / ldo multiples of 8 (>= 3C / C): TOK_ERR_INVALID otherwise.
+ * tok_global_attn_bwd: dq, dk, dv into dqkv bf16 [batch*n][ldd] (the layout of qkv; columns past 3C untouched), recomputing P
+ *   from qkv and lse; out / dout share the pitch ldo.  ws: tok_global_attn_bwd_ws_bytes(...) bytes (row sums of dout * out).
+ *   No float atomics: bit-reproducible.                                                                                       */
+#define TOK_GLOBAL_ATTN_MAX_TOKENS 4096
+int tok_global_attn_fwd(const void* qkv, int ldq, int batch, int n, int heads, int head_dim, void* out, int ldo, float* lse,
+                        void* stream);
+size_t tok_global_attn_bwd_ws_bytes(int batch, int n, int heads);
+int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse, int batch, int n,
+                        int heads, int head_dim, void* dqkv, int ldd, void* ws, size_t ws_bytes, void* stream);
+/* Patch embedding as a GEMM: img NHWC bf16 [n][h][w][4] (3 channels zero-padded to 4) -> rows bf16 [n*(h/p)*(w/p)][p*p*4],
+ * element (py, px, c) of a row at (py*p + px)*4 + c — the k = p, stride = p convolution is then a 1x1 layer against the
+ * [D][p][p][4] weight pack.  h, w multiples of p.                                                                             */
+int tok_patch_gather(const void* img, int n, int h, int w, int p, void* rows, void* stream);
+/* Token assembly, rounded once to bf16: out [batch*T][d] with T = patches + (cls != NULL);
+ *   default:          out[b][0] = cls + pos[0],  out[b][1+i] = patch[b][i] + pos[1+i]
+ *   no_embed_class:   out[b][0] = cls,           out[b][1+i] = patch[b][i] + pos[i]        (no cls: out[b][i] = patch + pos[i])
+ * patch bf16 [batch*patches][d], pos / cls fp32.  tok_vit_embed_bwd: d(pos) / d(cls) (each nullable; =|+= per *_acc) as sums over
+ * the images in image order (no float atomics); d(patch) is tok_rows_select of dout.                                          */
+int tok_vit_embed_fwd(const void* patch, const float* pos, const float* cls, int batch, int patches, int d, int no_embed_class,
+                      void* out, void* stream);
+int tok_vit_embed_bwd(const void* dout, int batch, int patches, int d, int has_cls, int no_embed_class, float* dpos, int pos_acc,
+                      float* dcls, int cls_acc, void* stream);
+/* Rows [first, first + count) of every image's t token rows (bf16, pitch d, d % 8 == 0).  dir 0: dst [batch*count][d] = those
+ * rows of src [batch*t][d].  dir 1 (the transpose): dst [batch*t][d] receives src [batch*count][d] in those rows (+= with
+ * accumulate) and 0 in the others (left as they are with accumulate).                                                         */
+int tok_rows_select(const void* src, int batch, int t, int first, int count, int d, void* dst, int dir, int accumulate,
+                    void* stream);
+
 /* ---- retrieval meters (validation path) -------------------------------------------------------
  * IndexBasedMeter.compute (metrics/index_base_metric.py:170-270) with exact_index=True: the faiss flat index
  * (:523-545) is an exhaustive search = similarity matrix + k best per row; the ranx metric functions bound by

@@ -194,6 +194,13 @@ PROTOTYPES = {
     'tok_se_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tok_se_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int,
                            _P, _P]),
+    'tok_global_attn_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
+    'tok_global_attn_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'tok_global_attn_bwd': (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    'tok_patch_gather': (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    'tok_vit_embed_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    'tok_vit_embed_bwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P]),
+    'tok_rows_select': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P]),
     'tok_sim_matrix': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P]),
     'tok_topk_rows': (c_int, [_P, c_int, c_int, c_int64, c_int, _P, _P, _P]),
     'tok_retrieval_nrel': (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, _P]),

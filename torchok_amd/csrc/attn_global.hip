@@ -1,0 +1,519 @@
+// Global (whole-image) multi-head self-attention of the Vision Transformer and its token-embedding helpers.
+//
+// [timm 0.6.13] vision_transformer.Attention.forward between qkv and proj:
+//   q, k, v = qkv.reshape(B, N, 3, H, 64).permute(2, 0, 3, 1, 4);  O = softmax(q k^T * 64^-0.5) v;  O.transpose(1, 2).reshape(B, N, C)
+// qkv rows bf16 [B*N][ldq] with columns (3, heads, 64); O rows bf16 [B*N][ldo] at column h*64 + d; lse fp32 [B][H][N] (natural log).
+//
+// Forward : one workgroup per (image, head, 64-query tile), one wave per 16 queries.  K / V tiles of 64 keys are staged in LDS (V
+//           transposed), S = Q K^T and O += P V on mfma_f32_16x16x32_bf16, online fp32 softmax in exp2 units, key tail masked.
+// Backward: delta = rowsum(dO o O) (pre-pass); dK / dV per (image, head, 64-key tile), dQ per (image, head, 64-query tile), each
+//           recomputing P from Q, K and the LSE.  Every output element is written by exactly one lane and every sum runs in a fixed
+//           order: no float atomics, bit-reproducible run to run.
+#include "tok_common.h"
+
+namespace {
+
+constexpr int HD = 64;         // head_dim served
+constexpr int TL = 64;         // tokens per tile (queries of a workgroup, keys per staged tile)
+constexpr int PT = 72;         // LDS row pitch in bf16 (144 B: 16-B aligned rows)
+constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+constexpr float SCALE = 0.125f;  // 64^-0.5
+
+__device__ __forceinline__ bf16x8 lds8(const bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
+
+// rows [r0, r0 + 64) of the 64-wide column block `col` of a token matrix -> LDS row-major [row][PT] and/or transposed [d][PT];
+// rows past n are zero
+__device__ __forceinline__ void stage_tile(const bf16* __restrict__ base, int ld, int col, int r0, int n, bf16* rm, bf16* tr) {
+  for (int c = threadIdx.x; c < TL * (HD / 8); c += 256) {
+    const int row = c >> 3, d0 = (c & 7) * 8, gr = r0 + row;
+    const bf16x8 v = gr < n ? ldg16(base + (size_t)gr * ld + col + d0) : zero8();
+    if (rm) *reinterpret_cast<bf16x8*>(rm + row * PT + d0) = v;
+    if (tr) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) tr[(d0 + j) * PT + row] = v[j];
+    }
+  }
+}
+
+__device__ __forceinline__ float max16(float v) {
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float sum16(float v) {
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void gattn_fwd_kernel(const bf16* __restrict__ qkv, int ldq, int N, int H,
+                                                        bf16* __restrict__ out, int ldo, float* __restrict__ lse) {
+  __shared__ __attribute__((aligned(16))) bf16 ks[TL * PT];        // K [key][d]
+  __shared__ __attribute__((aligned(16))) bf16 vt[HD * PT];        // V^T [d][key]
+  __shared__ __attribute__((aligned(16))) bf16 ps[4][16 * PT];     // per wave: P [query][key]
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
+  const int b = blockIdx.y / H, h = blockIdx.y % H, C = H * HD;
+  const int q0 = blockIdx.x * TL + wv * 16;
+  const bf16* base = qkv + (size_t)b * N * ldq;
+  bf16x8 qf[2];
+  {
+    const int qr = q0 + l15;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) qf[s] = qr < N ? ldg16(base + (size_t)qr * ldq + h * HD + 32 * s + 8 * g) : zero8();
+  }
+  float m[4], l[4];
+  f32x4 o[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    m[r] = -INFINITY;
+    l[r] = 0.f;
+    o[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  const float sc = SCALE * LOG2E;
+  for (int k0 = 0; k0 < N; k0 += TL) {
+    __syncthreads();                                    // the previous tile has been consumed by every wave
+    stage_tile(base, ldq, C + h * HD, k0, N, ks, nullptr);
+    stage_tile(base, ldq, 2 * C + h * HD, k0, N, nullptr, vt);
+    __syncthreads();
+    f32x4 s[4];
+#pragma unroll
+    for (int kj = 0; kj < 4; ++kj) {
+      s[kj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) s[kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t], lds8(ks + (kj * 16 + l15) * PT + 32 * t + 8 * g), s[kj], 0, 0, 0);
+    }
+    // element (kj, r): query 4g + r of the wave's 16, key k0 + 16 kj + l15
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v[4], mx = -INFINITY;
+#pragma unroll
+      for (int kj = 0; kj < 4; ++kj) {
+        v[kj] = (k0 + kj * 16 + l15 < N) ? s[kj][r] * sc : -INFINITY;
+        mx = fmaxf(mx, v[kj]);
+      }
+      const float mn = fmaxf(m[r], max16(mx));           // finite: key k0 < N is in every tile
+      const float alpha = exp2f(m[r] - mn);
+      float ls = 0.f;
+#pragma unroll
+      for (int kj = 0; kj < 4; ++kj) {
+        const float p = exp2f(v[kj] - mn);
+        ls += p;
+        ps[wv][(4 * g + r) * PT + kj * 16 + l15] = f2bf(p);
+      }
+      l[r] = l[r] * alpha + sum16(ls);
+      m[r] = mn;
+#pragma unroll
+      for (int dj = 0; dj < 4; ++dj) o[dj][r] *= alpha;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16x8 pf = lds8(ps[wv] + l15 * PT + 32 * t + 8 * g);
+#pragma unroll
+      for (int dj = 0; dj < 4; ++dj)
+        o[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, lds8(vt + (dj * 16 + l15) * PT + 32 * t + 8 * g), o[dj], 0, 0, 0);
+    }
+  }
+  // o[dj][r]: query q0 + 4g + r, dim 16 dj + l15
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int q = q0 + 4 * g + r;
+    if (q >= N) continue;
+    const float inv = 1.f / l[r];
+    bf16* orow = out + ((size_t)b * N + q) * ldo + h * HD;
+#pragma unroll
+    for (int dj = 0; dj < 4; ++dj) orow[dj * 16 + l15] = f2bf(o[dj][r] * inv);
+    if (l15 == 0) lse[((size_t)b * H + h) * N + q] = (m[r] + log2f(l[r])) * LN2;
+  }
+}
+
+// delta[b][h][q] = sum_d dO[q][h*64+d] * O[q][h*64+d]   (one thread per (token, head), fixed order over d)
+__global__ __launch_bounds__(256) void gattn_delta_kernel(const bf16* __restrict__ out, const bf16* __restrict__ dout, int ldo,
+                                                          int B, int N, int H, float* __restrict__ delta) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)B * N * H) return;
+  const int h = (int)(i % H);
+  const int64_t row = i / H;
+  const int b = (int)(row / N), q = (int)(row % N);
+  const bf16* po = out + row * ldo + h * HD;
+  const bf16* pd = dout + row * ldo + h * HD;
+  float acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < HD; c += 8) {
+    const bf16x8 a = ldg16(po + c), d = ldg16(pd + c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = fmaf(bf2f(a[j]), bf2f(d[j]), acc);
+  }
+  delta[((size_t)b * H + h) * N + q] = acc;
+}
+
+// dK, dV of 64 keys: a wave owns 16 keys and walks every query tile
+__global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__ qkv, int ldq, const bf16* __restrict__ dout,
+                                                        int ldo, const float* __restrict__ lse, const float* __restrict__ delta,
+                                                        int N, int H, bf16* __restrict__ dqkv, int ldd) {
+  __shared__ __attribute__((aligned(16))) bf16 qs[TL * PT];       // Q [query][d]
+  __shared__ __attribute__((aligned(16))) bf16 qt[HD * PT];       // Q^T [d][query]
+  __shared__ __attribute__((aligned(16))) bf16 dos[TL * PT];      // dO [query][d]
+  __shared__ __attribute__((aligned(16))) bf16 dot[HD * PT];      // dO^T [d][query]
+  __shared__ __attribute__((aligned(16))) bf16 ws[4][16 * PT];    // per wave: P^T, then dS^T [key][query]
+  __shared__ float lsl[TL], dl[TL];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
+  const int b = blockIdx.y / H, h = blockIdx.y % H, C = H * HD;
+  const int k0 = blockIdx.x * TL + wv * 16;
+  const bf16* base = qkv + (size_t)b * N * ldq;
+  const bf16* dbase = dout + (size_t)b * N * ldo;
+  const float* lrow = lse + ((size_t)b * H + h) * N;
+  const float* drow = delta + ((size_t)b * H + h) * N;
+  bf16x8 kf[2], vf[2];
+  {
+    const int kr = k0 + l15;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      kf[t] = kr < N ? ldg16(base + (size_t)kr * ldq + C + h * HD + 32 * t + 8 * g) : zero8();
+      vf[t] = kr < N ? ldg16(base + (size_t)kr * ldq + 2 * C + h * HD + 32 * t + 8 * g) : zero8();
+    }
+  }
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) dk[j] = dv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const float sc = SCALE * LOG2E;
+  for (int q0 = 0; q0 < N; q0 += TL) {
+    __syncthreads();
+    stage_tile(base, ldq, h * HD, q0, N, qs, qt);
+    stage_tile(dbase, ldo, h * HD, q0, N, dos, dot);
+    if (threadIdx.x < TL) {
+      const int q = q0 + threadIdx.x;
+      lsl[threadIdx.x] = q < N ? lrow[q] * LOG2E : INFINITY;      // queries past N: P = 0
+      dl[threadIdx.x] = q < N ? drow[q] : 0.f;
+    }
+    __syncthreads();
+    f32x4 st[4], dpt[4];
+#pragma unroll
+    for (int qj = 0; qj < 4; ++qj) {
+      st[qj] = dpt[qj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        st[qj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t], lds8(qs + (qj * 16 + l15) * PT + 32 * t + 8 * g), st[qj], 0, 0, 0);
+        dpt[qj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[t], lds8(dos + (qj * 16 + l15) * PT + 32 * t + 8 * g), dpt[qj], 0, 0, 0);
+      }
+    }
+    // element (qj, r): key k0 + 4g + r, query q0 + 16 qj + l15
+    float dsv[4][4];
+#pragma unroll
+    for (int qj = 0; qj < 4; ++qj) {
+      const int ql = qj * 16 + l15;
+      const float lq = lsl[ql], dq = dl[ql];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = exp2f(st[qj][r] * sc - lq);
+        ws[wv][(4 * g + r) * PT + ql] = f2bf(p);
+        dsv[qj][r] = p * (dpt[qj][r] - dq);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16x8 pf = lds8(ws[wv] + l15 * PT + 32 * t + 8 * g);
+#pragma unroll
+      for (int dj = 0; dj < 4; ++dj)
+        dv[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, lds8(dot + (dj * 16 + l15) * PT + 32 * t + 8 * g), dv[dj], 0, 0, 0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int qj = 0; qj < 4; ++qj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ws[wv][(4 * g + r) * PT + qj * 16 + l15] = f2bf(dsv[qj][r]);
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16x8 sf = lds8(ws[wv] + l15 * PT + 32 * t + 8 * g);
+#pragma unroll
+      for (int dj = 0; dj < 4; ++dj)
+        dk[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, lds8(qt + (dj * 16 + l15) * PT + 32 * t + 8 * g), dk[dj], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int k = k0 + 4 * g + r;
+    if (k >= N) continue;
+    bf16* row = dqkv + ((size_t)b * N + k) * ldd + h * HD;
+#pragma unroll
+    for (int dj = 0; dj < 4; ++dj) {
+      row[C + dj * 16 + l15] = f2bf(dk[dj][r] * SCALE);
+      row[2 * C + dj * 16 + l15] = f2bf(dv[dj][r]);
+    }
+  }
+}
+
+// dQ of 64 queries: a wave owns 16 queries and walks every key tile
+__global__ __launch_bounds__(256) void gattn_dq_kernel(const bf16* __restrict__ qkv, int ldq, const bf16* __restrict__ dout,
+                                                       int ldo, const float* __restrict__ lse, const float* __restrict__ delta,
+                                                       int N, int H, bf16* __restrict__ dqkv, int ldd) {
+  __shared__ __attribute__((aligned(16))) bf16 ks[TL * PT];       // K [key][d]
+  __shared__ __attribute__((aligned(16))) bf16 kt[HD * PT];       // K^T [d][key]
+  __shared__ __attribute__((aligned(16))) bf16 vs[TL * PT];       // V [key][d]
+  __shared__ __attribute__((aligned(16))) bf16 ws[4][16 * PT];    // per wave: dS [query][key]
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
+  const int b = blockIdx.y / H, h = blockIdx.y % H, C = H * HD;
+  const int q0 = blockIdx.x * TL + wv * 16;
+  const bf16* base = qkv + (size_t)b * N * ldq;
+  const float* lrow = lse + ((size_t)b * H + h) * N;
+  const float* drow = delta + ((size_t)b * H + h) * N;
+  bf16x8 qf[2], df[2];
+  {
+    const int qr = q0 + l15;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      qf[t] = qr < N ? ldg16(base + (size_t)qr * ldq + h * HD + 32 * t + 8 * g) : zero8();
+      df[t] = qr < N ? ldg16(dout + ((size_t)b * N + qr) * ldo + h * HD + 32 * t + 8 * g) : zero8();
+    }
+  }
+  float lr[4], dr[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int q = q0 + 4 * g + r;
+    lr[r] = q < N ? lrow[q] * LOG2E : INFINITY;
+    dr[r] = q < N ? drow[q] : 0.f;
+  }
+  f32x4 dq[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) dq[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const float sc = SCALE * LOG2E;
+  for (int k0 = 0; k0 < N; k0 += TL) {
+    __syncthreads();
+    stage_tile(base, ldq, C + h * HD, k0, N, ks, kt);
+    stage_tile(base, ldq, 2 * C + h * HD, k0, N, vs, nullptr);
+    __syncthreads();
+    f32x4 s[4], dp[4];
+#pragma unroll
+    for (int kj = 0; kj < 4; ++kj) {
+      s[kj] = dp[kj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        s[kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t], lds8(ks + (kj * 16 + l15) * PT + 32 * t + 8 * g), s[kj], 0, 0, 0);
+        dp[kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[t], lds8(vs + (kj * 16 + l15) * PT + 32 * t + 8 * g), dp[kj], 0, 0, 0);
+      }
+    }
+    // element (kj, r): query q0 + 4g + r, key k0 + 16 kj + l15
+#pragma unroll
+    for (int kj = 0; kj < 4; ++kj) {
+      const bool live = k0 + kj * 16 + l15 < N;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = live ? exp2f(s[kj][r] * sc - lr[r]) : 0.f;
+        ws[wv][(4 * g + r) * PT + kj * 16 + l15] = f2bf(p * (dp[kj][r] - dr[r]));
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16x8 sf = lds8(ws[wv] + l15 * PT + 32 * t + 8 * g);
+#pragma unroll
+      for (int dj = 0; dj < 4; ++dj)
+        dq[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, lds8(kt + (dj * 16 + l15) * PT + 32 * t + 8 * g), dq[dj], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int q = q0 + 4 * g + r;
+    if (q >= N) continue;
+    bf16* row = dqkv + ((size_t)b * N + q) * ldd + h * HD;
+#pragma unroll
+    for (int dj = 0; dj < 4; ++dj) row[dj * 16 + l15] = f2bf(dq[dj][r] * SCALE);
+  }
+}
+
+// ---- embedding helpers ------------------------------------------------------------------------------------------------------
+// img NHWC bf16 [n][h][w][4] -> rows [n * (h/p) * (w/p)][p * p * 4]: one thread per pixel (8 bytes)
+__global__ __launch_bounds__(256) void patch_gather_kernel(const uint2* __restrict__ img, int n, int h, int w, int p,
+                                                           uint2* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)n * h * w) return;
+  const int x = (int)(i % w);
+  const int64_t t = i / w;
+  const int y = (int)(t % h), b = (int)(t / h);
+  const int gh = h / p, gw = w / p;
+  const int64_t row = ((int64_t)b * gh + y / p) * gw + x / p;
+  rows[row * p * p + (y % p) * p + (x % p)] = img[i];
+}
+
+// out[b][t] = (t < prefix ? cls (+ pos[0]) : patch[b][t - prefix] + pos[no_embed_class ? t - prefix : t]), rounded once
+__global__ __launch_bounds__(256) void vit_embed_fwd_kernel(const bf16* __restrict__ patch, const float* __restrict__ pos,
+                                                            const float* __restrict__ cls, int B, int P, int D, int prefix,
+                                                            int no_embed_class, bf16* __restrict__ out) {
+  const int T = P + prefix, dg = D / 8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)B * T * dg) return;
+  const int d0 = (int)(i % dg) * 8;
+  const int64_t row = i / dg;
+  const int t = (int)(row % T), b = (int)(row / T);
+  float v[8];
+  if (t < prefix) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = cls[d0 + j] + (no_embed_class ? 0.f : pos[d0 + j]);
+  } else {
+    const bf16x8 x = ldg16(patch + ((int64_t)b * P + (t - prefix)) * D + d0);
+    const float* pr = pos + (size_t)(no_embed_class ? t - prefix : t) * D + d0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = bf2f(x[j]) + pr[j];
+  }
+  bf16x8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = f2bf(v[j]);
+  stg16(out + row * D + d0, r);
+}
+
+// d(pos)[j][d] = sum_b dout[b][j + off][d] for j < L; d(cls)[d] = sum_b dout[b][0][d] (row L of the launch); image order
+__global__ __launch_bounds__(256) void vit_embed_bwd_kernel(const bf16* __restrict__ dout, int B, int T, int D, int L, int off,
+                                                            float* __restrict__ dpos, int pos_acc, float* __restrict__ dcls,
+                                                            int cls_acc) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)(L + 1) * D) return;
+  const int d = (int)(i % D), j = (int)(i / D);
+  float* dst;
+  int acc, row;
+  if (j < L) {
+    if (!dpos) return;
+    dst = dpos + (size_t)j * D + d;
+    acc = pos_acc;
+    row = j + off;
+  } else {
+    if (!dcls) return;
+    dst = dcls + d;
+    acc = cls_acc;
+    row = 0;
+  }
+  float s = 0.f;
+  for (int b = 0; b < B; ++b) s += bf2f(dout[((int64_t)b * T + row) * D + d]);
+  *dst = acc ? *dst + s : s;
+}
+
+// rows [first, first + count) of every image's T rows: forward gather (dir 0) or its transpose (dir 1: dsrc (+)= scatter, the
+// other rows 0 / unchanged)
+__global__ __launch_bounds__(256) void rows_select_kernel(const bf16* __restrict__ src, int B, int T, int first, int count, int D,
+                                                          bf16* __restrict__ dst, int dir, int accumulate) {
+  const int dg = D / 8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (dir == 0) {
+    if (i >= (int64_t)B * count * dg) return;
+    const int d0 = (int)(i % dg) * 8;
+    const int64_t r = i / dg;
+    const int b = (int)(r / count), t = (int)(r % count) + first;
+    stg16(dst + r * D + d0, ldg16(src + ((int64_t)b * T + t) * D + d0));
+    return;
+  }
+  if (i >= (int64_t)B * T * dg) return;
+  const int d0 = (int)(i % dg) * 8;
+  const int64_t r = i / dg;
+  const int b = (int)(r / T), t = (int)(r % T);
+  bf16* o = dst + r * D + d0;
+  if (t < first || t >= first + count) {
+    if (!accumulate) stg16(o, zero8());
+    return;
+  }
+  const bf16x8 gsel = ldg16(src + ((int64_t)b * count + (t - first)) * D + d0);
+  if (!accumulate) {
+    stg16(o, gsel);
+    return;
+  }
+  const bf16x8 cur = ldg16(o);
+  bf16x8 r8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r8[j] = f2bf(bf2f(cur[j]) + bf2f(gsel[j]));
+  stg16(o, r8);
+}
+
+unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+#define GA_CHECK_GEO(who)                                                                                                   \
+  TOK_CHECK_ARG(head_dim == HD, "%s: head_dim %d is not served (64 only)", who, head_dim);                                  \
+  TOK_CHECK_ARG(batch > 0 && heads > 0 && n >= 1 && n <= TOK_GLOBAL_ATTN_MAX_TOKENS, "%s: %d tokens (1 ... %d served)", who, \
+                n, TOK_GLOBAL_ATTN_MAX_TOKENS);                                                                              \
+  TOK_CHECK_ARG(ldq >= 3 * heads * HD && ldq % 8 == 0 && ldo >= heads * HD && ldo % 8 == 0,                                 \
+                "%s: row pitches ldq %d / ldo %d (>= 3C / C, multiples of 8)", who, ldq, ldo);                               \
+  TOK_CHECK_ARG((size_t)batch * heads <= 65535u, "%s: batch * heads %d > 65535", who, batch * heads)
+
+extern "C" int tok_global_attn_fwd(const void* qkv, int ldq, int batch, int n, int heads, int head_dim, void* out, int ldo,
+                                   float* lse, void* stream) {
+  GA_CHECK_GEO("tok_global_attn_fwd");
+  TOK_CHECK_ARG(qkv && out && lse, "tok_global_attn_fwd: null pointer");
+  hipLaunchKernelGGL(gattn_fwd_kernel, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)qkv, ldq, n, heads, (bf16*)out, ldo, lse);
+  TOK_CHECK_LAUNCH("tok_global_attn_fwd");
+  return TOK_OK;
+}
+
+extern "C" size_t tok_global_attn_bwd_ws_bytes(int batch, int n, int heads) {
+  if (batch <= 0 || n <= 0 || heads <= 0) return 0;
+  return ((size_t)batch * heads * n * sizeof(float) + 255) / 256 * 256;
+}
+
+extern "C" int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
+                                   int batch, int n, int heads, int head_dim, void* dqkv, int ldd, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  GA_CHECK_GEO("tok_global_attn_bwd");
+  TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "tok_global_attn_bwd: null pointer");
+  TOK_CHECK_ARG(ldd >= 3 * heads * HD && ldd % 8 == 0, "tok_global_attn_bwd: ldd %d", ldd);
+  if (ws_bytes < tok_global_attn_bwd_ws_bytes(batch, n, heads)) {
+    tok_set_error("tok_global_attn_bwd: workspace %zu < %zu bytes", ws_bytes, tok_global_attn_bwd_ws_bytes(batch, n, heads));
+    return TOK_ERR_WORKSPACE;
+  }
+  hipStream_t st = tok_stream(stream);
+  float* delta = (float*)ws;
+  hipLaunchKernelGGL(gattn_delta_kernel, dim3(blocks_of((int64_t)batch * n * heads)), dim3(256), 0, st, (const bf16*)out,
+                     (const bf16*)dout, ldo, batch, n, heads, delta);
+  TOK_CHECK_LAUNCH("tok_global_attn_bwd(delta)");
+  hipLaunchKernelGGL(gattn_dkv_kernel, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd);
+  TOK_CHECK_LAUNCH("tok_global_attn_bwd(dkv)");
+  hipLaunchKernelGGL(gattn_dq_kernel, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd);
+  TOK_CHECK_LAUNCH("tok_global_attn_bwd(dq)");
+  return TOK_OK;
+}
+
+extern "C" int tok_patch_gather(const void* img, int n, int h, int w, int p, void* rows, void* stream) {
+  TOK_CHECK_ARG(img && rows && n > 0 && p > 0 && h >= p && w >= p && h % p == 0 && w % p == 0,
+                "tok_patch_gather: %dx%d image, patch %d (sides must be multiples of the patch)", h, w, p);
+  const int64_t px = (int64_t)n * h * w;
+  hipLaunchKernelGGL(patch_gather_kernel, dim3(blocks_of(px)), dim3(256), 0, tok_stream(stream), (const uint2*)img, n, h, w, p,
+                     (uint2*)rows);
+  TOK_CHECK_LAUNCH("tok_patch_gather");
+  return TOK_OK;
+}
+
+extern "C" int tok_vit_embed_fwd(const void* patch, const float* pos, const float* cls, int batch, int patches, int d,
+                                 int no_embed_class, void* out, void* stream) {
+  TOK_CHECK_ARG(patch && pos && out && batch > 0 && patches > 0 && d > 0 && d % 8 == 0, "tok_vit_embed_fwd: bad args");
+  const int prefix = cls ? 1 : 0;
+  hipLaunchKernelGGL(vit_embed_fwd_kernel, dim3(blocks_of((int64_t)batch * (patches + prefix) * (d / 8))), dim3(256), 0,
+                     tok_stream(stream), (const bf16*)patch, pos, cls, batch, patches, d, prefix, no_embed_class ? 1 : 0,
+                     (bf16*)out);
+  TOK_CHECK_LAUNCH("tok_vit_embed_fwd");
+  return TOK_OK;
+}
+
+extern "C" int tok_vit_embed_bwd(const void* dout, int batch, int patches, int d, int has_cls, int no_embed_class, float* dpos,
+                                 int pos_acc, float* dcls, int cls_acc, void* stream) {
+  TOK_CHECK_ARG(dout && batch > 0 && patches > 0 && d > 0 && d % 8 == 0 && (!dcls || has_cls), "tok_vit_embed_bwd: bad args");
+  if (!dpos && !dcls) return TOK_OK;
+  const int prefix = has_cls ? 1 : 0, T = patches + prefix;
+  const int L = no_embed_class ? patches : T, off = no_embed_class ? prefix : 0;
+  hipLaunchKernelGGL(vit_embed_bwd_kernel, dim3(blocks_of((int64_t)(L + 1) * d)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)dout, batch, T, d, L, off, dpos, pos_acc, dcls, cls_acc);
+  TOK_CHECK_LAUNCH("tok_vit_embed_bwd");
+  return TOK_OK;
+}
+
+extern "C" int tok_rows_select(const void* src, int batch, int t, int first, int count, int d, void* dst, int dir,
+                               int accumulate, void* stream) {
+  TOK_CHECK_ARG(src && dst && batch > 0 && t > 0 && first >= 0 && count > 0 && first + count <= t && d > 0 && d % 8 == 0 &&
+                (dir == 0 || dir == 1), "tok_rows_select: bad args");
+  const int64_t work = (int64_t)batch * (dir == 0 ? count : t) * (d / 8);
+  hipLaunchKernelGGL(rows_select_kernel, dim3(blocks_of(work)), dim3(256), 0, tok_stream(stream), (const bf16*)src, batch, t,
+                     first, count, d, (bf16*)dst, dir, accumulate ? 1 : 0);
+  TOK_CHECK_LAUNCH("tok_rows_select");
+  return TOK_OK;
+}

@@ -11,6 +11,10 @@ window_attention     WindowAttention.forward between qkv and proj, with roll / w
                      folded into the kernel's token addressing
 patch_merge          PatchMerging's strided 2x2 gather + cat
 reshape              .view between (B, H, W, C) maps and (B*H*W, C) token rows (zero copy)
+global_attention     ViT Attention.forward between qkv and proj: softmax(q k^T / 8) v over all tokens of an image
+patch_embed          ViT PatchEmbed.proj (k = stride = patch): patch gather + 1x1 GEMM
+vit_embed            VisionTransformer._pos_embed: cls token + pos_embed, one rounding
+rows_select          x[:, first:first + count] of the (B, T, C) token view (cls rows, patch rows)
 """
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -791,5 +795,234 @@ def dwconv3x3(region: Region, x: TTensor, conv: nn.Conv2d) -> TTensor:
         out.node = node
         if x.requires_grad:
             x.uses += 1
+        region.add(node)
+    return out
+
+
+# ---- Vision Transformer: global attention, patch embedding, token assembly ---------------------------------------------------
+class _GlobalAttnNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        lib, st = _C.lib(), stream_ptr()
+        g = self.out.grad
+        if g is None:
+            return
+        b, n, heads = self.geo
+        qkv, o = self.qkv, self.out
+        if g.stride(0) != o.data.stride(0):
+            raise RuntimeError('global_attention: d(out) and out do not share a row pitch')
+        tgt, acc = grad_target(qkv)
+        if acc:
+            raise RuntimeError('global_attention: qkv has a single consumer')
+        ws_bytes = int(lib.tok_global_attn_bwd_ws_bytes(b, n, heads))
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
+        _C.check(lib.tok_global_attn_bwd(ptr(qkv.data), qkv.cp, ptr(o.data), ptr(g), o.cp, ptr(self.lse), b, n, heads, 64,
+                                         ptr(tgt), qkv.cp, ptr(ws), ws_bytes, st), 'tok_global_attn_bwd')
+        c = heads * 64
+        if qkv.cp != 3 * c:
+            tgt[:, 3 * c:] = 0
+        self.out.grad = None
+
+    def release(self):
+        self.qkv = self.out = self.lse = None
+
+
+def global_attention(region: Region, qkv: TTensor, batch: int, tokens: int, heads: int, head_dim: int = 64) -> TTensor:
+    """[timm 0.6.13] Attention.forward between qkv and proj: qkv rows [B*N][3C] -> softmax(q k^T * 64^-0.5) v rows [B*N][C],
+    over all N tokens of an image.  The node keeps qkv, the output and the row log-sum-exp; its backward writes d(qkv)."""
+    c = heads * head_dim
+    if qkv.c != 3 * c:
+        raise ValueError(f'global_attention: qkv width {qkv.c} != 3 * {heads} heads * {head_dim}')
+    lib, st = _C.lib(), stream_ptr()
+    dev = qkv.data.device
+    out_data = torch.empty((batch * tokens, c), dtype=BF16, device=dev)
+    lse = torch.empty((batch, heads, tokens), dtype=F32, device=dev)
+    rc = lib.tok_global_attn_fwd(ptr(qkv.data), qkv.cp, batch, tokens, heads, head_dim, ptr(out_data), c, ptr(lse), st)
+    if rc != 0 and head_dim != 64:
+        raise NotImplementedError(f'global_attention: head_dim {head_dim} (64 only)')
+    _C.check(rc, 'tok_global_attn_fwd')
+    req = region.grad_mode and qkv.requires_grad
+    out = TTensor(out_data, c, requires_grad=req)
+    if req:
+        node = _GlobalAttnNode()
+        node.qkv, node.out, node.lse, node.geo = qkv, out, lse, (batch, tokens, heads)
+        out.node = node
+        qkv.uses += 1
+        region.add(node)
+    return out
+
+
+class _PatchEmbedNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        lib, st = _C.lib(), stream_ptr()
+        g = self.out.grad
+        if g is None:
+            return
+        conv, d, rows = self.conv, self.desc, self.rows
+        m, kp = g.shape
+        k, p = conv.out_channels, conv.kernel_size[0]
+        if conv.bias is not None and conv.bias.requires_grad:
+            nrows = lib.tok_colsum_partial_rows(m, kp)
+            part = torch.empty((nrows, kp), dtype=F32, device=g.device)
+            _C.check(lib.tok_colsum_partial(ptr(g), m, kp, ptr(part), st), 'tok_colsum_partial')
+            slot, mode = param_grad_target(conv.bias)
+            tmp = torch.empty_like(slot) if mode == 2 else slot
+            _C.check(lib.tok_colsum_f32(ptr(part), nrows, kp, ptr(tmp), 1 if mode == 1 else 0, st), 'tok_colsum_f32')
+            commit_param_grad(conv.bias, tmp if mode == 2 else slot, mode)
+        if conv.weight.requires_grad:
+            # the GEMM's weight gradient over the gathered rows is [K][p][p][4]; the master's channels-last slot is [K][p][p][3]
+            ws_bytes = int(lib.tok_conv_wgrad_ws_bytes(d))
+            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
+            full = torch.empty((k, p, p, 4), dtype=F32, device=g.device)
+            _C.check(lib.tok_conv_wgrad(d, ptr(rows), ptr(g), ptr(full), k, d.c, ptr(ws), ws_bytes, 0, st), 'tok_conv_wgrad')
+            slot, mode = param_grad_target(conv.weight)
+            dst = slot.permute(0, 2, 3, 1)
+            if mode == 1:
+                dst.add_(full[..., :conv.in_channels])
+            else:
+                dst.copy_(full[..., :conv.in_channels])
+            commit_param_grad(conv.weight, slot, mode)
+        self.out.grad = None
+
+    def release(self):
+        self.out = self.rows = None
+
+
+def patch_embed(region: Region, x: TTensor, conv: nn.Conv2d) -> Tuple[TTensor, Tuple[int, int]]:
+    """[timm 0.6.13] PatchEmbed.proj (k = p, stride = p, no padding) on the c4 NHWC image: the non-overlapping patches are
+    gathered into rows [B*gh*gw][p*p*4] (tok_patch_gather) and multiplied with the [D][p][p][4] weight pack on the 1x1 GEMM.
+    -> (token rows [B*gh*gw][D], (gh, gw)).  The image takes no gradient."""
+    p = conv.kernel_size[0]
+    if (tuple(conv.kernel_size) != (p, p) or tuple(conv.stride) != (p, p) or tuple(conv.padding) != (0, 0) or conv.groups != 1
+            or tuple(conv.dilation) != (1, 1) or conv.in_channels > 4 or x.data.dim() != 4 or x.cp != 4):
+        raise NotImplementedError('patch_embed: k = stride = p, no padding, at most 3 (4) input channels')
+    if x.requires_grad:
+        raise NotImplementedError('patch_embed: the image takes no gradient')
+    n, h, w, _ = x.shape
+    if h % p or w % p:
+        raise NotImplementedError(f'patch_embed: a {h}x{w} image is not a multiple of the patch size {p}')
+    lib, st = _C.lib(), stream_ptr()
+    gh, gw = h // p, w // p
+    m, kc = n * gh * gw, p * p * 4
+    k = conv.out_channels
+    kp = pad8(k)
+    if kp != k:
+        raise NotImplementedError('patch_embed: embed_dim % 8 == 0')
+    rows = torch.empty((m, kc), dtype=BF16, device=x.data.device)
+    _C.check(lib.tok_patch_gather(ptr(x.data), n, h, w, p, ptr(rows), st), 'tok_patch_gather')
+    pk = get_packs(conv.weight, conv.bias, kp, p, 4, want_dgrad=False, refresh=True)
+    d = _C.ConvDesc(m, 1, 1, kc, kp, 1, 1, 1, 1, 1, 0, 1)
+    y = torch.empty((m, kp), dtype=BF16, device=x.data.device)
+    _C.check(lib.tok_conv_fwd(d, ptr(rows), ptr(pk.fwd), ptr(pk.bias), ptr(y), None, st), 'tok_conv_fwd')
+    req = region.grad_mode and (conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad))
+    out = TTensor(y, k, requires_grad=req)
+    if req:
+        node = _PatchEmbedNode()
+        node.out, node.conv, node.desc, node.rows = out, conv, d, rows
+        out.node = node
+        region.add(node)
+    return out, (gh, gw)
+
+
+class _VitEmbedNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        lib, st = _C.lib(), stream_ptr()
+        g = self.out.grad
+        if g is None:
+            return
+        b, n_p, dim, no_embed_class = self.geo
+        pos, cls, x = self.pos, self.cls, self.x
+        has_cls = cls is not None
+        pos_need, cls_need = pos.requires_grad, has_cls and cls.requires_grad
+        if pos_need or cls_need:       # a frozen parameter takes no fold at all
+            (ps, pm) = param_grad_target(pos) if pos_need else (None, 0)
+            (cs, cm) = param_grad_target(cls) if cls_need else (None, 0)
+            pt = torch.empty_like(ps) if pm == 2 else ps
+            ct = torch.empty_like(cs) if cm == 2 else cs
+            _C.check(lib.tok_vit_embed_bwd(ptr(g), b, n_p, dim, 1 if has_cls else 0, 1 if no_embed_class else 0, ptr(pt),
+                                           1 if pm == 1 else 0, ptr(ct), 1 if cm == 1 else 0, st), 'tok_vit_embed_bwd')
+            if pos_need:
+                commit_param_grad(pos, pt if pm == 2 else ps, pm)
+            if cls_need:
+                commit_param_grad(cls, ct if cm == 2 else cs, cm)
+        if x.requires_grad:
+            tgt, acc = grad_target(x)
+            prefix = 1 if has_cls else 0
+            if acc:
+                tmp = torch.empty_like(tgt)
+                _C.check(lib.tok_rows_select(ptr(g), b, n_p + prefix, prefix, n_p, dim, ptr(tmp), 0, 0, st), 'tok_rows_select')
+                _C.check(lib.tok_act_bwd(2, ptr(tmp), ptr(tmp), ptr(tgt), 1, tmp.numel(), st), 'tok_act_bwd')
+            else:
+                _C.check(lib.tok_rows_select(ptr(g), b, n_p + prefix, prefix, n_p, dim, ptr(tgt), 0, 0, st), 'tok_rows_select')
+        self.out.grad = None
+
+    def release(self):
+        self.x = self.out = self.pos = self.cls = None
+
+
+def vit_embed(region: Region, x: TTensor, batch: int, pos_embed: nn.Parameter, cls_token: Optional[nn.Parameter],
+              no_embed_class: bool = False) -> TTensor:
+    """VisionTransformer._pos_embed (vit.py:284-298) on patch rows [B*P][D]: prepend the class token and add the position
+    embedding, rounded once -> token rows [B*T][D] (T = P + 1 with a class token).  Frozen parameters take no fold."""
+    dim = x.c
+    if x.cp != dim or dim % 8:
+        raise NotImplementedError('vit_embed: embed_dim % 8 == 0')
+    n_p = x.rows() // batch
+    prefix = 1 if cls_token is not None else 0
+    want = n_p if no_embed_class else n_p + prefix
+    if pos_embed.numel() != want * dim or not pos_embed.is_contiguous():
+        raise ValueError(f'vit_embed: pos_embed {tuple(pos_embed.shape)} does not hold {want} x {dim} (contiguous)')
+    if cls_token is not None and (cls_token.numel() != dim or not cls_token.is_contiguous()):
+        raise ValueError(f'vit_embed: cls_token {tuple(cls_token.shape)}')
+    out_data = torch.empty((batch * (n_p + prefix), dim), dtype=BF16, device=x.data.device)
+    _C.check(_C.lib().tok_vit_embed_fwd(ptr(x.data), ptr(pos_embed.detach()), ptr(cls_token.detach()) if prefix else None, batch,
+                                        n_p, dim, 1 if no_embed_class else 0, ptr(out_data), stream_ptr()), 'tok_vit_embed_fwd')
+    req = region.grad_mode and (x.requires_grad or pos_embed.requires_grad or (prefix and cls_token.requires_grad))
+    out = TTensor(out_data, dim, requires_grad=bool(req))
+    if req:
+        node = _VitEmbedNode()
+        node.x, node.out, node.pos, node.cls, node.geo = x, out, pos_embed, cls_token, (batch, n_p, dim, no_embed_class)
+        out.node = node
+        if x.requires_grad:
+            x.uses += 1
+        region.add(node)
+    return out
+
+
+class _RowsSelectNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        g = self.out.grad
+        if g is None or not self.x.requires_grad:
+            return
+        b, t, first, count = self.geo
+        tgt, acc = grad_target(self.x)
+        _C.check(_C.lib().tok_rows_select(ptr(g), b, t, first, count, self.x.cp, ptr(tgt), 1, acc, stream_ptr()),
+                 'tok_rows_select')
+        self.out.grad = None
+
+    def release(self):
+        self.x = self.out = None
+
+
+def rows_select(region: Region, x: TTensor, batch: int, first: int, count: int) -> TTensor:
+    """Rows [first, first + count) of every image's token rows: x[:, first:first + count] of the (B, T, C) view (the class
+    token the final norm reads, or the patch tokens of forward_features)."""
+    t = x.rows() // batch
+    y = torch.empty((batch * count, x.cp), dtype=BF16, device=x.data.device)
+    _C.check(_C.lib().tok_rows_select(ptr(x.data), batch, t, first, count, x.cp, ptr(y), 0, 0, stream_ptr()), 'tok_rows_select')
+    req = region.grad_mode and x.requires_grad
+    out = TTensor(y, x.c, requires_grad=req)
+    if req:
+        node = _RowsSelectNode()
+        node.x, node.out, node.geo = x, out, (batch, t, first, count)
+        out.node = node
+        x.uses += 1
         region.add(node)
     return out
