@@ -108,3 +108,65 @@ def record_distance(test: str, tensor: str, hip_vs_autocast=None, hip_vs_fp32=No
             f.write(json.dumps(rec) + '\n')
     except OSError:
         pass
+
+
+# ---- element-wise error bounds and output canaries (kernel contract tests) -----------------------------------------------
+def assert_bounded(mine, ref, mag, a, b, what='', test=None):
+    """Element by element |mine - ref| <= a * |ref| + b * mag, with `ref` the fp64 result of the operation and `mag` the same
+    operation applied to absolute values (e.g. conv(|x|, |w|)): `a` covers the rounding of the result itself, `b` the
+    accumulation.  A NaN anywhere in `mine` fails.  Returns the worst |err| / bound (recorded with record_distance when `test`
+    is given); on failure reports the worst element, its value and its bound."""
+    mine = mine.detach().double().cpu()
+    ref, mag = ref.detach().double().cpu(), mag.detach().double().cpu()
+    assert mine.shape == ref.shape == mag.shape, (what, tuple(mine.shape), tuple(ref.shape), tuple(mag.shape))
+    err = (mine - ref).abs()
+    bound = a * ref.abs() + b * mag
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, float('inf'), 0.0))
+    ratio = torch.nan_to_num(ratio, nan=float('inf'))
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    if test is not None:
+        record_distance(test, what, err_over_bound=worst)
+    if worst > 1.0:
+        i = int(ratio.argmax())
+        idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), ratio.shape))
+        raise AssertionError(f'{what}: element {idx} = {float(mine.reshape(-1)[i])!r}, fp64 {float(ref.reshape(-1)[i])!r}, '
+                             f'|err| {float(err.reshape(-1)[i]):.3e} > bound {float(bound.reshape(-1)[i]):.3e} '
+                             f'(worst |err| / bound {worst:.3g})')
+    return worst
+
+
+_INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32}
+SENTINEL = {torch.bfloat16: 0x5A5B, torch.float32: 0x5A5B5C5D}   # finite, ~1e16: no kernel here produces these bits
+BF16_NAN = 0x7FC1
+
+
+class Guarded:
+    """A [rows][cols] operand inside a [rows + 1][ld] buffer (ld >= cols): the kernel gets `view` (pitch ld) or `ptr`.
+    Outputs: the pad columns and the guard row past the end hold SENTINEL bits, which `check()` asserts unchanged after the
+    call, so a stray write inside the test's own memory shows up as a failure.  Inputs (nan_pad=True): pad and guard row hold
+    bf16 NaN, so a kernel that lets a value it does not own into a result is caught.  `init` (optional) fills the view."""
+
+    def __init__(self, rows, cols, ld=None, dtype=torch.bfloat16, init=None, nan_pad=False, device='cuda'):
+        ld = cols if ld is None else ld
+        assert ld >= cols
+        self.rows, self.cols, self.ld, self.dtype = rows, cols, ld, dtype
+        self.buf = torch.empty((rows + 1, ld), dtype=dtype, device=device)
+        self.bits = BF16_NAN if nan_pad else SENTINEL[dtype]
+        self.buf.view(_INT_OF[dtype]).fill_(self.bits)        # (every pattern here is positive in the signed view)
+        self.view = self.buf[:rows, :cols]
+        if init is not None:
+            self.view.copy_(init.reshape(rows, cols))
+
+    @property
+    def ptr(self):
+        return self.buf.data_ptr()
+
+    def value(self):
+        return self.view.detach().cpu()
+
+    def check(self, what=''):
+        iv = self.buf.view(_INT_OF[self.dtype]).cpu()
+        pads = iv[:self.rows, self.cols:]
+        bad_pad = int((pads != self.bits).sum()) if pads.numel() else 0
+        bad_guard = int((iv[self.rows] != self.bits).sum())
+        assert bad_pad == 0 and bad_guard == 0, f'{what}: {bad_pad} pad and {bad_guard} guard-row elements overwritten'
