@@ -217,21 +217,6 @@ class FakeTok:
         p[1, 1] = (dz * yv).sum(0)
         return rc
 
-    def tok_conv_fwd_bn(self, d, x, w, y, stats, bn, st):
-        b = _desc(bn)
-        rc = self.tok_conv_fwd(d, x, w, None, y, stats, st)
-        dd = _desc(d)
-        assert _t(b.counters, (64,), torch.int32).abs().sum() == 0
-        return rc or self.tok_bn_finalize(stats, self.tok_conv_fwd_stat_rows(d), b.count, dd.k, b.c_real, b.gamma, b.beta, b.running_mean,
-                                          b.running_var, b.nbt, b.momentum, b.eps, b.mean, b.rstd, b.scale, b.shift, st)
-
-    def tok_conv_dgrad_bn(self, d, dy, wd, dx, accumulate, bn_y, bn_mask, partial, bn, st):
-        b = _desc(bn)
-        rc = self.tok_conv_dgrad_bnstats(d, dy, wd, dx, accumulate, bn_y, bn_mask, partial, st)
-        dd = _desc(d)
-        return rc or self.tok_bn_bwd_finalize(partial, self.tok_conv_dgrad_stat_rows(d), b.count, dd.c, b.c_real, b.gamma, b.mean, b.rstd, b.dgamma,
-                                              b.dbeta, b.coef, b.param_accumulate, 1, st)
-
     # ---- "unit 3" (1x1 conv -> BatchNorm -> + shortcut -> ReLU without the pre-normalisation tensor) -----------------------
     def tok_bn_gram_finalize(self, Z, zsum, w, count, p, k, gamma, beta, rm, rv, nbt, momentum, eps, mean, rstd, scale, shift,
                              wz, st):

@@ -27,7 +27,7 @@ def product_run(args, image, target, state=None, old_order=False):
             r = engine.current_region()
             y = EF.conv_bn_act(r, x, self.conv1, self.bn1, relu=True)
             y = EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True)
-            shortcut = RN._shortcut_branch(r, x, self.downsample)
+            shortcut = RN._shortcut(r, x, self.downsample)
             return EF.conv_bn_act(r, y, self.conv3, self.bn3, relu=True, shortcut=shortcut)
         RN.Bottleneck.forward = fwd
     torch.manual_seed(1234)

@@ -57,11 +57,6 @@ struct ConvArgs {
   FastDiv fd_pq, fd_q;
   unsigned long long* timing;   // TOK_TIMING builds only: per-phase cycle totals of wave 0
   int stat_rows;   // workgroups per channel tile = rows of the partial-statistics buffer
-  // fused BatchNorm finalize: the LAST workgroup of a channel tile to deliver its statistics row (device
-  // ticket counter) folds the rows of that tile — saves the separate finalize launch between two dependent
-  // kernels.  fin_mode 0: off, 1: forward (mean/rstd/scale/shift/running stats), 2: backward (dgamma/dbeta/coef)
-  int fin_mode;
-  tok_bn_fused fin;
   // IN_DIV == 2: per parity class (ph*2 + pw); m-tile index = 4 * (tile inside class) + class
   int cls_M[4], cls_nw[4], cls_hw[4];
   FastDiv cls_fd_hw[4], cls_fd_w[4];

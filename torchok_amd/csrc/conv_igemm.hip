@@ -692,87 +692,7 @@ __global__ __launch_bounds__(256, (BN == 64 && PWM != 4) ? 3 : 2) void conv_igem
       const int row = xcd * S8 + jm;
       const int n = bn_fixed * BN + c;
       if (n < a.K) {
-        float* dst = &a.stats[((size_t)which * a.stat_rows + row) * a.K + n];
-        // fused finalize: device-coherent (sc1, write-through) store so that the folding workgroup can read the row
-        // without anybody flushing or invalidating an L2 — an agent-scope release fence here costs a full L2
-        // write-back per workgroup (measured: +40 % step time)
-        if (a.fin_mode != 0) __hip_atomic_store(dst, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *dst = t;
-      }
-    }
-    if (a.fin_mode != 0) {
-      __shared__ int s_ticket;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's row elements have reached the coherence point
-      __syncthreads();
-      if (tid == 0) s_ticket = __hip_atomic_fetch_add(&a.fin.counters[bn_fixed], 1, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      if (s_ticket == a.stat_rows - 1) {
-        constexpr int PARTS = NT / BN;
-        double* scr = reinterpret_cast<double*>(smem);   // [2][PARTS][BN]; the tile buffers are dead by now
-        const int c = tid % BN, part = tid / BN;
-        const int n = bn_fixed * BN + c;
-        double a1 = 0.0, a2 = 0.0;
-        if (n < a.K)
-          for (int r = part; r < a.stat_rows; r += PARTS) {
-            a1 += (double)__hip_atomic_load(&a.stats[(size_t)r * a.K + n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a2 += (double)__hip_atomic_load(&a.stats[((size_t)a.stat_rows + r) * a.K + n], __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-          }
-        scr[(0 * PARTS + part) * BN + c] = a1;
-        scr[(1 * PARTS + part) * BN + c] = a2;
-        __syncthreads();
-        if (part == 0 && n < a.K) {
-#pragma unroll
-          for (int q = 1; q < PARTS; ++q) { a1 += scr[(0 * PARTS + q) * BN + c]; a2 += scr[(1 * PARTS + q) * BN + c]; }
-          const tok_bn_fused& f = a.fin;
-          const bool real = n < f.c_real;
-          if (a.fin_mode == 1) {
-            const double inv = 1.0 / (double)f.count;
-            const double mu = a1 * inv;
-            double var = a2 * inv - mu * mu;
-            if (var < 0.0) var = 0.0;
-            const float muf = (float)mu;
-            const float rs = (float)(1.0 / sqrt(var + (double)f.eps));
-            if (real) {
-              f.mean[n] = muf;
-              f.rstd[n] = rs;
-              const float sc = f.gamma[n] * rs;
-              f.scale[n] = sc;
-              f.shift[n] = fmaf(-muf, sc, f.beta[n]);
-              if (f.running_mean != nullptr) {
-                const double unbias = f.count > 1 ? (double)f.count / (double)(f.count - 1) : 1.0;
-                f.running_mean[n] = (1.f - f.momentum) * f.running_mean[n] + f.momentum * muf;
-                f.running_var[n] = (1.f - f.momentum) * f.running_var[n] + f.momentum * (float)(var * unbias);
-              }
-            } else {
-              f.mean[n] = 0.f; f.rstd[n] = 0.f; f.scale[n] = 0.f; f.shift[n] = 0.f;
-            }
-          } else {
-            float* coef = f.coef;
-            if (real) {
-              // second sum is sum(dz * y): sum(dz * xhat) = rstd * (sum(dz*y) - mean * sum(dz))
-              const double sx = (double)f.rstd[n] * (a2 - (double)f.mean[n] * a1);
-              const float sdz = (float)a1, sdzx = (float)sx;
-              if (f.dgamma != nullptr) f.dgamma[n] = f.param_accumulate ? f.dgamma[n] + sdzx : sdzx;
-              if (f.dbeta != nullptr) f.dbeta[n] = f.param_accumulate ? f.dbeta[n] + sdz : sdz;
-              const double inv_m = 1.0 / (double)f.count;
-              const float m1 = (float)(a1 * inv_m), m2 = (float)(sx * inv_m);
-              const float g = f.gamma[n], rs = f.rstd[n], mu = f.mean[n];
-              const float c1 = g * rs;
-              const float c2 = -c1 * rs * m2;
-              coef[n] = c1;
-              coef[a.K + n] = c2;
-              coef[2 * a.K + n] = -c1 * m1 - c2 * mu;
-            } else {
-              coef[n] = 0.f; coef[a.K + n] = 0.f; coef[2 * a.K + n] = 0.f;
-            }
-          }
-        }
-        if (tid == 0) {
-          a.fin.counters[bn_fixed] = 0;     // leave the ticket counters zero for the next launch
-          if (a.fin_mode == 1 && bn_fixed == 0 && a.fin.nbt != nullptr) *a.fin.nbt += 1;
-        }
+        a.stats[((size_t)which * a.stat_rows + row) * a.K + n] = t;
       }
     }
   }
@@ -781,8 +701,6 @@ __global__ __launch_bounds__(256, (BN == 64 && PWM != 4) ? 3 : 2) void conv_igem
 // Persistent grid: 2 (128x128 tile) or 3 (128x64) workgroups per CU, rounded to a multiple of
 // 8 * gridN so every XCD holds whole (channel tile, m-slot) groups; never more than the tiles need.
 int plan_grid(int bn_tile, int gridM, int gridN, int per_cu = 0) {
-  static const int pc64 = [] { const char* e = getenv("TOK_IGEMM_PER_CU_64"); return (int)(e ? atoi(e) : 0); }();      // TOK_IGEMM_PER_CU_64=<n>: persistent workgroups per CU of the 128 x 64 tile (experiment; default 3)
-  if (per_cu == 0 && bn_tile == 64 && pc64 > 0) per_cu = pc64;
   const int unit = 8 * gridN;
   int G = 256 * (per_cu > 0 ? per_cu : (bn_tile == 64 ? 3 : 2));
   const long long need = (long long)gridM * gridN;
@@ -836,15 +754,9 @@ static long long pw_min_rows() {
   if (v < 0) { const char* e = getenv("TOK_PW_RING_MIN_ROWS"); v = e ? atoll(e) : 100000; }
   return v;
 }
-static int pw_ring128() {   // TOK_PW_RING_BN128=<k>: 128-wide tiles with a reduction depth >= k also ride the ring (experiment; 0 = off)
-  static const int v = [] { const char* e = getenv("TOK_PW_RING_BN128"); return (int)(e ? atoi(e) : 0); }();
-  return v;
-}
 static bool pw_serves(int bn_tile, long long rows, int c_red, int n_out) {
   // (the 128-wide tile would run 1 workgroup per CU on the ring: SwinV2-T 26.0 -> 30.3 ms/step; 64-wide tiles only)
-  if (bn_tile == 128 && pw_ring128() > 0 && c_red >= pw_ring128())
-    return pw_ring_enabled() && rows >= pw_min_rows() && c_red % 8 == 0 && n_out % 64 == 0;
-  return pw_ring_enabled() && bn_tile == 64 && rows >= pw_min_rows() && c_red % 8 == 0 && n_out % 64 == 0;
+  return bn_tile == 64 && rows >= pw_min_rows() && c_red % 8 == 0 && n_out % 64 == 0;
 }
 
 // 256 x 256 tiles (gemm256.hip) — decided on the GEOMETRY alone, and behind the pointwise ring, so that the statistics-row
@@ -858,9 +770,9 @@ int launch(ConvArgs& a, hipStream_t st) {
   if constexpr (IN_DIV == 1 && !C4) {
     if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) {
       if (pw_serves(BN, a.M, a.C, a.K)) {
-        // pointwise layers run on the three-stage DMA ring (pw_gemm.hip); modes it does not carry (fused activation, "last
-        // workgroup finalizes") stay here, on the ring's grid so that the statistics rows agree
-        if (a.y2 == nullptr && a.act_x == nullptr && a.fin_mode == 0) {
+        // pointwise layers run on the three-stage DMA ring (pw_gemm.hip); modes it does not carry (fused activation) stay
+        // here, on the ring's grid so that the statistics rows agree
+        if (a.y2 == nullptr && a.act_x == nullptr) {
           PwArgs p = {};
           p.x = a.x; p.w = a.w; p.y = a.y; p.bias = a.bias; p.stats = a.stats;
           p.stat_rows = pw_ring_grid(BN, a.gridM, a.gridN) / a.gridN;
@@ -895,12 +807,6 @@ int launch(ConvArgs& a, hipStream_t st) {
   return launch_pw<BM, BN, IN_DIV, C4, 0>(a, st);
 }
 
-// experiment knob: TOK_BN64=1 forces the 128x64 tile for every layer
-static int force_bn64() {
-  static const int v = [] { const char* e = getenv("TOK_BN64"); return (int)((e && e[0] == '1') ? 1 : 0); }();
-  return v;
-}
-
 // Channel-tile width.  Short-K layers are HBM-streaming problems: the 128x64 tile (4 waves, 3
 // workgroups per CU) keeps more loads/stores in flight; deep-K layers are MFMA-bound and want the
 // 128x128 tile's operand reuse.  (Measured on the ResNet-50 shapes, tools/bench_conv.py.)
@@ -909,20 +815,13 @@ static int short_k() {   // TOK_SHORT_K=<k>: reduction depths up to k take the 1
   return v;
 }
 
-static int small_m_tiles() {   // TOK_SMALLM_TILES=<n>: layers with fewer 128x128 tiles than n take the 128x64 tile
-  static const int v = [] { const char* e = getenv("TOK_SMALLM_TILES"); return (int)(e ? atoi(e) : 0); }();
-  return v;
-}
-
-int pick_bn(int n_out, int ktot, int grid_m, bool token_rows = false) {
-  if (n_out <= 64 || force_bn64()) return 64;
+int pick_bn(int n_out, int ktot, bool token_rows = false) {
+  if (n_out <= 64) return 64;
   // token matrices (h = w = 1: the Linear layers of SwinV2 / DaViT, N = 288 ... 3072 output features): the 128-wide tile
   // at every depth — half the tiles and half the re-reads of the A operand (measured: SwinV2-T 27.7 -> 26.9 ms/step,
   // DaViT-T 27.0 -> 26.2); the short-K rule below was tuned on the ResNet-50 convolutions, where 64 wins
   if (token_rows && getenv("TOK_SHORT_K") == nullptr) return 128;
   if (ktot <= short_k()) return 64;
-  // few pixels x deep K (HRNet's low-resolution branches, the 7x7 ResNet stage): 128x128 tiles cannot fill 256 CUs
-  if ((long long)grid_m * tok_cdiv(n_out, 128) < small_m_tiles()) return 64;
   return 128;
 }
 
@@ -947,7 +846,7 @@ int check_desc(const tok_conv_desc* d, const char* who) {
 extern "C" int tok_conv_fwd_stat_rows(const tok_conv_desc* d) {
   if (check_desc(d, "tok_conv_fwd_stat_rows")) return TOK_ERR_INVALID;
   const int gridM = tok_cdiv((long long)d->n * d->p * d->q, 128);
-  const int bn_tile = pick_bn(d->k, d->r * d->s_pad * d->c, gridM, d->h == 1 && d->w == 1);
+  const int bn_tile = pick_bn(d->k, d->r * d->s_pad * d->c, d->h == 1 && d->w == 1);
   const int gridN = tok_cdiv(d->k, bn_tile);
   if (d->c != 4) {
     ConvArgs g = {};
@@ -970,42 +869,22 @@ extern "C" int tok_conv_fwd_stat_rows(const tok_conv_desc* d) {
 extern "C" int tok_conv_dgrad_stat_rows(const tok_conv_desc* d);
 
 namespace {
-int check_fused(const tok_bn_fused* bn, int k, bool fwd, const char* who) {
-  TOK_CHECK_ARG(bn->counters && bn->count > 0 && bn->c_real > 0 && bn->c_real <= k && bn->gamma && bn->mean && bn->rstd,
-                "%s: bad tok_bn_fused", who);
-  if (fwd) TOK_CHECK_ARG(bn->beta && bn->scale && bn->shift && ((bn->running_mean == nullptr) == (bn->running_var == nullptr)),
-                         "%s: bad tok_bn_fused (forward fields)", who);
-  else TOK_CHECK_ARG(bn->coef, "%s: bad tok_bn_fused (coef)", who);
-  return 0;
-}
 struct BnEpilogue { const float* scale; const float* shift; const void* shortcut; uint8_t* mask; int relu; };
 int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
-                  const tok_bn_fused* bn, void* stream, void* y_act = nullptr, int act = 0, const BnEpilogue* ep = nullptr);
+                  void* stream, void* y_act = nullptr, int act = 0, const BnEpilogue* ep = nullptr);
 }  // namespace
 
 extern "C" int tok_conv_fwd(const tok_conv_desc* d, const void* x, const void* w,
                             const float* bias, void* y, float* stats, void* stream) {
-  return conv_fwd_impl(d, x, w, bias, y, stats, nullptr, stream);
-}
-
-extern "C" int tok_conv_fwd_bn(const tok_conv_desc* d, const void* x, const void* w, void* y, float* stats,
-                               const tok_bn_fused* bn, void* stream) {
-  TOK_CHECK_ARG(stats && bn, "tok_conv_fwd_bn: stats / bn must not be null");
-  return conv_fwd_impl(d, x, w, nullptr, y, stats, bn, stream);
+  return conv_fwd_impl(d, x, w, bias, y, stats, stream);
 }
 
 namespace {
 int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
-                  const tok_bn_fused* bn, void* stream, void* y_act, int act, const BnEpilogue* ep) {
+                  void* stream, void* y_act, int act, const BnEpilogue* ep) {
   if (int e = check_desc(d, "tok_conv_fwd")) return e;
   TOK_CHECK_ARG(x && w && y, "tok_conv_fwd: null pointer");
   ConvArgs a = {};
-  if (bn != nullptr) {
-    if (int e = check_fused(bn, d->k, true, "tok_conv_fwd_bn")) return e;
-    TOK_CHECK_ARG(tok_cdiv(d->k, 64) <= 64, "tok_conv_fwd_bn: more than 64 channel tiles");
-    a.fin_mode = 1;
-    a.fin = *bn;
-  }
   a.x = (const bf16*)x; a.w = (const bf16*)w; a.y = (bf16*)y; a.bias = bias; a.stats = stats;
   a.y2 = (bf16*)y_act; a.act = act;
   if (ep != nullptr) {
@@ -1027,7 +906,7 @@ int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const fl
   hipStream_t st = tok_stream(stream);
   const bool c4 = d->c == 4;
   int rc;
-  const int bn_pick = pick_bn(d->k, a.Ktot, a.gridM, d->h == 1 && d->w == 1);
+  const int bn_pick = pick_bn(d->k, a.Ktot, d->h == 1 && d->w == 1);
   if (c4 && ep == nullptr && stem_win_serves(a)) {
     // the 7x7 / stride 2 stem on a shared input window (stem.hip); statistics rows as tok_conv_fwd_stat_rows sized them
     rc = stem_win_launch(a, tok_conv_fwd_stat_rows(d), st);
@@ -1051,14 +930,7 @@ int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const fl
     return TOK_OK;
   }
   // (a mode gemm256 does not carry that still writes statistics rows: this file's kernel on gemm256's row count — a multiple of 8)
-  if (g256 && a.stats != nullptr && a.fin_mode == 0) a.force_grid = gemm256_rows(a) * tok_cdiv(d->k, ep != nullptr ? 64 : bn_pick);
-  if (a.fin_mode != 0) {
-    // "last workgroup finalizes" stays on this file's kernels; the caller sized `stats` with tok_conv_fwd_stat_rows, which may
-    // describe the (smaller) grid of conv_win: never write more rows than that
-    const int rows_q = tok_conv_fwd_stat_rows(d);
-    const int gn = tok_cdiv(d->k, bn_pick);
-    if (rows_q > 0 && rows_q * gn < plan_grid(bn_pick, a.gridM, gn)) a.force_grid = rows_q * gn;
-  }
+  if (g256 && a.stats != nullptr) a.force_grid = gemm256_rows(a) * tok_cdiv(d->k, ep != nullptr ? 64 : bn_pick);
   if (ep != nullptr || bn_pick == 64) {   // (BN epilogue: 64-wide tiles)
     a.gridN = tok_cdiv(d->k, 64);
     rc = c4 ? launch<128, 64, 1, true>(a, st) : launch<128, 64, 1, false>(a, st);
@@ -1108,7 +980,7 @@ int dgrad_fill(const tok_conv_desc* d, ConvArgs& a, DgradPlan& pl) {
     }
     a.gridM = 4 * tmax;   // classes interleaved (m-tile & 3) so heavy and light tiles mix on every XCD
   }
-  pl.bn_tile = pick_bn(d->c, a.Ktot, a.gridM, d->h == 1 && d->w == 1);
+  pl.bn_tile = pick_bn(d->c, a.Ktot, d->h == 1 && d->w == 1);
   a.gridN = tok_cdiv(d->c, pl.bn_tile);
   pl.gridM = a.gridM; pl.gridN = a.gridN;
   return 0;
@@ -1116,7 +988,7 @@ int dgrad_fill(const tok_conv_desc* d, ConvArgs& a, DgradPlan& pl) {
 
 int dgrad_impl(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, int accumulate,
                const void* bn_y, const uint8_t* bn_mask, float* partial, void* stream, const char* who,
-               const tok_bn_fused* bn = nullptr, const void* act_x = nullptr, int act = 0, const float* bias = nullptr,
+               const void* act_x = nullptr, int act = 0, const float* bias = nullptr,
                int mask_store = 0, const void* sub = nullptr) {
   if (int e = check_desc(d, who)) return e;
   TOK_CHECK_ARG(dy && w_dgrad && dx, "%s: null pointer", who);
@@ -1128,12 +1000,6 @@ int dgrad_impl(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void
   a.accumulate = accumulate;
   a.sub = (const bf16*)sub;
   a.act_x = (const bf16*)act_x; a.act = act;
-  if (bn != nullptr) {
-    if (int e = check_fused(bn, d->c, false, who)) return e;
-    TOK_CHECK_ARG(tok_cdiv(d->c, 64) <= 64, "%s: more than 64 channel tiles", who);
-    a.fin_mode = 2;
-    a.fin = *bn;
-  }
   hipStream_t st = tok_stream(stream);
   int rc;
   if (d->stride == 1 && conv_win_serves(a)) {
@@ -1155,11 +1021,7 @@ int dgrad_impl(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void
     TOK_CHECK_LAUNCH(who);
     return TOK_OK;
   }
-  if (g256 && a.stats != nullptr && a.fin_mode == 0) a.force_grid = gemm256_rows(a) * pl.gridN;   // (see conv_fwd_impl)
-  if (a.fin_mode != 0) {
-    const int rows_q = tok_conv_dgrad_stat_rows(d);
-    if (rows_q > 0 && rows_q * pl.gridN < plan_grid(pl.bn_tile, pl.gridM, pl.gridN)) a.force_grid = rows_q * pl.gridN;
-  }
+  if (g256 && a.stats != nullptr) a.force_grid = gemm256_rows(a) * pl.gridN;   // (see conv_fwd_impl)
   if (pl.bn_tile == 64) rc = d->stride == 1 ? launch<128, 64, 1, false>(a, st) : launch<128, 64, 2, false>(a, st);
   else rc = d->stride == 1 ? launch<128, 128, 1, false>(a, st) : launch<128, 128, 2, false>(a, st);
   if (rc) return rc;
@@ -1172,13 +1034,13 @@ int dgrad_impl(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void
 extern "C" int tok_conv_fwd_act(const tok_conv_desc* d, const void* x, const void* w, const float* bias, void* y,
                                 void* y_act, int kind, void* stream) {
   TOK_CHECK_ARG(y_act != nullptr && (kind == 0 || kind == 1), "tok_conv_fwd_act: y_act and kind 0 (ReLU) / 1 (GELU)");
-  return conv_fwd_impl(d, x, w, bias, y, nullptr, nullptr, stream, y_act, kind);
+  return conv_fwd_impl(d, x, w, bias, y, nullptr, stream, y_act, kind);
 }
 
 extern "C" int tok_conv_dgrad_act(const tok_conv_desc* d, const void* dy, const void* w_dgrad, const void* act_x, int kind,
                                   void* dx, void* stream) {
   TOK_CHECK_ARG(act_x != nullptr && (kind == 0 || kind == 1), "tok_conv_dgrad_act: act_x and kind 0 (ReLU) / 1 (GELU)");
-  return dgrad_impl(d, dy, w_dgrad, dx, 0, nullptr, nullptr, nullptr, stream, "tok_conv_dgrad_act", nullptr, act_x, kind);
+  return dgrad_impl(d, dy, w_dgrad, dx, 0, nullptr, nullptr, nullptr, stream, "tok_conv_dgrad_act", act_x, kind);
 }
 
 extern "C" int tok_conv_dgrad(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
@@ -1214,13 +1076,6 @@ extern "C" int tok_conv_dgrad_bnstats(const tok_conv_desc* d, const void* dy, co
   return dgrad_impl(d, dy, w_dgrad, dx, accumulate, bn_y, bn_mask, partial, stream, "tok_conv_dgrad_bnstats");
 }
 
-extern "C" int tok_conv_dgrad_bn(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, int accumulate,
-                                 const void* bn_y, const uint8_t* bn_mask, float* partial, const tok_bn_fused* bn,
-                                 void* stream) {
-  TOK_CHECK_ARG(bn_y && partial && bn, "tok_conv_dgrad_bn: bn_y / partial / bn must not be null");
-  return dgrad_impl(d, dy, w_dgrad, dx, accumulate, bn_y, bn_mask, partial, stream, "tok_conv_dgrad_bn", bn);
-}
-
 
 // ---- "unit 3" of a bottleneck: 1x1 conv -> BatchNorm -> + shortcut -> ReLU without the pre-normalisation tensor -----------
 
@@ -1231,20 +1086,20 @@ extern "C" int tok_conv_fwd_bn_apply(const tok_conv_desc* d, const void* x, cons
   TOK_CHECK_ARG(d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->c % 8 == 0,
                 "tok_conv_fwd_bn_apply: 1x1 / stride 1 / no padding layers only");
   const BnEpilogue ep = {scale, shift, shortcut, mask, relu};
-  return conv_fwd_impl(d, x, w, nullptr, out, nullptr, nullptr, stream, nullptr, 0, &ep);
+  return conv_fwd_impl(d, x, w, nullptr, out, nullptr, stream, nullptr, 0, &ep);
 }
 
 extern "C" int tok_conv_dgrad_maskstore(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                                         int accumulate, const uint8_t* mask, float* partial, void* stream) {
   TOK_CHECK_ARG(mask && partial, "tok_conv_dgrad_maskstore: mask / partial must not be null");
   return dgrad_impl(d, dy, w_dgrad, dx, accumulate, nullptr, mask, partial, stream, "tok_conv_dgrad_maskstore", nullptr,
-                    nullptr, 0, nullptr, 1);
+                    0, nullptr, 1);
 }
 
 extern "C" int tok_conv_dgrad_bias(const tok_conv_desc* d, const void* dy, const void* w_dgrad, const float* bias, void* dx,
                                    int accumulate, const void* bn_y, const uint8_t* bn_mask, float* partial, void* stream) {
   TOK_CHECK_ARG((bn_y == nullptr) == (partial == nullptr), "tok_conv_dgrad_bias: bn_y and partial go together");
-  return dgrad_impl(d, dy, w_dgrad, dx, accumulate, bn_y, bn_mask, partial, stream, "tok_conv_dgrad_bias", nullptr, nullptr, 0,
+  return dgrad_impl(d, dy, w_dgrad, dx, accumulate, bn_y, bn_mask, partial, stream, "tok_conv_dgrad_bias", nullptr, 0,
                     bias);
 }
 
@@ -1267,7 +1122,7 @@ extern "C" int tok_conv_dgrad_subacc(const tok_conv_desc* d, const void* dy, con
   TOK_CHECK_ARG(dsub != nullptr, "tok_conv_dgrad_subacc: dsub must not be null");
   TOK_CHECK_ARG(!mask_store || (mask && partial && !bn_y), "tok_conv_dgrad_subacc: mask_store needs mask + partial, no bn_y");
   TOK_CHECK_ARG(mask_store || ((bn_y == nullptr) == (partial == nullptr)), "tok_conv_dgrad_subacc: bn_y and partial go together");
-  return dgrad_impl(d, dy, w_dgrad, dx, 0, bn_y, mask, partial, stream, "tok_conv_dgrad_subacc", nullptr, nullptr, 0, nullptr,
+  return dgrad_impl(d, dy, w_dgrad, dx, 0, bn_y, mask, partial, stream, "tok_conv_dgrad_subacc", nullptr, 0, nullptr,
                     mask_store, dsub);
 }
 
@@ -1285,8 +1140,7 @@ bool dgrad2_geometry(const tok_conv_desc* d1, const tok_conv_desc* d2) {
   if (d1->n != d2->n || d1->h != d2->h || d1->w != d2->w || d1->c != d2->c) return false;
   const long long rows = (long long)d1->n * d1->h * d1->w;
   // the second layer alone must sit on the 64-wide ring too: its statistics-row count is the one the caller sizes `partial` with
-  const int gridM = tok_cdiv(rows, 128);
-  if (pick_bn(d2->c, d2->k, gridM) != 64) return false;
+  if (pick_bn(d2->c, d2->k) != 64) return false;
   return pw_serves(64, rows, d1->k, d1->c) && pw_serves(64, rows, d2->k, d2->c);
 }
 }  // namespace

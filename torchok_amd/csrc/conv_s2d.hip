@@ -307,25 +307,16 @@ __global__ __launch_bounds__(256, 2) void conv_s2d_kernel(ConvArgs a, S2Geo geo)
 #undef TOK_WIN_PIXEL
 }
 
-int s2d_flag() {   // TOK_CONV_S2D=0: stride-2 data gradients stay on the implicit-GEMM kernel (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_CONV_S2D"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
 int s2d_min_tiles() {
   static const int v = [] { const char* e = getenv("TOK_CONV_S2D_MIN_TILES"); return (int)(e ? atoi(e) : 256); }();
   return v;
 }
 
 int pick_tw(int W) { return W <= 16 ? 16 : (W <= 32 ? 32 : 64); }
-int s2d_96() {      // TOK_CONV_WIN_96=0: layers of 96 / 192 channels stay on 128-wide tiles (A/B switch shared with conv_win.hip)
-  static const int v = [] { const char* e = getenv("TOK_CONV_WIN_96"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
 // channel tile of a layer of K output channels whose map gives `ptiles` pixel tiles: the widest form that does not pad (48 / 96 /
 // 192 -> 48 / 96), and 96 instead of 128 where both divide K but 128-wide tiles would leave CUs without a workgroup (HRNet-W48's
 // 384-channel branch at 16 x 32: 48 pixel tiles x 3 = 144 workgroups on 256 CUs; x 4 = 192 shorter ones)
 int pick_wbn(int K, long long ptiles) {
-  if (!s2d_96()) return K <= 64 ? 64 : 128;
   if (K == 48) return 48;
   if (K <= 64) return 64;
   if (K % 96 == 0 && K % 128 != 0) return 96;
@@ -348,14 +339,13 @@ void launch_variant(const ConvArgs& a, const S2Geo& g, int grid, hipStream_t st)
 
 // `a` as dgrad_fill (conv_igemm.hip) leaves it: gathered tensor = dY (B, P, Q, K) as (a.H, a.W, a.C), output = dX (a.P, a.Q, a.K)
 bool conv_s2d_serves(const ConvArgs& a, int stride, int pad) {
-  if (!s2d_flag()) return false;
   if (!(a.R == 3 && a.S == 3 && stride == 2 && pad == 1)) return false;
   if ((a.P & 1) || (a.Q & 1) || a.P != 2 * a.H || a.Q != 2 * a.W) return false;
   if (a.C % 8 != 0 || a.K % 8 != 0 || a.K < 32 || a.C < 32) return false;
   if (a.K > 64 && a.K < 96) return false;
   if (a.W < 12) return false;
   if (a.x_bytes >= 0x7FFFFFF0u) return false;
-  if (a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.sub != nullptr || a.fin_mode != 0) return false;
+  if (a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.sub != nullptr) return false;
   int gm, gn;
   conv_s2d_tiles(a, &gm, &gn);
   return (long long)gm * gn >= s2d_min_tiles();

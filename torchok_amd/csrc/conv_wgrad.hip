@@ -62,7 +62,7 @@ __device__ __forceinline__ bf16x4 tr_read(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p));
 }
 
-template <int TN, int TK, bool C4, int MS, bool DMA_T, bool PWK>
+template <int TN, int TK, bool C4, int MS, bool PWK>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {              // reduction rows staged per barrier (2 MFMA k-steps of 32)
   constexpr int CN = TN / 8, CK = TK / 8;      // 16-byte chunks per tile row
   constexpr int RPY = 256 / CN, RPX = 256 / CK;  // rows covered per pass
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {         
   // SOURCE side (the lane at slot c fetches logical chunk c ^ swz(row)) and on the reads.
   // Measured per layer (tools/bench_conv.py + whole-step bench): DMA wins on the short-M layers
   // (14x14, 7x7: -18 %), register staging with its longer prefetch distance on the long-M ones.
-  constexpr bool DMA = !C4 && DMA_T;
+  constexpr bool DMA = !C4;
   constexpr int YS = DMA ? TN * 2 : (TN + 16) * 2, XS = DMA ? TK * 2 : (TK + 16) * 2;  // row strides (bytes)
   constexpr int YBYTES = MS * YS, XBYTES = MS * XS;
   constexpr int SWY = CN / 2 - 1, SWX = CK / 2 - 1;   // swz(row) = (row & SW) << 1
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {         
 //                  issue stage st+2 into the buffer of stage st-1;  fragment reads + MFMAs of stage st
 // Tiles 64/128/256 x 64/128/256 (2 x 2 waves): a 64-channel layer takes a 64 x 256 (or 256 x 64) tile so that every barrier
 // still covers 16 MFMAs per wave.
-template <int TN, int TK, bool PWK>
+template <int TN, int TK>
 __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
   constexpr int MS = 32, NST = 3;
   constexpr int CN = TN / 8, CK = TK / 8;
@@ -369,11 +369,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
   const int tap = k0 / a.C;
   const int kc0 = k0 - tap * a.C;
   const int kr = tap / a.S;
-  const int ks = tap - kr * a.S;
   const bool k_ok = kr < a.R;
 
-  // row cursor: output pixel of this thread's X rows; (image, p, q) are re-derived per step by magic-number division —
-  // uniform straight-line code (the incremental "while (q >= Q)" cursor was a divergent loop per row and step)
+  // row cursor: output pixel of this thread's X rows (pointwise layers only: input pixel == output pixel)
   int xm[XP];
 #pragma unroll
   for (int i = 0; i < XP; ++i) xm[i] = mstart + xrow + i * RPX;
@@ -396,21 +394,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
     ym += MS;
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
-      uint32_t off;
-      if (PWK) {
-        off = (k_ok && xm[i] < mend) ? (uint32_t)(xm[i] * a.C + kc0) * 2u : 0xFFFFFFF0u;
-      } else {
-        const uint32_t mm = (uint32_t)min(xm[i], a.M - 1);
-        const uint32_t b = magic_div(mm, a.pq_mul, a.pq_shift);
-        const uint32_t rem = mm - b * (uint32_t)a.PQ;
-        const uint32_t pp = magic_div(rem, a.q_mul, a.q_shift);
-        const int hh = (int)pp * a.stride - a.pad + kr;
-        const int ww = (int)(rem - pp * (uint32_t)a.Q) * a.stride - a.pad + ks;
-        const bool ok = k_ok && xm[i] < mend && (unsigned)hh < (unsigned)a.H && (unsigned)ww < (unsigned)a.W;
-        uint32_t goff = (uint32_t)(((int)b * a.HW + hh * a.W + ww) * a.C + kc0) * 2u;
-        asm volatile("" : "+v"(goff));
-        off = ok ? goff : 0xFFFFFFF0u;
-      }
+      uint32_t off = (k_ok && xm[i] < mend) ? (uint32_t)(xm[i] * a.C + kc0) * 2u : 0xFFFFFFF0u;
       asm volatile("" : "+v"(off));
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrd, (lds_void*)(Xdst + i * RPX * XS), 16, off, 0, 0, 0);
       xm[i] += MS;
@@ -1227,19 +1211,11 @@ struct Plan {
   bool taps;     // tap-stationary 3x3 kernel: tilesK counts 64-wide INPUT-CHANNEL tiles
 };
 
-static int taps_enabled() {   // TOK_WGRAD_TAPS=0: 3x3 layers stay on the two-buffer kernel (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_WGRAD_TAPS"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
 static int taps_target() {    // TOK_WGRAD_TAPS_WGS=<n>: workgroups the split aims at (default 256; 512 is faster in isolation, 256 on the step)
   static const int v = [] { const char* e = getenv("TOK_WGRAD_TAPS_WGS"); return (int)(e ? atoi(e) : 256); }();
   return v;
 }
 
-static int ring_enabled() {   // TOK_WGRAD_RING=0: the two-buffer kernels of round 1 (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_WGRAD_RING"); return (int)(e ? atoi(e) : 1); }();   // 2: every layer
-  return v;
-}
 static int ring_target() {    // TOK_WGRAD_WGS=<n>: workgroups the split aims at (default: what is resident at once)
   static const int v = [] { const char* e = getenv("TOK_WGRAD_WGS"); return (int)(e ? atoi(e) : 0); }();
   return v;
@@ -1254,12 +1230,12 @@ Plan make_plan(const tok_conv_desc* d) {
   p.taps = false;
   // (64-wide channel tiles; widths that are multiples of 48 but not of 64 — HRNet's 48 / 96 — take the 48-wide form of the
   //  window kernel on stride-1 layers and stay on the two-buffer kernel otherwise)
-  const bool same3 = d->r == 3 && d->s == 3 && d->s_pad == 3 && d->stride == 1 && d->pad == 1 && taps_enabled() != 2 &&
+  const bool same3 = d->r == 3 && d->s == 3 && d->s_pad == 3 && d->stride == 1 && d->pad == 1 &&
                      (unsigned long long)d->n * d->h * d->w * d->c * 2 < 0x40000000ull &&
                      (unsigned long long)d->n * d->p * d->q * d->k * 2 < 0x40000000ull;
   const bool w64 = d->c % 64 == 0 && d->k % 64 == 0;
-  const bool w48 = !w64 && d->c % 48 == 0 && d->k % 48 == 0 && same3 && taps_enabled() != 3;   // window kernel only
-  if (d->c != 4 && (w64 || w48) && d->r == 3 && d->s == 3 && d->s_pad == 3 && taps_enabled()) {
+  const bool w48 = !w64 && d->c % 48 == 0 && d->k % 48 == 0 && same3;   // window kernel only
+  if (d->c != 4 && (w64 || w48) && d->r == 3 && d->s == 3 && d->s_pad == 3) {
     p.taps = true; p.ring = false;
     p.TN = w64 ? 64 : 48; p.TK = p.TN; p.MS = 32;
     p.tilesN = tok_cdiv(d->k, p.TN);
@@ -1276,7 +1252,7 @@ Plan make_plan(const tok_conv_desc* d) {
     p.splitM = (int)((M + chunk - 1) / chunk);
     return p;
   }
-  p.ring = d->c != 4 && ring_enabled() && ((d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0) || ring_enabled() == 2);
+  p.ring = d->c != 4 && d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0;
   if (p.ring) {
     // ring kernel: 32 reduction rows per stage, three stages.  Narrow layers take a 64 x 256 / 256 x 64 tile.
     p.MS = 32;
@@ -1326,8 +1302,7 @@ Plan make_plan(const tok_conv_desc* d) {
   long long split = (tb_target + tiles - 1) / tiles;  // aim at ~4 workgroups per CU
   // reduction rows per barrier: 64 on the long-M layers (twice the MFMAs per barrier), 32 where M is
   // short and occupancy (4 workgroups per CU instead of 2) matters more
-  static const int ms64_any = [] { const char* e = getenv("TOK_WGRAD_MS64_ANY"); return (int)(e ? atoi(e) : 0); }();     // TOK_WGRAD_MS64_ANY=1: 64 rows per barrier on every long-M tile shape (experiment)
-  p.MS = (M >= 100000 && ((p.TN == 128 && p.TK == 128) || ms64_any)) ? 64 : 32;
+  p.MS = (M >= 100000 && p.TN == 128 && p.TK == 128) ? 64 : 32;
   const long long max_split = (M + 8 * p.MS - 1) / (8 * p.MS);   // at least 8 steps per workgroup
   if (split > max_split) split = max_split;
   // (512 only for the stem — 2 tiles over 3.2 M pixels at B = 256: 512 workgroups left every CU with 2 and the launch
@@ -1342,53 +1317,37 @@ Plan make_plan(const tok_conv_desc* d) {
   return p;
 }
 
-template <int TN, int TK, bool PWK>
-void launch_ring_pw(const WgradArgs& a, hipStream_t st) {
+template <int TN, int TK>
+void launch_ring(const WgradArgs& a, hipStream_t st) {
   constexpr int smem = 3 * 32 * (TN + TK) * 2;
   static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ring_kernel<TN, TK, PWK>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ring_kernel<TN, TK>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     return true;
   }();   // once per process (thread-safe function-local static)
   (void)attr_set;
-  hipLaunchKernelGGL((conv_wgrad_ring_kernel<TN, TK, PWK>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(256), smem, st, a);
+  hipLaunchKernelGGL((conv_wgrad_ring_kernel<TN, TK>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(256), smem, st, a);
 }
 
-template <int TN, int TK>
-void launch_ring(const WgradArgs& a, hipStream_t st) {
-  if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) launch_ring_pw<TN, TK, true>(a, st);
-  else launch_ring_pw<TN, TK, false>(a, st);
-}
-
-template <int TN, int TK, bool C4, int MS, bool DMA_T, bool PWK>
+template <int TN, int TK, bool C4, int MS, bool PWK>
 void launch_wgrad_pw(const WgradArgs& a, hipStream_t st) {
   constexpr int smem = 2 * MS * ((TN + 16) * 2 + (TK + 16) * 2);   // (the unpadded DMA layout needs less)
   static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TN, TK, C4, MS, DMA_T, PWK>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TN, TK, C4, MS, PWK>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     return true;
   }();   // once per process (thread-safe function-local static)
   (void)attr_set;
-  hipLaunchKernelGGL((conv_wgrad_kernel<TN, TK, C4, MS, DMA_T, PWK>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(256),
+  hipLaunchKernelGGL((conv_wgrad_kernel<TN, TK, C4, MS, PWK>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(256),
                      smem, st, a);
-}
-
-template <int TN, int TK, bool C4, int MS, bool DMA_T>
-void launch_wgrad_dma(const WgradArgs& a, hipStream_t st) {
-  if constexpr (!C4) {
-    if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) { launch_wgrad_pw<TN, TK, C4, MS, DMA_T, true>(a, st); return; }
-  }
-  launch_wgrad_pw<TN, TK, C4, MS, DMA_T, false>(a, st);
 }
 
 template <int TN, int TK, bool C4, int MS>
 void launch_wgrad_ms(const WgradArgs& a, hipStream_t st) {
   if constexpr (!C4) {
-    static long long dma_rows = -1;      // TOK_WGRAD_DMA_ROWS=<n>: layers with fewer output pixels stage by DMA
-    if (dma_rows < 0) { const char* e = getenv("TOK_WGRAD_DMA_ROWS"); dma_rows = e ? atoll(e) : (1ll << 40); }
-    if (a.M < dma_rows) { launch_wgrad_dma<TN, TK, C4, MS, true>(a, st); return; }
+    if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) { launch_wgrad_pw<TN, TK, C4, MS, true>(a, st); return; }
   }
-  launch_wgrad_dma<TN, TK, C4, MS, false>(a, st);
+  launch_wgrad_pw<TN, TK, C4, MS, false>(a, st);
 }
 
 template <int TN, int TK, bool C4>
@@ -1492,8 +1451,7 @@ int wgrad_impl(const tok_conv_desc* d, const void* x, const void* dy, float* dw,
     (void)attr_set;
     // stride 1 / "same" padding: the shared-window kernel (its idle DMA lanes sit at 2^31 + 2^30: tensors below 1 GiB — make_plan
     // sends 48-wide layers elsewhere above that, 64-wide ones take the per-tap kernel below)
-    const bool same = a.stride == 1 && a.pad == 1 && a.P == a.H && a.Q == a.W && a.x_bytes < 0x40000000u && a.dy_bytes < 0x40000000u &&
-                      taps_enabled() != 2;
+    const bool same = a.stride == 1 && a.pad == 1 && a.P == a.H && a.Q == a.W && a.x_bytes < 0x40000000u && a.dy_bytes < 0x40000000u;
     if (same) {
       // (probe, round 6: asking for 160 KB of LDS — no LDS-using workgroup of another kernel beside this one — costs HRNet-W48 +1.2 ms and
       //  ResNet-50 +0.13 ms per step: the co-residency of the main stream's kernels is worth more than an undisturbed CU;

@@ -319,25 +319,16 @@ __global__ __launch_bounds__(256, 2) void conv_win_kernel(ConvArgs a, WinGeo geo
 #undef TOK_WIN_PIXEL
 }
 
-int win_flag() {   // TOK_CONV_WIN=0: 3x3 layers stay on the implicit-GEMM kernels (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_CONV_WIN"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
 int win_min_tiles() {
   static const int v = [] { const char* e = getenv("TOK_CONV_WIN_MIN_TILES"); return (int)(e ? atoi(e) : 128); }();
   return v;
 }
 
 int pick_tw(int W) { return W <= 16 ? 16 : (W <= 32 ? 32 : 64); }
-int win_96() {      // TOK_CONV_WIN_96=0: layers of 48 / 96 / 192 channels stay on 64- / 128-wide tiles (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_CONV_WIN_96"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
 // channel tile of a layer of K output channels whose map gives `ptiles` pixel tiles: the widest form that does not pad (48 / 96 /
 // 192 -> 48 / 96), and 96 instead of 128 where both divide K but 128-wide tiles would leave CUs without a workgroup (HRNet-W48's
 // 384-channel branch at 16 x 32: 48 pixel tiles x 3 = 144 workgroups on 256 CUs; x 4 = 192 shorter ones)
 int pick_wbn(int K, long long ptiles) {
-  if (!win_96()) return K <= 64 ? 64 : 128;
   if (K == 48) return 48;
   if (K <= 64) return 64;
   if (K % 96 == 0 && K % 128 != 0) return 96;
@@ -360,14 +351,13 @@ void launch_variant(const ConvArgs& a, const WinGeo& g, int grid, hipStream_t st
 
 // geometry of the 3x3 window kernel for an (H x W, C -> K) layer over B images; gathered tensor = (B, H, W, C)
 bool conv_win_serves(const ConvArgs& a) {
-  if (!win_flag()) return false;
   if (!(a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1)) return false;
   if (a.H != a.P || a.W != a.Q) return false;
   if (a.C % 8 != 0 || a.K % 8 != 0 || a.K < 32 || a.C < 32) return false;
   if (a.K > 64 && a.K < 96) return false;          // 72 / 80 / 88 channels would leave 128-wide tiles a third empty
   if (a.W < 12) return false;                       // 7 x 7 maps would use 7 of 16 columns
   if (a.x_bytes >= 0x7FFFFFF0u) return false;       // window offsets are kept as non-negative ints
-  if (a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.sub != nullptr || a.fin_mode != 0) return false;
+  if (a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.sub != nullptr) return false;
   int gm, gn;
   conv_win_tiles(a, &gm, &gn);
   return (long long)gm * gn >= win_min_tiles();

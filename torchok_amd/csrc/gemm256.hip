@@ -286,7 +286,7 @@ int g256_min_tiles() {
 // epilogue mode — so every mode that writes statistics rows must be served whenever the geometry is (plain, BatchNorm forward /
 // backward sums, mask-store: all here; fused activation has no rows); the modes below carry no rows (or, fused finalize, fold their own) and fall back freely.
 bool gemm256_modes(const ConvArgs& a) {
-  if (a.ep_scale != nullptr || a.sub != nullptr || a.fin_mode != 0) return false;
+  if (a.ep_scale != nullptr || a.sub != nullptr) return false;
   if (a.mask_store && (a.bn_mask == nullptr || a.stats == nullptr)) return false;
   // (fused activation — round 4's gemm256_kernel<4> — was bit-identical and 0.06 ms slower on the step: DESIGN.md "measured and rejected")
   if (a.y2 != nullptr || a.act_x != nullptr) return false;

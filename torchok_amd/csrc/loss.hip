@@ -666,9 +666,8 @@ __global__ __launch_bounds__(256) void upce_bwd_tiled_kernel(const bf16* __restr
 
 // window of UT source pixels at destination/source ratio r: (UT - 1) r between first and last pixel + (2 r + 4) per pixel
 bool up_tiled_ok(const UpArgs& a) {
-  static const int flag = [] { const char* e = getenv("TOK_UPCE_TILED"); return (int)(e ? atoi(e) : 1); }();
   const float r = fmaxf(1.f / a.sh, 1.f / a.sw);
-  return flag && (int)ceilf((UT + 1) * r) + 4 <= UWIN;
+  return (int)ceilf((UT + 1) * r) + 4 <= UWIN;
 }
 
 bool fill_up(UpArgs& a, int n, int hs, int ws, int classes, int ld, int hd, int wd) {
@@ -726,7 +725,7 @@ extern "C" int tok_upsample_ce_bwd(const void* low, int n, int hs, int ws, int c
     const int tiles_y = tok_cdiv(hs, UT), tiles_x = tok_cdiv(ws, UT);
     const int tgrid = n * tiles_y * tiles_x;
     const int smem = UWIN * UWIN * ld * 2;
-#define TOK_UPCE_TILED(NV)                                                                                                          \
+#define UPCE_TILED_LAUNCH(NV)                                                                                                          \
     {                                                                                                                               \
       static const bool attr_set = [] {                                                                                             \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upce_bwd_tiled_kernel<NV>),                                        \
@@ -738,12 +737,12 @@ extern "C" int tok_upsample_ce_bwd(const void* low, int n, int hs, int ws, int c
                          lse, loss, gscale, (bf16*)dlow, accumulate, tiles_y, tiles_x);                                             \
     }
     switch (ld >> 3) {
-      case 1: TOK_UPCE_TILED(1) break;
-      case 2: TOK_UPCE_TILED(2) break;
-      case 3: TOK_UPCE_TILED(3) break;
-      default: TOK_UPCE_TILED(4) break;
+      case 1: UPCE_TILED_LAUNCH(1) break;
+      case 2: UPCE_TILED_LAUNCH(2) break;
+      case 3: UPCE_TILED_LAUNCH(3) break;
+      default: UPCE_TILED_LAUNCH(4) break;
     }
-#undef TOK_UPCE_TILED
+#undef UPCE_TILED_LAUNCH
     TOK_CHECK_LAUNCH("tok_upsample_ce_bwd(tiled)");
     return TOK_OK;
   }

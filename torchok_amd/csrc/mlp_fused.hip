@@ -488,10 +488,7 @@ void launch_c(const MlpArgs& a, int c, hipStream_t st) {
   // -8 % (C = 384) / -28 % (C = 192), no stage barrier -7 %: no single bound, the stage's three phases serialise per wave.
   // C = 192 forward on 64 hidden units per stage (half the stage barriers: 259 vs 292 us in save mode; the backward spills at
   // that stage size: 349 vs 278 us; C = 96 with 128 per stage: 406 vs 376 us)
-  static const int w4 = [] { const char* e = getenv("TOK_MLP_W4"); return (int)(e ? atoi(e) : 0); }();
-  if (c == 96 && w4) launch_m<96, 64, 2, 4, true, MODE>(a, st);
-  else if (c == 192 && w4) launch_m<192, 32, 2, 4, false, MODE>(a, st);
-  else if (c == 96) launch_m<96, 64, 2, 8, true, MODE>(a, st);
+  if (c == 96) launch_m<96, 64, 2, 8, true, MODE>(a, st);
   else if (c == 192) {
     // (if constexpr: the 64-per-stage backward form spills 44-58 VGPRs and must not even be instantiated)
     if constexpr (MODE == 0) launch_m<192, 64, 2, 8, false, MODE>(a, st);
@@ -504,20 +501,11 @@ int mlp_min_rows() {   // below this the serial chain of hidden chunks of one ti
   static const int v = [] { const char* e = getenv("TOK_MLP_MIN_ROWS"); return (int)(e ? atoi(e) : 32768); }();
   return v;
 }
-int mlp_max_c() {   // TOK_MLP_MAX_C=<c>: widths above c stay on the two GEMM launches (A/B switch per stage)
-  static const int v = [] { const char* e = getenv("TOK_MLP_MAX_C"); return (int)(e ? atoi(e) : 384); }();
-  return v;
-}
-int mlp_flag() {   // TOK_MLP_FUSED=0: the MLP stays on the two GEMM launches (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_MLP_FUSED"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
 
 }  // namespace
 
 extern "C" int tok_mlp_serves(int64_t rows, int c, int hidden) {
-  if (!mlp_flag()) return 0;
-  if (!(c == 96 || c == 192 || c == 384) || c > mlp_max_c()) return 0;
+  if (!(c == 96 || c == 192 || c == 384)) return 0;
   if (hidden != 4 * c) return 0;
   if (rows < mlp_min_rows() || rows <= 0 || rows * (long long)hidden * 2 >= (1ll << 32)) return 0;
   return 1;

@@ -35,4 +35,3 @@ struct PwArgs {
 // 0 = launched; > 0: this configuration is not served by the ring kernel (caller falls back); < 0: error
 int pw_ring_launch(const PwArgs& a, int bn_tile, hipStream_t st);
 int pw_ring_grid(int bn_tile, int gridM, int gridN);   // persistent grid size (for the statistics-row count)
-bool pw_ring_enabled();

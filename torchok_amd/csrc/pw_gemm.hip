@@ -429,11 +429,6 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void pw_gemm_ring_kernel(PwA
   }
 }
 
-int ring_flag() {   // TOK_PW_RING=0: every pointwise launch stays on conv_igemm's two-buffer loop (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_PW_RING"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
-
 template <int BN, bool BNEP>
 int launch_ring(const PwArgs& a, hipStream_t st) {
   constexpr int STAGE = BM * BK * 2 + BN * BK * 2 + (BN == 64 ? 1024 : 4096);
@@ -468,8 +463,6 @@ int launch_ring(const PwArgs& a, hipStream_t st) {
 
 }  // namespace
 
-bool pw_ring_enabled() { return ring_flag() != 0; }
-
 int pw_ring_grid(int bn_tile, int gridM, int gridN) {
   const int unit = 8 * gridN;
   int G = 256 * (bn_tile == 64 ? 2 : 1);
@@ -481,7 +474,6 @@ int pw_ring_grid(int bn_tile, int gridM, int gridN) {
 }
 
 int pw_ring_launch(const PwArgs& a, int bn_tile, hipStream_t st) {
-  if (!pw_ring_enabled()) return 1;
   if (a.C % 8 != 0 || a.N % 8 != 0) return 1;
   if (a.mask_in != nullptr && a.N % 64 != 0) return 1;       // mask rows are fetched as aligned 4 / 16-byte pieces
   if (a.accumulate && a.e1 == nullptr) return 1;

@@ -813,8 +813,7 @@ extern "C" int tok_bilinear_sum_stats(const void* y0, const void* t1, int h1, in
   }
   a.n = n; a.h = h; a.w = w; a.c = c;
   const int rows = tok_bilinear_sum_stats_rows(n, h, w, c);
-  static const int off = [] { const char* e = getenv("TOK_BILINEAR_SUM_TILED"); return (int)(e ? atoi(e) == 0 : 0); }();   // A/B switch
-  if (tiled && !off) {
+  if (tiled) {
     hipLaunchKernelGGL(bilinear_sum_tiled_kernel, dim3(rows), dim3(256), 0, tok_stream(stream), u);
   } else {
     // (any grid works for the generic kernel: blocks beyond the rows write zero partials)
@@ -845,9 +844,8 @@ extern "C" int tok_bilinear_bwd_multi(const void* ddst, int n, int hd, int wd, i
     if (hs[j] * f == hd && ws[j] * f == wd && slot != nullptr && *slot == nullptr) *slot = (bf16*)ds[j];   // one source per factor
     else fast = false;
   }
-  static const int off = [] { const char* e = getenv("TOK_BILINEAR_ADJ3"); return (int)(e ? atoi(e) == 0 : 0); }();   // A/B switch
   if (present == 0) return TOK_OK;
-  if (fast && !off) {
+  if (fast) {
     static const bool attr_set = [] {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bilinear_adj3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 ADJ_SMEM);

@@ -351,18 +351,12 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_kernel(StemWg a) {
     }
 }
 
-int stem_flag() {   // TOK_STEM_WIN=0: the stem stays on conv_igemm's C4 path (A/B switch)
-  static const int v = [] { const char* e = getenv("TOK_STEM_WIN"); return (int)(e ? atoi(e) : 1); }();
-  return v;
-}
-
 }  // namespace
 
 bool stem_win_serves(const ConvArgs& a) {
-  if (!stem_flag()) return false;
   if (!(a.C == 4 && a.R == 7 && a.S == 8 && a.stride == 2 && a.pad == 3)) return false;
   if (a.K % 8 != 0 || a.K > 64 || a.W % 2 != 0) return false;
-  if (a.bias != nullptr || a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.fin_mode != 0 || a.accumulate) return false;
+  if (a.bias != nullptr || a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.accumulate) return false;
   return (long long)(a.M / (a.P * a.Q)) * tok_cdiv(a.P, ST_T) * tok_cdiv(a.Q, ST_T) >= 16;      // (tiny inputs: not worth a second kernel)
 }
 
@@ -383,8 +377,6 @@ int stem_win_launch(ConvArgs& a, int stat_rows, hipStream_t st) {
 }
 
 bool stem_wgrad_serves(const tok_conv_desc* d) {
-  static const int on = [] { const char* e = getenv("TOK_STEM_WGRAD"); return (int)(e ? atoi(e) : 1); }();   // TOK_STEM_WGRAD=0: conv_wgrad_kernel's C4 path (A/B switch)
-  if (!on || !stem_flag()) return false;
   if (!(d->c == 4 && d->r == 7 && d->s == 7 && d->s_pad == 8 && d->stride == 2 && d->pad == 3)) return false;
   if (d->k % 8 != 0 || d->k > 64 || d->w % 2 != 0) return false;
   return (long long)d->n * tok_cdiv(d->p, SG_TH) * tok_cdiv(d->q, SG_TW) >= 16;

@@ -1174,12 +1174,6 @@ inline int blocks_for(size_t total) {
   return (int)(b > 65536 ? 65536 : (b < 1 ? 1 : b));
 }
 
-// TOK_ATTN_SCALAR=1 forces the VALU reference kernels (debugging aid)
-inline bool tok_attn_scalar() {
-  static const int v = [] { const char* e = getenv("TOK_ATTN_SCALAR"); return (int)((e && e[0] == '1') ? 1 : 0); }();
-  return v == 1;
-}
-
 bool fill_attn(AttnArgs& a, int B, int H, int W, int C, int heads, int ws, int shift, int ld) {
   if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || ws <= 0 || C != heads * HD || H % ws || W % ws || shift < 0 ||
       shift >= ws || ld < 3 * C || (ld & 7)) return false;
@@ -1258,8 +1252,7 @@ extern "C" int tok_layernorm_bwd(const void* dout, const void* x, const float* m
 extern "C" int tok_colsum_f32(const float* src, int64_t rows, int cols, float* dst, int accumulate, void* stream) {
   TOK_CHECK_ARG(src && dst && rows > 0 && cols > 0, "tok_colsum_f32: bad args");
   if (tok_dbg_skip(4)) return TOK_OK;
-  static const int wide = [] { const char* e = getenv("TOK_COLSUM_WIDE"); return e ? atoi(e) : 1; }();   // 0: the narrow kernel everywhere (A/B switch)
-  if (wide && cols >= 2048) {
+  if (cols >= 2048) {
     hipLaunchKernelGGL(colsum_f32_wide_kernel, dim3((cols + 255) / 256), dim3(1024), 0, tok_stream(stream), src, rows, cols, dst,
                        accumulate);
     TOK_CHECK_LAUNCH("tok_colsum_f32(wide)");
@@ -1323,7 +1316,7 @@ extern "C" int tok_window_attn_fwd(const void* qkv, int batch, int h, int w, int
   a.plain = logit_scale == nullptr;
   TOK_CHECK_ARG(!a.plain || (a.N <= 64 && !mask && shift == 0),
                 "tok_window_attn_fwd: the plain mode covers unshifted windows of up to 64 tokens");
-  if (a.N <= 64 && (a.plain || !tok_attn_scalar())) {
+  if (a.N <= 64) {
     const int bpw = attn_bpw(a);
     const int groups = tok_cdiv(batch, bpw) * a.nW * heads;
     hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(8 * tok_cdiv(groups, 8)), dim3(256), MFMA_FWD_LDS, tok_stream(stream), a,
@@ -1349,7 +1342,7 @@ extern "C" int tok_window_attn_fwd(const void* qkv, int batch, int h, int w, int
 extern "C" int tok_window_attn_bwd_rows(int batch, int h, int w, int heads, int ws) {
   AttnArgs a;
   if (!fill_attn(a, batch, h, w, heads * HD, heads, ws, 0, 3 * heads * HD)) return TOK_ERR_INVALID;
-  if (a.N <= 64 && !tok_attn_scalar()) return tok_cdiv(batch, attn_bpw(a)) * a.nW;
+  if (a.N <= 64) return tok_cdiv(batch, attn_bpw(a)) * a.nW;
   return batch * a.nW;
 }
 
@@ -1362,7 +1355,7 @@ extern "C" int tok_window_attn_bwd(const void* qkv, const void* dout, int batch,
   a.plain = logit_scale == nullptr;
   TOK_CHECK_ARG(a.plain ? (!bias && !mask && shift == 0 && a.N <= 64) : (bias && ds_scratch && dscale_part),
                 "tok_window_attn_bwd: bad args (plain mode: no bias / mask / shift, windows of up to 64 tokens)");
-  if (a.N <= 64 && (a.plain || !tok_attn_scalar())) {
+  if (a.N <= 64) {
     const int bpw = attn_bpw(a);
     const int waves = tok_cdiv(batch, bpw) * a.nW * heads;
     static const bool attr_m = [&] {

@@ -24,11 +24,6 @@ from .. import _C
 BF16 = torch.bfloat16
 
 
-# main-stream weight gradients run this many units late (Region.defer_wgrad); 0: in place.  Measured on ResNet-50 B=256: see
-# DESIGN.md section 8
-WGRAD_DEFER = int(os.environ.get('TOK_WGRAD_DEFER', '0'))   # measured: 0 -> 19.62, 3 -> 19.66, 5 -> 19.74, 8 -> 19.73 ms/step: off
-
-
 # TOK_HOST_PROF=1: host seconds spent enqueuing each node class's backward (tools: where the launch thread goes)
 HOST_PROF = os.environ.get('TOK_HOST_PROF', '0') == '1'
 _host_prof = {}
@@ -353,7 +348,6 @@ _tls = threading.local()
 _side_streams = {}
 _branch_streams = {}
 BRANCH_STREAMS = os.environ.get('TOK_BRANCH_STREAMS', '1') == '1'
-LAZY_EVENTS = os.environ.get('TOK_LAZY_EVENTS', '1') == '1'
 
 
 # ---- streams on distinct hardware queues -------------------------------------------------------------------------------
@@ -365,7 +359,6 @@ LAZY_EVENTS = os.environ.get('TOK_LAZY_EVENTS', '1') == '1'
 # is first needed: a candidate shares a queue with stream `a` iff an event recorded on the idle candidate completes only
 # after a spin kernel given to `a` before it.  The pick never shares with the main stream if any of eight candidates
 # avoids it, and shares with as few (and as recently picked) of the streams already handed out as possible.
-PICK_STREAMS = os.environ.get('TOK_PICK_STREAMS', '1') == '1'
 _picked = {}          # device -> streams handed out by pick_stream
 _main_hint = {}       # device -> the stream regions are opened on (Region.input): what "beside the main stream" refers to
 
@@ -394,25 +387,21 @@ def _shares_queue(a: 'torch.cuda.Stream', b: 'torch.cuda.Stream') -> bool:
     return e0.elapsed_time(eb) > 0.5 * e0.elapsed_time(ea)
 
 
-# TOK_STREAM_PRIO=-1: the picked (side / branch / comm) streams are created with HIGH priority (experiment, round 5)
-_STREAM_PRIO = int(os.environ.get('TOK_STREAM_PRIO', '0'))
-
-
 def pick_stream(device, main: Optional['torch.cuda.Stream'] = None, share_cost: Optional[int] = None) -> 'torch.cuda.Stream':
     """A new stream for work that is meant to run BESIDE the calling (main) stream and beside the streams picked before.
     `share_cost`: what it costs a LATER pick to land on this stream's hardware queue (default: 2 + how long ago it was handed
     out — HRNet's branches are handed out busiest first).  The weight-gradient side stream passes 1: in a process that ran a
     ResNet first (bench.py's secondary workloads) HRNet-W48's third branch stream otherwise shared a queue with the second one
     and left the side stream, which only its neck / head region uses, a queue of its own (67.2 vs 65.6 ms/step)."""
-    if (not PICK_STREAMS or torch.cuda.is_current_stream_capturing()):
-        return torch.cuda.Stream(device=device, priority=_STREAM_PRIO)
+    if torch.cuda.is_current_stream_capturing():
+        return torch.cuda.Stream(device=device)
     with torch.cuda.device(device):
         if main is None:
             main = _main_hint.get(str(device)) or torch.cuda.current_stream()
         others = _picked.setdefault(str(device), [])
         best, best_cost = None, None
         for _ in range(8):
-            c = torch.cuda.Stream(device=device, priority=_STREAM_PRIO)
+            c = torch.cuda.Stream(device=device)
             cost = 1000 * int(_shares_queue(main, c))
             if cost < 1000:
                 # when sharing cannot be avoided (five streams on four queues: HRNet's three branch streams + the side
@@ -427,19 +416,12 @@ def pick_stream(device, main: Optional['torch.cuda.Stream'] = None, share_cost: 
     return best
 
 
-# TOK_BRANCH_MAP="0,1,2,2": branch index -> stream slot (experiment: HRNet's four branches + the side stream are five streams on
-# four hardware queues; folding two of the small branches onto one stream gives every stream a queue of its own)
-_BRANCH_MAP = [int(v) for v in os.environ['TOK_BRANCH_MAP'].split(',')] if os.environ.get('TOK_BRANCH_MAP') else None
-
-
 def _branch_stream(device, idx: int) -> 'torch.cuda.Stream':
-    if _BRANCH_MAP is not None and idx < len(_BRANCH_MAP):
-        idx = _BRANCH_MAP[idx]
     key = (device, idx)
     s = _branch_streams.get(key)
     if s is None:
         s = pick_stream(device)
-        if PICK_STREAMS and torch.cuda.is_current_stream_capturing():
+        if torch.cuda.is_current_stream_capturing():
             return s     # an unprobed stream (no probing under capture): not remembered, the first eager use picks again
         _branch_streams[key] = s
     return s
@@ -490,7 +472,7 @@ def _side_stream(device) -> 'torch.cuda.Stream':
     s = _side_streams.get(device)
     if s is None:
         s = pick_stream(device, share_cost=1)
-        if PICK_STREAMS and torch.cuda.is_current_stream_capturing():
+        if torch.cuda.is_current_stream_capturing():
             return s     # see _branch_stream
         _side_streams[device] = s
     return s
@@ -544,7 +526,6 @@ class Region:
         self.device = None
         self._side = None
         self._deferred = []
-        self._wq = []          # main-stream weight-gradient launches held back (defer_wgrad)
         self._raw_used = []    # library events handed out since the last join (raw_event)
         self._tag = 0            # branch stream index of the units being recorded (0 = main)
         self._streams = {}       # branch index -> stream, for the branches this region used
@@ -696,8 +677,7 @@ class Region:
                     # a gradient written for a producer that sits on another stream: that edge is known now, so its event
                     # is recorded here, right behind the writer (precise: HRNet's fuse layers, 78.8 -> 77.5 ms/step against
                     # the lazy record alone).  Anything else gets its event at the first cross-stream reader, if ever.
-                    if _ms.touched and (not LAZY_EVENTS or any(
-                            t.node is not None and getattr(t.node, 'stream_tag', 0) != node.stream_tag for t in _ms.touched)):
+                    if any(t.node is not None and getattr(t.node, 'stream_tag', 0) != node.stream_tag for t in _ms.touched):
                         ev = torch.cuda.Event()
                         ev.record(s)
                         _ms.events[s] = (seq, ev)
@@ -726,13 +706,6 @@ class Region:
             node.release()
 
     # -- side stream (weight gradients run beside the main chain) --------------------------------
-    def mark_side(self):
-        """An event on the main stream NOW, for a later fork_side(..., event=...): the side kernels are then ordered after
-        the main stream's work up to this point only, although the host enqueues them after further main-stream launches."""
-        ev = torch.cuda.Event()
-        ev.record(cur_stream())
-        return ev
-
     def raw_event(self):
         """A HIP event from the library's pool, for tok_next_launch_event + fork_side(raw_event=...); recycled at the join."""
         dev = torch.cuda.current_device()
@@ -743,21 +716,18 @@ class Region:
         self._raw_used.append((dev, ev))
         return ev
 
-    def fork_side(self, keep_alive, event=None, raw_event=None):
+    def fork_side(self, keep_alive, raw_event=None):
         """Context manager: kernels enqueued inside run on this device's side stream, ordered after everything the
-        main stream has been given so far (or up to `event`, see mark_side).  `keep_alive` (tensors the side kernels read
-        or use as scratch) stay referenced until the join, so the allocator cannot hand their memory to later main-stream
-        work."""
+        main stream has been given so far.  `keep_alive` (tensors the side kernels read or use as scratch) stay referenced
+        until the join, so the allocator cannot hand their memory to later main-stream work."""
         main = cur_stream()
         side = _side_stream(main.device)
         if raw_event is not None:
             # the event is signalled by the completion of a kernel already launched on the main stream (no record packet)
             _C.check(_C.lib().tok_stream_wait_event(side.cuda_stream, raw_event), 'tok_stream_wait_event')
         else:
-            ev = event
-            if ev is None:
-                ev = torch.cuda.Event()
-                ev.record(main)
+            ev = torch.cuda.Event()
+            ev.record(main)
             side.wait_event(ev)
         self._side = (main, side)
         self._deferred.extend(keep_alive)
@@ -766,25 +736,7 @@ class Region:
     def keep_until_join(self, *tensors):
         self._deferred.extend(tensors)
 
-    # -- held-back weight gradients ------------------------------------------------------------------
-    def defer_wgrad(self, fn):
-        """Run `fn` (a main-stream weight-gradient launch; nothing downstream waits for its result) WGRAD_DEFER units later
-        than its place in the tape.  The last ones are therefore still pending when the backward walk reaches the region
-        input, and run beside the side stream's final launches (the stem's issue-bound weight gradient in a ResNet) instead
-        of leaving the main stream idle until the join."""
-        if WGRAD_DEFER <= 0 or torch.cuda.is_current_stream_capturing():
-            fn()
-            return
-        self._wq.append(fn)
-        if len(self._wq) > WGRAD_DEFER:
-            self._wq.pop(0)()
-
-    def flush_wgrads(self):
-        while self._wq:
-            self._wq.pop(0)()
-
     def join_side(self):
-        self.flush_wgrads()
         if self._side is not None:
             cur_stream().wait_stream(self._side[1])
             self._side = None

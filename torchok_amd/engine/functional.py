@@ -127,51 +127,33 @@ def get_packs(weight: nn.Parameter, bias: Optional[nn.Parameter], kp: int, sp: i
 
 
 WGRAD_SIDE_STREAM = os.environ.get('TOK_WGRAD_SIDE', '1') == '1'
-# which weight gradients go to the side stream: 'all', or only the LDS/MFMA-bound ones ('3x3': filters larger than 1x1),
-# whose resource profile complements the HBM-bound main chain
-WGRAD_AFTER_DGRAD = os.environ.get('TOK_WGRAD_AFTER_DGRAD', '0') == '1'   # measured: 22.0 vs 21.1 ms/step — the later start costs more
+# which weight gradients go to the side stream: the LDS/MFMA-bound ones (filters larger than 1x1), whose resource profile
+# complements the HBM-bound main chain, and the short-M or MFMA-bound pointwise ones (_wgrad_side_ok).  Measured (ResNet-50,
+# unit-3 fusion on): every weight gradient on the side stream 21.58, this choice 21.45 ms/step
 WGRAD_SIDE_MAX_ROWS = int(os.environ.get('TOK_WGRAD_SIDE_MAX_ROWS', '100000'))
-WGRAD_SIDE_WHICH = os.environ.get('TOK_WGRAD_SIDE_WHICH', '3x3')   # measured (ResNet-50, unit-3 fusion on): all 21.58, 3x3 21.45 ms/step
 # long-M pointwise weight gradients stay on the main stream when they are HBM-bound like the chain they would fight (ResNet-50: 51-102
 # MACs per operand element), and go to the side stream when they are MFMA-bound (HRNet-W48's 720 -> 720 neck convolution over 786 432
 # pixels: 360): HRNet-W48 70.65 -> 69.83 ms/step, ResNet-50 / SwinV2-T unchanged (profiles/r05_side_stream_resweep.txt)
 WGRAD_SIDE_MIN_INTENSITY = float(os.environ.get('TOK_WGRAD_SIDE_MIN_INTENSITY', '128'))
 
 
-def _pointwise_wgrad_is_mfma_bound(k, c) -> bool:
-    return (k * c) / float(k + c) >= WGRAD_SIDE_MIN_INTENSITY
+def _wgrad_side_ok(r, s, m, k, c) -> bool:
+    return r * s > 1 or m < WGRAD_SIDE_MAX_ROWS or (k * c) / float(k + c) >= WGRAD_SIDE_MIN_INTENSITY
 
 
 # Only units of the MAIN stream fork their weight gradients to the side stream (round 6).  A unit recorded on a branch stream
 # (HRNet's low-resolution branches, SwinV2's position-bias chain) keeps them on its own stream: with three branch streams + the
 # side stream there are more streams than hardware queues (two share one), and the side queue — every weight gradient of every
 # branch in one FIFO — was 33 ms busy beside a 46-ms HRNet-W48 backward.  HRNet-W48 B=24: 67.1 -> 66.1 ms/step (nobody forks:
-# 66.1 as well; only the branches fork: 67.9).  TOK_WGRAD_SIDE_TAGS=<comma-separated stream tags that fork> overrides ("0,1,2,3":
-# rounds 1-5).
-_SIDE_TAGS = {int(v) for v in os.environ.get('TOK_WGRAD_SIDE_TAGS', '0').split(',') if v != ''}
-_SIDE_TAGS_FORCED = 'TOK_WGRAD_SIDE_TAGS' in os.environ
+# 66.1 as well; only the branches fork: 67.9).
 
 
 def _side_for_tag(tag, region=None) -> bool:
     # ... and nobody forks in a region whose main stream and branch streams alone fill the four hardware queues (HRNet-W48: main +
     # three branches; a fifth stream shares a queue with one of them: 65.4 vs 65.9 ms/step without the side stream, same box)
-    if int(tag or 0) not in _SIDE_TAGS:
+    if tag:
         return False
-    return _SIDE_TAGS_FORCED or region is None or len(getattr(region, '_streams', ())) < 3
-
-
-FUSE_BN_FINALIZE = os.environ.get('TOK_FUSE_BN_FINALIZE', '0') == '1'    # tok_conv_*_bn ("last workgroup finalizes") measured slower than the stand-alone finalize launches, see DESIGN.md §4
-_ticket_rings = {}
-
-
-def _ticket_counters(device):
-    """Pointer to 64 zeroed device ints for one fused-finalize launch.  A ring of 256 slots per device: kernels
-    leave their counters zero, and no 256 such launches are ever in flight at once."""
-    ring = _ticket_rings.get(device)
-    if ring is None:
-        ring = _ticket_rings[device] = [torch.zeros(256 * 64, dtype=torch.int32, device=device), 0]
-    ring[1] = (ring[1] + 1) & 255
-    return ring[0].data_ptr() + ring[1] * 256
+    return region is None or len(getattr(region, '_streams', ())) < 3
 
 
 _pack_generation = 0   # bumped whenever a pack buffer is (re)allocated: invalidates cached batch tables
@@ -258,14 +240,13 @@ class _ConvBnActNode(Node):
         self.y = self.mask = None
         self.region = None
         self.fused_partial = None   # (partial, rows) when a consumer's dgrad epilogue did our BN-bwd reduce
-        self.fused_coef = None      # apply coefficients when that dgrad also finalized (tok_conv_dgrad_bn)
         self.coef = None
         self.pool = None            # tap indices of the fused 3x3/s2 max-pool: `out` is the POOLED map, z was never stored
         self.ypool = None           # raw conv output at the winning taps (pooled-domain BatchNorm-backward sums)
 
     def release(self):
         self.x = self.out = self.shortcut = None
-        self.y = self.pk = self.mask = self.fused_partial = self.fused_coef = self.coef = self.pool = self.ypool = None
+        self.y = self.pk = self.mask = self.fused_partial = self.coef = self.pool = self.ypool = None
         self.mean = self.rstd = self.scale = self.shift = None
 
     def wants_fused_bwd_stats(self) -> bool:
@@ -337,10 +318,8 @@ class _ConvBnActNode(Node):
             r = s = 1
         else:
             r, s = conv.weight.shape[2], conv.weight.shape[3]
-        side_ok = (WGRAD_SIDE_WHICH == 'all' or (r * s > 1 and WGRAD_SIDE_WHICH != '1x1') or
-                   (m < WGRAD_SIDE_MAX_ROWS and (r * s == 1 or WGRAD_SIDE_WHICH != '1x1')) or
-                   (r * s == 1 and _pointwise_wgrad_is_mfma_bound(conv.weight.shape[0], conv.weight.shape[1])))   # == launch_wgrad's side_ok
-        return bool(WGRAD_SIDE_STREAM and side_ok and _side_for_tag(self.stream_tag, self.region) and g.is_cuda and self.region is not None and not WGRAD_AFTER_DGRAD
+        return bool(WGRAD_SIDE_STREAM and _wgrad_side_ok(r, s, m, conv.weight.shape[0], conv.weight.shape[1])
+                    and _side_for_tag(self.stream_tag, self.region) and g.is_cuda and self.region is not None
                     and not torch.cuda.is_current_stream_capturing())
 
     def backward(self):
@@ -365,13 +344,8 @@ class _ConvBnActNode(Node):
             mask = self.mask if self.relu else None
             need_dy = w_need or x_need or bias_need
             if self.batch_stats:
-                if self.fused_coef is not None:
-                    # the dgrad that completed d(out) reduced AND finalized (tok_conv_dgrad_bn): dgamma / dbeta are
-                    # already in their slots, only the apply coefficients are needed here
-                    coef = self.fused_coef
-                else:
-                    self._finalize_bwd(lib, st, g, mask, m, kp, g_need, b_need)
-                    coef = self.coef
+                self._finalize_bwd(lib, st, g, mask, m, kp, g_need, b_need)
+                coef = self.coef
             else:
                 # eval-mode BN: y -> out is a fixed affine map: dy = scale * dz, dgamma/dbeta unsupported
                 if g_need or b_need:
@@ -381,7 +355,7 @@ class _ConvBnActNode(Node):
             need_dy = w_need or x_need or bias_need
             if need_dy or sc_need:
                 dy = torch.empty_like(self.y)
-                if LAUNCH_EVENTS and w_need and self.pool is None and self._wgrad_goes_side(g, m):
+                if w_need and self.pool is None and self._wgrad_goes_side(g, m):
                     # the weight gradient will be forked to the side stream behind THIS apply pass: the pass carries the
                     # completion event itself (no event-record packet on the main queue)
                     apply_event = self.region.raw_event()     # armed right in front of the launch that carries it (below)
@@ -416,7 +390,7 @@ class _ConvBnActNode(Node):
         if dy is None:
             return
         # the bias gradient (column sums of dy) rides the weight-gradient kernel where that serves the layer
-        bias_in_wgrad = bool(bias_need and w_need and BIAS_IN_WGRAD and lib.tok_conv_wgrad_bias_ok(d))
+        bias_in_wgrad = bool(bias_need and w_need and lib.tok_conv_wgrad_bias_ok(d))
         if bias_need and not bias_in_wgrad:
             bs, bm = param_grad_target(conv.bias)
             if m > 4096 and kp == conv.bias.shape[0]:
@@ -453,27 +427,22 @@ class _ConvBnActNode(Node):
                 return ws
             # LDS/MFMA-bound (3x3) and short-M weight gradients complement the HBM-bound main chain; the long-M pointwise ones
             # are HBM-bound themselves and only fight it for bandwidth
-            side_ok = (WGRAD_SIDE_WHICH == 'all' or (r * s > 1 and WGRAD_SIDE_WHICH != '1x1') or
-                       (m < WGRAD_SIDE_MAX_ROWS and (r * s == 1 or WGRAD_SIDE_WHICH != '1x1')) or
-                       (r * s == 1 and _pointwise_wgrad_is_mfma_bound(k, c)))
-            if WGRAD_SIDE_STREAM and side_ok and _side_for_tag(self.stream_tag, self.region) and g.is_cuda and self.region is not None \
-                    and (SIDE_IN_GRAPH or not torch.cuda.is_current_stream_capturing()):
+            if WGRAD_SIDE_STREAM and _wgrad_side_ok(r, s, m, k, c) and _side_for_tag(self.stream_tag, self.region) and g.is_cuda and self.region is not None \
+                    and not torch.cuda.is_current_stream_capturing():
                 # nothing on the main chain waits for dW: the weight gradient (LDS/MFMA-bound) runs on the side stream
                 # beside the HBM-bound BatchNorm passes and the dgrad of the units below; joined at the end of the region
                 with self.region.fork_side((x.data, dy), raw_event=apply_event):
                     self.region.keep_until_join(run_wgrad())
-            elif self.region is not None and g.is_cuda:
-                self.region.defer_wgrad(run_wgrad)     # (the closure keeps x and dy alive)
             else:
                 run_wgrad()
-        # a 3x3 weight gradient started BEFORE its unit's 3x3 data gradient runs beside it — two LDS/MFMA-bound kernels
-        # sharing the LDS pipes; started AFTER it, it runs beside the HBM-bound BatchNorm / pointwise kernels that follow
-        if w_need and not WGRAD_AFTER_DGRAD:
+        # the weight gradient is started BEFORE its unit's data gradient (started after it: 22.0 vs 21.1 ms/step, the later
+        # start costs more)
+        if w_need:
             launch_wgrad()
         if x_need:
             prod = x.node
             fuse = (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.wants_fused_bwd_stats()
-                    and prod.fused_partial is None and prod.fused_coef is None)
+                    and prod.fused_partial is None)
             # (a fused unit WITHOUT activation has no ReLU bits: its d(out) is dz itself and takes the plain path)
             mask_fuse = (isinstance(prod, _Unit3Node) and prod.relu and prod.mask is not None and is_last_contribution(x)
                          and prod.masked_partial is None)
@@ -512,48 +481,17 @@ class _ConvBnActNode(Node):
                 # unit that produced x (saves that unit a full pass over d(x) and y)
                 rows = lib.tok_conv_dgrad_stat_rows(d)
                 partial = torch.empty((2, rows, x.cp), dtype=F32, device=g.device)
-                pbn = prod.bn
-                pg, pb = pbn.weight.requires_grad, pbn.bias.requires_grad
-                gs, gm = param_grad_target(pbn.weight) if pg else (None, 0)
-                bs, bm = param_grad_target(pbn.bias) if pb else (None, 0)
-                simple = FUSE_BN_FINALIZE and gm != 2 and bm != 2 and not (pg and pb and gm != bm)
-                if simple:
-                    # ... and folds them: dgamma, dbeta, apply coefficients of the producer (last workgroup per
-                    # channel tile) — the producer's backward starts directly with its apply pass
-                    pm = prod.y.numel() // prod.y.shape[-1]
-                    coef = torch.empty((3, x.cp), dtype=F32, device=g.device)
-                    fb = _C.BnFused(_ticket_counters(g.device), pm, pbn.num_features, 1 if (gm == 1 or bm == 1) else 0,
-                                    0.0, 0.0, ptr(pbn.weight), None, None, None, None, ptr(prod.mean), ptr(prod.rstd),
-                                    None, None, ptr(gs), ptr(bs), ptr(coef))
-                    _C.check(lib.tok_conv_dgrad_bn(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, ptr(prod.y),
-                                                   ptr(prod.mask) if prod.relu else None, ptr(partial), fb, st),
-                             'tok_conv_dgrad_bn')
-                    prod.fused_coef = coef
-                    if pg:
-                        commit_param_grad(pbn.weight, gs, gm)
-                    if pb:
-                        commit_param_grad(pbn.bias, bs, bm)
-                else:
-                    _C.check(lib.tok_conv_dgrad_bnstats(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, ptr(prod.y),
-                                                        ptr(prod.mask) if prod.relu else None, ptr(partial), st),
-                             'tok_conv_dgrad_bnstats')
-                    prod.fused_partial = (partial, rows)
+                _C.check(lib.tok_conv_dgrad_bnstats(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, ptr(prod.y),
+                                                    ptr(prod.mask) if prod.relu else None, ptr(partial), st),
+                         'tok_conv_dgrad_bnstats')
+                prod.fused_partial = (partial, rows)
             else:
                 _C.check(lib.tok_conv_dgrad(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, st), 'tok_conv_dgrad')
-        if w_need and WGRAD_AFTER_DGRAD:
-            launch_wgrad()
-
 
 
 # ---- unit 3 of a bottleneck: 1x1 conv -> BatchNorm -> + shortcut -> ReLU without the pre-normalisation tensor ----------
 
 FUSE_UNIT3 = os.environ.get('TOK_FUSE_UNIT3', '1') != '0'
-# the side-stream fork / join of the weight gradients inside a hipGraph capture (cross-stream capture): experiment switch
-SIDE_IN_GRAPH = os.environ.get('TOK_SIDE_IN_GRAPH', '0') == '1'
-BIAS_IN_WGRAD = os.environ.get('TOK_BIAS_IN_WGRAD', '1') != '0'
-COLSUM_IN_ACT = os.environ.get('TOK_COLSUM_IN_ACT', '1') != '0'
-LAUNCH_EVENTS = os.environ.get('TOK_LAUNCH_EVENTS', '1') != '0'
-DGRAD2 = os.environ.get('TOK_DGRAD2', '1') != '0'
 # the fused unit trades ~27 tensor-units of HBM traffic for a handful of small launches (Gram matrix, two K x P x P products):
 # it pays where the 4P-channel maps are large (ResNet-50 at batch 256: layers 1-2 and, marginally, 3)
 UNIT3_MIN_ROWS = int(os.environ.get('TOK_UNIT3_MIN_ROWS', '100000'))   # measured: 0 -> 22.4, 40000 -> 22.0, 100000 -> 21.8, plain 23.2 ms/step
@@ -675,10 +613,10 @@ class _Unit3Node(Node):
         # 5. d(x) = dz wa + x wb + cvec  (+ the BatchNorm-backward sums of the unit that produced x)
         prod = x.node
         fuse = (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.wants_fused_bwd_stats()
-                and prod.fused_partial is None and prod.fused_coef is None)
+                and prod.fused_partial is None)
         tgt, acc = grad_target(x)
         dpp = _pointwise_desc(x, p)
-        if DGRAD2 and lib.tok_conv_dgrad2_ok(d, dpp):
+        if lib.tok_conv_dgrad2_ok(d, dpp):
             # both products in one launch of the ring kernel: d(x) is stored once
             part2 = None
             if fuse:
@@ -812,30 +750,16 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     if batch_stats:
         rows = lib.tok_conv_fwd_stat_rows(d)
         stats = torch.empty((2, rows, kp), dtype=F32, device=dev)
-    fused_fin = batch_stats and pk.bias is None and FUSE_BN_FINALIZE
     node = _ConvBnActNode()
-    if fused_fin:
-        # the conv launch also folds its statistics rows (last workgroup per channel tile): no finalize launch
-        if bn.momentum is None:
-            raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
-        scale, shift, mean, rstd = (torch.empty(kp, dtype=F32, device=dev) for _ in range(4))
-        track = bn.training and bn.track_running_stats and bn.running_mean is not None
-        fb = _C.BnFused(_ticket_counters(dev), m, bn.num_features, 0, float(bn.momentum), float(bn.eps), ptr(bn.weight),
-                        ptr(bn.bias), ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                        ptr(bn.num_batches_tracked) if track else None, ptr(mean), ptr(rstd), ptr(scale), ptr(shift),
-                        None, None, None)
-        _C.check(lib.tok_conv_fwd_bn(d, ptr(x4.data), ptr(pk.fwd), ptr(y), ptr(stats), fb, st), 'tok_conv_fwd_bn')
-    else:
-        _C.check(lib.tok_conv_fwd(d, ptr(x4.data), ptr(pk.fwd), ptr(pk.bias), ptr(y), ptr(stats), st), 'tok_conv_fwd')
+    _C.check(lib.tok_conv_fwd(d, ptr(x4.data), ptr(pk.fwd), ptr(pk.bias), ptr(y), ptr(stats), st), 'tok_conv_fwd')
 
     if bn is not None:
-        if not fused_fin:
-            # one allocation for the per-channel vectors (an allocator call costs the launch thread 2-3 us; HRNet-W48 makes 307
-            # of these units per step)
-            vec = torch.empty((4, kp), dtype=F32, device=dev)
-            scale, shift = vec[0], vec[1]
-            mean = rstd = None
-        if batch_stats and not fused_fin:
+        # one allocation for the per-channel vectors (an allocator call costs the launch thread 2-3 us; HRNet-W48 makes 307
+        # of these units per step)
+        vec = torch.empty((4, kp), dtype=F32, device=dev)
+        scale, shift = vec[0], vec[1]
+        mean = rstd = None
+        if batch_stats:
             if bn.momentum is None:
                 raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
             mean, rstd = vec[2], vec[3]
@@ -846,12 +770,12 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
                                          ptr(bn.num_batches_tracked) if track else None,
                                          float(bn.momentum), float(bn.eps), ptr(mean), ptr(rstd),
                                          ptr(scale), ptr(shift), st), 'tok_bn_finalize')
-        elif not batch_stats:
+        else:
             _C.check(lib.tok_bn_eval_coeffs(ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
                                             ptr(bn.running_var), float(bn.eps), kp, bn.num_features, ptr(scale), ptr(shift), st),
                      'tok_bn_eval_coeffs')
         mask = None
-        deferred = bool(defer_apply and not relu and shortcut is None and not pool and x.data.dim() == 4 and not fused_fin)
+        deferred = bool(defer_apply and not relu and shortcut is None and not pool and x.data.dim() == 4)
         if deferred:
             out_data = y
             cs_part = None
@@ -871,7 +795,7 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
                 mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=dev)
             # a 3x3 unit of a bottleneck feeds the fused residual unit, which wants colsum(z) of its input: the activation pass
             # has z in registers (saves that unit a stand-alone pass over z)
-            want_cs = (FUSE_UNIT3 and COLSUM_IN_ACT and r == 3 and relu and shortcut is None and m >= UNIT3_MIN_ROWS
+            want_cs = (FUSE_UNIT3 and r == 3 and relu and shortcut is None and m >= UNIT3_MIN_ROWS
                        and kp == k_real and kp <= 1024 and region.grad_mode and batch_stats)
             cs_part = None
             if want_cs:
@@ -1029,7 +953,7 @@ class _AvgPool2Node(Node):
 
 def avg_pool_2x2(region: Region, x: TTensor) -> TTensor:
     """AvgPool2d(2, stride 2, ceil_mode=True, count_include_pad=False) ([timm] downsample_avg)."""
-    await_ready(x)       # a projection shortcut on a branch stream (resnet.py, TOK_SHORTCUT_BRANCH=1) reads x here
+    await_ready(x)       # x may come from a branch stream
     n, h, w, c = x.shape
     y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=BF16, device=x.data.device)
     _C.check(_C.lib().tok_avgpool2x2_fwd(ptr(x.data), ptr(y), n, h, w, c, stream_ptr()), 'tok_avgpool2x2_fwd')
@@ -1154,11 +1078,8 @@ class _DwConvBnActNode(_ConvBnActNode):
         w_need, x_need = conv.weight.requires_grad, x.requires_grad
         mask = self.mask if self.relu else None
         if self.batch_stats:
-            if self.fused_coef is not None:
-                coef = self.fused_coef
-            else:
-                self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
-                coef = self.coef
+            self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
+            coef = self.coef
         else:
             if bn.weight.requires_grad or bn.bias.requires_grad:
                 raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')

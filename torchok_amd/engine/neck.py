@@ -33,7 +33,6 @@ from .core import (BF16, Region, TTensor, await_ready, commit_param_grad, grad_t
 
 F32 = torch.float32
 NECK_COMMUTE = os.environ.get('TOK_NECK_COMMUTE', '1') != '0'
-NECK_WGRAD_SIDE = os.environ.get('TOK_NECK_WGRAD_SIDE', '1') != '0'
 
 
 class _CommutedNeckNode(EF._ConvBnActNode):
@@ -57,11 +56,8 @@ class _CommutedNeckNode(EF._ConvBnActNode):
         w_need = conv.weight.requires_grad
         srcs: List[TTensor] = self.srcs
         mask = self.mask if self.relu else None
-        if self.fused_coef is not None:
-            coef = self.fused_coef
-        else:
-            self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
-            coef = self.coef
+        self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
+        coef = self.coef
         if not (w_need or any(t.requires_grad for t in srcs)):
             out.grad = None
             return
@@ -107,7 +103,7 @@ class _CommutedNeckNode(EF._ConvBnActNode):
             commit_param_grad(conv.weight, slot, mode)
             return keep
 
-        side = (NECK_WGRAD_SIDE and EF.WGRAD_SIDE_STREAM and EF._side_for_tag(self.stream_tag, self.region) and dy.is_cuda
+        side = (EF.WGRAD_SIDE_STREAM and EF._side_for_tag(self.stream_tag, self.region) and dy.is_cuda
                 and self.region is not None and not torch.cuda.is_current_stream_capturing())
         if side:
             with self.region.fork_side([t.data for t in srcs] + dys):

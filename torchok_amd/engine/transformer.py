@@ -25,7 +25,7 @@ from torch import nn
 from .. import _C
 from .core import (BF16, Node, Region, TTensor, await_mark, await_ready, commit_param_grad, donate_grad, grad_target,
                    pad8, param_grad_target, ptr, stream_ptr, written_mark)
-from .functional import BIAS_IN_WGRAD, _krsc, get_packs
+from .functional import _krsc, get_packs
 
 F32 = torch.float32
 
@@ -111,7 +111,7 @@ class _LinearNode(Node):
         # the column sums of g (bias gradients) come out of the weight-gradient kernel where it serves the layer
         # (plan facts of the geometry are cached: two library calls less per layer and step on the launch thread)
         plan = _linear_plan(lib, d)
-        bias_in_wgrad = bool(self.bias_sinks and w.requires_grad and BIAS_IN_WGRAD and plan[0])
+        bias_in_wgrad = bool(self.bias_sinks and w.requires_grad and plan[0])
         if self.bias_sinks and not bias_in_wgrad:
             def run_bias():
                 tmp = torch.empty(kp, dtype=F32, device=g.device)
@@ -157,26 +157,20 @@ class _LinearNode(Node):
                 return ws
             wgrad_fn = run_wgrad
 
-        def param_grads(event=None):
-            if bias_fn is not None:
-                if side:       # parameter gradients only: off the main chain, beside it (see functional.py)
-                    with self.region.fork_side((g,), event=event):
-                        self.region.keep_until_join(*bias_fn())
-                else:
-                    bias_fn()
-            if wgrad_fn is not None:
-                if side:
-                    with self.region.fork_side((x.data, g), event=event):       # dW beside the main chain (see functional.py)
-                        self.region.keep_until_join(wgrad_fn())
-                else:
-                    wgrad_fn()
-        # the data gradient is the main chain: with DGRAD_FIRST the host enqueues it before the side-stream work (fork, scratch
-        # allocation, weight-gradient + bias launches, hooks) — the side kernels still start where they used to (the fork event
-        # is recorded up front).  Measured on SwinV2-T B=256: the main queue idled 100-190 us per block behind that host work.
-        early = DGRAD_FIRST and side and x.requires_grad
-        ev = self.region.mark_side() if early else None
-        if not early:
-            param_grads()
+        # the parameter gradients are enqueued before the data gradient (the other order measured neutral: SwinV2-T 24.98 vs
+        # 24.97, DaViT-T 24.33 vs 24.20 ms/step)
+        if bias_fn is not None:
+            if side:       # parameter gradients only: off the main chain, beside it (see functional.py)
+                with self.region.fork_side((g,)):
+                    self.region.keep_until_join(*bias_fn())
+            else:
+                bias_fn()
+        if wgrad_fn is not None:
+            if side:
+                with self.region.fork_side((x.data, g)):       # dW beside the main chain (see functional.py)
+                    self.region.keep_until_join(wgrad_fn())
+            else:
+                wgrad_fn()
         if x.requires_grad and self.dx_done:
             pass            # fc1 of a fused Mlp: fc2's backward launch already sent this gradient on (tok_mlp_bwd_dx)
         elif x.requires_grad:
@@ -204,8 +198,6 @@ class _LinearNode(Node):
             else:
                 tgt, acc = grad_target(x)
                 _C.check(lib.tok_conv_dgrad(d, ptr(g), ptr(self.pk.dgrad), ptr(tgt), acc, st), 'tok_conv_dgrad')
-        if early:
-            param_grads(ev)
         self.out.grad = None
 
     def release(self):
@@ -218,7 +210,6 @@ class _LinearNode(Node):
 # wins: SwinV2-T 24.87 -> 24.59, DaViT-T 24.14 -> 23.95 ms/step, and 12 activation-sized tensor passes per block leave the
 # step's HBM traffic.  On by default; TOK_FUSE_ACT=0 restores the separate launches.
 FUSE_ACT = os.environ.get('TOK_FUSE_ACT', '1') == '1'
-DGRAD_FIRST = os.environ.get('TOK_DGRAD_FIRST', '0') == '1'   # measured neutral (SwinV2-T 24.98 vs 24.97, DaViT-T 24.33 vs 24.20 ms): off
 
 
 def linear_op(region: Region, x: TTensor, weight: nn.Parameter, bias_vec: Optional[torch.Tensor] = None,

@@ -24,10 +24,7 @@ from ...engine import resample as ER
 from ..base import BaseBackbone
 from .resnet import BasicBlock, Bottleneck
 
-_BRANCH0_FIRST = os.environ.get('TOK_HRNET_BRANCH0_FIRST', '0') == '1'     # A/B switch: the enqueue order of rounds 1-5
-_FUSE_STREAMS = os.environ.get('TOK_HRNET_FUSE_STREAMS', '3') != '0'       # A/B switch: fuse rows on the branch streams (forward)
-_FUSE_BWD_MAIN = os.environ.get('TOK_HRNET_FUSE_STREAMS', '3') != '2'      # =2: their backward on the branch streams too
-_FUSE_BWD_SRC = os.environ.get('TOK_HRNET_FUSE_STREAMS', '3') == '3'       # =3 (probe): path j -> i backward on stream j, the sum's on stream i
+_FUSE_STREAMS = os.environ.get('TOK_HRNET_FUSE_STREAMS', '1') != '0'       # fuse rows on the branch streams
 
 _BN_MOMENTUM = 0.1
 blocks_dict = {'BASIC': BasicBlock, 'BOTTLENECK': Bottleneck}
@@ -69,14 +66,13 @@ def _conv_bn(cin, cout, k, stride, pad, relu):
 
 # the last unit of a fuse path (Conv2d + BatchNorm2d, no activation) hands its RAW output + BatchNorm coefficients to the row's
 # summation kernel instead of running its own apply pass (round 6: by ablation those passes cost 1.3 ms of a 64.3-ms HRNet-W48
-# step; TOK_HRNET_DEFER_TERM_BN=0 restores them)
-_DEFER_TERM_BN = os.environ.get('TOK_HRNET_DEFER_TERM_BN', '1') != '0'
+# step)
 
 
 def _run_conv_bn(r, x, seq: nn.Sequential, defer_apply: bool = False):
     """One `Conv2d, BatchNorm2d[, ReLU]` Sequential (transition / fuse building block) as one engine unit."""
     relu = len(seq) > 2 and isinstance(seq[2], nn.ReLU)
-    return EF.conv_bn_act(r, x, seq[0], seq[1], relu=relu, defer_apply=defer_apply and not relu and _DEFER_TERM_BN)
+    return EF.conv_bn_act(r, x, seq[0], seq[1], relu=relu, defer_apply=defer_apply and not relu)
 
 
 class HighResolutionModule(nn.Module):
@@ -142,17 +138,16 @@ class HighResolutionModule(nn.Module):
         # tiles, long reductions: they cannot fill the GPU alone) each on its own branch stream beside it.
         # LOW-RESOLUTION BRANCHES FIRST (round 6): entering a branch stream records its fork event on the main stream at that
         # moment — recorded after branch 0's two dozen launches it made branches 1..3 START when branch 0 had FINISHED (per-queue
-        # dump of a step: the forward of every module ran [branch 0] then [branches 1-3]; TOK_HRNET_BRANCH0_FIRST=1 restores it)
-        order = range(self.num_branches) if _BRANCH0_FIRST else reversed(range(self.num_branches))
+        # dump of a step: the forward of every module ran [branch 0] then [branches 1-3])
         outs = [None] * self.num_branches
         nodes = getattr(r, 'nodes', None)
         start, spans = (len(nodes) if nodes is not None else 0), {}
-        for i in order:
+        for i in reversed(range(self.num_branches)):
             a = len(nodes) if nodes is not None else 0
             with r.branch(i) as br:
                 outs[i] = br.publish(self.branches[i](x[i]))
             spans[i] = (a, len(nodes) if nodes is not None else 0)
-        if nodes is not None and not _BRANCH0_FIRST:
+        if nodes is not None:
             # ... but the TAPE keeps the order branch 0, 1, 2, 3 (the branches are independent blocks of it): the backward walks
             # it in reverse and starts with the low-resolution branches, as before — enqueued the other way round it was 2.5 ms
             # slower (same box: forward 23.9 vs 24.2 ms, backward 48.6 vs 46.1)
@@ -176,7 +171,7 @@ class HighResolutionModule(nn.Module):
                         terms.append((x[j], 0))
                     elif j > i:      # 1x1 conv + BN at the low resolution; the nearest upsample is folded into the sum
                         p0 = len(nodes) if nodes is not None else 0
-                        terms.append((EF.conv_bn_act(r, x[j], row[j][0], row[j][1], relu=False, defer_apply=_DEFER_TERM_BN), j - i))
+                        terms.append((EF.conv_bn_act(r, x[j], row[j][0], row[j][1], relu=False, defer_apply=True), j - i))
                         path_spans.append((p0, len(nodes) if nodes is not None else 0, j))
                     else:
                         p0 = len(nodes) if nodes is not None else 0
@@ -189,19 +184,13 @@ class HighResolutionModule(nn.Module):
                 terms.sort(key=lambda ts: ts[1])
                 fused[i] = br.publish(ER.fuse_sum_relu(r, terms, relu=True))
             spans[i] = (a, len(nodes) if nodes is not None else 0)
-        if nodes is not None and _FUSE_STREAMS and _FUSE_BWD_SRC:
-            # probe: the backward of path j -> i on the SOURCE branch's stream j (every write into d(x_j) then comes from one stream)
+        if nodes is not None and _FUSE_STREAMS:
+            # the backward of path j -> i runs on the SOURCE branch's stream j (every write into d(x_j) then comes from one
+            # stream), the sum's on stream i
             for p0, p1, j in path_spans:
                 for n in nodes[p0:p1]:
                     n.stream_tag = j
-        if nodes is not None and _FUSE_STREAMS:
             nodes[start:] = [n for i in rows for n in nodes[spans[i][0]:spans[i][1]]]
-            if _FUSE_BWD_MAIN and not _FUSE_BWD_SRC:
-                # ... and the BACKWARD of the fuse rows stays on the main stream: their gradient contributions fan into the
-                # branches' outputs from every row, and ordering those accumulations across four queues cost more events and
-                # waits than the rows' concurrency returned
-                for n in nodes[start:]:
-                    n.stream_tag = 0
         return fused
 
 

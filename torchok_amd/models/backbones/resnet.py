@@ -62,7 +62,7 @@ class BasicBlock(nn.Module):
         return EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True, shortcut=shortcut)
 
     def _shortcut(self, r, x):
-        return _shortcut_branch(r, x, self.downsample)
+        return _shortcut(r, x, self.downsample)
 
 
 class Bottleneck(nn.Module):
@@ -94,37 +94,22 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         r = engine.current_region()
-        late = SHORTCUT_LATE and self.downsample is not None and not SHORTCUT_BRANCH
-        shortcut = None if late else _shortcut_branch(r, x, self.downsample)
         y = EF.conv_bn_act(r, x, self.conv1, self.bn1, relu=True)
         y = EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True)
-        if late:
-            shortcut = _shortcut_branch(r, x, self.downsample)
+        # the projection is recorded LAST before the unit that adds it: in backward its (strided) data gradient then opens the
+        # gradient of the block input and conv1's dense 1x1 data gradient closes it — the accumulate + ReLU-mask pass over the
+        # whole tensor runs in the ring kernel's staged epilogue instead of the parity-class kernel's read-modify-write of
+        # untouched pixels
+        shortcut = _shortcut(r, x, self.downsample)
         return EF.conv_bn_act(r, y, self.conv3, self.bn3, relu=True, shortcut=shortcut)
 
 
-# measured on ResNet-50 (B=256): no gain (23.8 vs 23.7 ms/step) — the main-stream kernels already fill the GPU; the
-# mechanism pays off where the main chain is under-filled (HRNet's parallel branches)
-import os as _os
-SHORTCUT_BRANCH = _os.environ.get('TOK_SHORTCUT_BRANCH', '0') == '1'
-# The projection recorded LAST before the unit that adds it: in backward its (strided) data gradient then opens the
-# gradient of the block input and conv1's dense 1x1 data gradient closes it — the accumulate + ReLU-mask pass over the whole
-# tensor runs in the ring kernel's staged epilogue instead of the parity-class kernel's read-modify-write of untouched pixels
-SHORTCUT_LATE = _os.environ.get('TOK_SHORTCUT_LATE', '1') == '1'
-
-
-def _shortcut_branch(r, x, downsample):
-    """The projection shortcut does not depend on the conv1..conv3 chain: it is recorded first, on branch stream 1, and
-    runs beside the chain in forward and in backward; the unit that adds it waits for it."""
+def _shortcut(r, x, downsample):
+    """The block input, or its projection: an ``nn.Sequential(conv, bn)`` ([timm] downsample_conv, hrnet.py) or a ConvBnAct
+    brick without activation (necks/classification/hrnet.py:62-69).  On the main stream: on a branch stream of its own it
+    measured no gain on ResNet-50 B=256 (23.8 vs 23.7 ms/step), the main-stream kernels already fill the GPU."""
     if downsample is None:
         return x
-    with r.branch(1 if SHORTCUT_BRANCH else 0) as br:
-        return br.publish(_run_downsample(r, x, downsample))
-
-
-def _run_downsample(r, x, downsample):
-    """Shortcut projection: an ``nn.Sequential(conv, bn)`` ([timm] downsample_conv, hrnet.py) or a ConvBnAct brick
-    without activation (necks/classification/hrnet.py:62-69)."""
     if hasattr(downsample, 'run'):
         return downsample.run(r, x)
     if len(downsample) == 3:       # [timm] downsample_avg: (AvgPool2d | Identity, 1x1 conv, norm)
