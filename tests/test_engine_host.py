@@ -328,3 +328,232 @@ def test_strided_projection_runs_pointwise_and_parks_its_gradient(fake_backend, 
     g1 = dict(task.named_parameters())
     for n, p in task2.named_parameters():
         assert rel_err(p.grad, g1[n].grad) < 1e-6, n
+
+
+# ---- parameter gradients of every unit kind in every state of `.grad` -----------------------------------------------------
+
+def _bf(shape, seed, grad=True):
+    g = torch.Generator().manual_seed(seed)
+    t = torch.randn(*shape, generator=g).to(torch.bfloat16)
+    if len(shape) == 4:
+        t = t.contiguous(memory_format=torch.channels_last)
+    return t.requires_grad_(grad)
+
+
+def _unit(params, lead, forward, calls=()):
+    """(parameters by name, the one that alone keeps / gets a gradient in the mixed states, one forward + backward)."""
+    gout = []
+
+    def step(fake):
+        from torchok_amd.engine.core import Region
+        fake.calls.clear()
+        r = Region()
+        y = r.output(forward(r))
+        if not gout:
+            gout.append(torch.randn(y.shape, generator=torch.Generator().manual_seed(77)).to(torch.bfloat16))
+        y.backward(gout[0])
+        for c in calls:
+            assert c in fake.calls, c
+    return params, lead, step
+
+
+def _conv_unit(conv, bn, x, calls=(), **kw):
+    from torchok_amd.engine import functional as EF
+    params = dict(conv.named_parameters(prefix='conv'))
+    if bn is not None:
+        params = {**dict(bn.named_parameters(prefix='bn')), **params}
+    pad = 4 if x.shape[1] <= 4 else 8
+    return _unit(params, next(iter(params)), lambda r: EF.conv_bn_act(r, r.input(x, c_pad_to=pad), conv, bn, **kw), calls)
+
+
+def _u_conv_bn_relu():
+    return _conv_unit(torch.nn.Conv2d(8, 16, 3, padding=1, bias=False), torch.nn.BatchNorm2d(16), _bf((2, 8, 6, 6), 1), relu=True)
+
+
+def _u_conv_bias_short():
+    return _conv_unit(torch.nn.Conv2d(8, 16, 3, padding=1), None, _bf((2, 8, 6, 6), 2))
+
+
+def _u_conv_bias_tall():          # more than 4096 output rows: partial rows, then the fold
+    return _conv_unit(torch.nn.Conv2d(8, 16, 3, padding=1), None, _bf((2, 8, 48, 48), 3), calls=['conv_wgrad'])
+
+
+def _u_conv_bias_pointwise():     # the bias gradient rides the weight-gradient launch
+    return _conv_unit(torch.nn.Conv2d(8, 16, 1), None, _bf((2, 8, 6, 6), 4), calls=['wgrad_bias'])
+
+
+def _u_unit3():
+    from torchok_amd.engine import functional as EF
+    conv, bn = torch.nn.Conv2d(8, 32, 1, bias=False), torch.nn.BatchNorm2d(32)
+    x, sc = _bf((2, 8, 6, 6), 5), _bf((2, 32, 6, 6), 6)
+    params = {**dict(bn.named_parameters(prefix='bn')), **dict(conv.named_parameters(prefix='conv'))}
+    return _unit(params, 'bn.weight',
+                 lambda r: EF.conv_bn_act(r, r.input(x), conv, bn, relu=True, shortcut=r.input(sc)), ['bn3_bwd_prepare'])
+
+
+def _u_stem_pool():
+    return _conv_unit(torch.nn.Conv2d(3, 16, 7, stride=2, padding=3, bias=False), torch.nn.BatchNorm2d(16),
+                      _bf((2, 3, 32, 32), 7, grad=False), relu=True, pool=True)
+
+
+def _u_depthwise():
+    from torchok_amd.engine import functional as EF
+    conv, bn = torch.nn.Conv2d(16, 16, 3, padding=1, groups=16, bias=False), torch.nn.BatchNorm2d(16)
+    x = _bf((2, 16, 6, 6), 8)
+    params = {**dict(bn.named_parameters(prefix='bn')), **dict(conv.named_parameters(prefix='conv'))}
+    return _unit(params, 'bn.weight', lambda r: EF.dwconv_bn_act(r, r.input(x), conv, bn))
+
+
+def _u_squeeze_excite():
+    from torchok_amd.engine import functional as EF
+    se = torch.nn.Module()
+    se.conv_reduce, se.conv_expand = torch.nn.Conv2d(16, 8, 1), torch.nn.Conv2d(8, 16, 1)
+    x = _bf((2, 16, 6, 6), 9)
+    return _unit(dict(se.named_parameters()), 'conv_reduce.weight', lambda r: EF.squeeze_excite(r, r.input(x), se))
+
+
+def _u_linear_head():
+    from torchok_amd.engine import functional as EF
+    fc, x = torch.nn.Linear(16, 10), _bf((4, 16), 10)
+    return _unit(dict(fc.named_parameters()), 'weight', lambda r: EF.linear(r, r.input(x), fc))
+
+
+def _u_token_linear():
+    from torchok_amd.engine import transformer as ET
+    fc, x = torch.nn.Linear(16, 24), _bf((6, 16), 11)
+    return _unit(dict(fc.named_parameters()), 'weight', lambda r: ET.linear_module(r, r.input(x), fc), ['wgrad_bias'])
+
+
+def _qkv(weight_grad):
+    from torchok_amd.engine import transformer as ET
+    torch.manual_seed(12)
+    w = torch.nn.Parameter(torch.randn(24, 16) * 0.1, requires_grad=weight_grad)
+    qb, vb = torch.nn.Parameter(torch.randn(8)), torch.nn.Parameter(torch.randn(8))
+    x = _bf((6, 16), 12)
+    params = {'q_bias': qb, 'v_bias': vb}
+    if weight_grad:
+        params['weight'] = w
+
+    def forward(r):
+        bias = torch.cat((qb.detach(), torch.zeros(8), vb.detach()))
+        return ET.linear_op(r, r.input(x), w, bias, [(qb, 0), (vb, 16)])
+    return _unit(params, 'q_bias', forward, ['wgrad_bias'] if weight_grad else [])
+
+
+def _u_token_linear_qkv():        # several bias sinks: the sums land in a temporary and are scattered
+    return _qkv(True)
+
+
+def _u_token_linear_frozen_weight():      # no weight-gradient launch to ride: column sums on their own
+    return _qkv(False)
+
+
+def _u_fused_mlp():
+    from torchok_amd.models.backbones.swin import Mlp
+    torch.manual_seed(13)
+    m, x = Mlp(96, 384), _bf((40, 96), 13)
+    return _unit(dict(m.named_parameters()), 'fc1.weight', lambda r: m.run(r, r.input(x)), ['mlp_fwd', 'mlp_bwd_dx'])
+
+
+def _u_layer_norm():
+    from torchok_amd.engine import transformer as ET
+    ln, x = torch.nn.LayerNorm(16), _bf((6, 16), 14)
+    return _unit(dict(ln.named_parameters()), 'weight', lambda r: ET.layer_norm(r, r.input(x), ln))
+
+
+def _u_patch_embed():
+    from torchok_amd.engine import transformer as ET
+    conv, x = torch.nn.Conv2d(3, 16, 4, stride=4), _bf((2, 3, 8, 8), 15, grad=False)
+    return _unit(dict(conv.named_parameters()), 'weight', lambda r: ET.patch_embed(r, r.input(x, c_pad_to=4), conv)[0])
+
+
+def _u_vit_embed():
+    from torchok_amd.engine import transformer as ET
+    torch.manual_seed(16)
+    pos, cls = torch.nn.Parameter(torch.randn(1, 5, 16)), torch.nn.Parameter(torch.randn(1, 1, 16))
+    x = _bf((8, 16), 16)
+    return _unit({'pos_embed': pos, 'cls_token': cls}, 'pos_embed', lambda r: ET.vit_embed(r, r.input(x), 2, pos, cls))
+
+
+def _u_cosine_linear():
+    from torchok_amd.engine import metric as EM
+    torch.manual_seed(17)
+    w, x = torch.nn.Parameter(torch.randn(10, 16)), _bf((4, 16), 17)
+    return _unit({'weight': w}, 'weight', lambda r: EM.cosine_linear(r, r.input(x), w))
+
+
+def _u_commuted_neck():
+    from torchok_amd.engine import neck as EN
+    conv, bn = torch.nn.Conv2d(24, 16, 1, bias=False), torch.nn.BatchNorm2d(16)
+    x0, x1 = _bf((2, 8, 8, 8), 18), _bf((2, 16, 4, 4), 19)
+    params = {**dict(bn.named_parameters(prefix='bn')), **dict(conv.named_parameters(prefix='conv'))}
+    return _unit(params, 'bn.weight',
+                 lambda r: EN.upsample_concat_conv_bn_relu(r, [r.input(x0), r.input(x1)], (8, 8), conv, bn),
+                 ['bilinear_sum_stats'])
+
+
+_PARAM_GRAD_UNITS = {f.__name__[3:]: f for f in (
+    _u_conv_bn_relu, _u_conv_bias_short, _u_conv_bias_tall, _u_conv_bias_pointwise, _u_unit3, _u_stem_pool, _u_depthwise,
+    _u_squeeze_excite, _u_linear_head, _u_token_linear, _u_token_linear_qkv, _u_token_linear_frozen_weight, _u_fused_mlp,
+    _u_layer_norm, _u_patch_embed, _u_vit_embed, _u_cosine_linear, _u_commuted_neck)}
+
+
+@pytest.fixture
+def full_fake_backend():
+    """The stand-in with the entry points the ViT and MnasNet host tests add to it (patch gather, token assembly, depthwise
+    convolution, squeeze-excite)."""
+    import fake_backend as fb
+    from test_mnasnet import MnasFake
+    from test_vit import VitFake
+    token = fb.install(type('FullFake', (VitFake, MnasFake), {})())
+    yield token[0]
+    fb.uninstall(token)
+
+
+@pytest.mark.parametrize('state', ['fresh', 'accumulate', 'foreign', 'mixed_foreign', 'mixed_accumulate'])
+@pytest.mark.parametrize('kind', sorted(_PARAM_GRAD_UNITS))
+def test_param_grads_in_every_state_of_grad(full_fake_backend, monkeypatch, kind, state):
+    """Every unit that produces parameter gradients, in every state `.grad` can be in when its backward runs: empty (the
+    kernel writes the gradient slot), the slot itself from an earlier backward (the kernel accumulates), a tensor the user put
+    there (the gradient is added to THAT tensor, which stays the same object), and the two mixed states in which only one
+    parameter of the unit (the BatchNorm / LayerNorm weight where there is one) holds a foreign tensor or an earlier gradient.
+    On the stand-in the results are exact: g, g + g, foreign + g.  Every `param_grad_hooks` callback fires once per parameter
+    and backward (the DDP bucket launch hangs on it)."""
+    from torchok_amd.engine import core as EC
+    from torchok_amd.engine import functional as EF
+    monkeypatch.setattr(EF, 'UNIT3_MIN_ROWS', 0)
+    params, lead, step = _PARAM_GRAD_UNITS[kind]()
+    assert lead in params and all(p.requires_grad for p in params.values())
+    fired = []
+
+    def hook(p):
+        fired.append(id(p))
+    EC.param_grad_hooks.append(hook)
+    try:
+        def backward():
+            fired.clear()
+            step(full_fake_backend)
+            assert sorted(fired) == sorted(id(p) for p in params.values()), 'one hook call per parameter and backward'
+        backward()
+        assert all(p.grad is not None and p.grad.shape == p.shape and p.grad.dtype == torch.float32 for p in params.values())
+        g0 = {n: p.grad.detach().clone() for n, p in params.items()}
+        assert all(torch.isfinite(g).all() and g.abs().sum() > 0 for g in g0.values())
+        want, foreign = dict(g0), {}
+        if state == 'fresh':
+            return
+        for i, (n, p) in enumerate(params.items()):
+            if state == 'accumulate' or (state == 'mixed_accumulate' and n == lead):
+                want[n] = g0[n] + g0[n]
+            elif state == 'foreign' or (state == 'mixed_foreign' and n == lead):
+                f = torch.randn(g0[n].shape, generator=torch.Generator().manual_seed(100 + i))
+                want[n] = f + g0[n]
+                foreign[n] = p.grad = f
+            else:
+                p.grad = None
+        backward()
+        for n, p in params.items():
+            assert torch.equal(p.grad, want[n]), n
+            if n in foreign:
+                assert p.grad is foreign[n], n
+    finally:
+        EC.param_grad_hooks.remove(hook)

@@ -97,7 +97,7 @@ class ParamArena:
         return [p.data_ptr() for p in self.params] == self._want_ptrs
 
     def grad_flags(self):
-        """Per parameter: 0 no gradient, 1 the gradient IS the registered slot (what engine.core.commit_param_grad leaves
+        """Per parameter: 0 no gradient, 1 the gradient IS the registered slot (what engine.paramgrad.commit leaves
         behind: the common case of a training step, recognised without a data_ptr() call), 2 some other tensor."""
         return [0 if p.grad is None else (1 if p.grad is g else 2) for p, g in zip(self.params, self.gviews)]
 

@@ -316,29 +316,9 @@ def grad_slot(p: torch.nn.Parameter) -> torch.Tensor:
     return slot
 
 
-def param_grad_target(p: torch.nn.Parameter):
-    """(slot, accumulate): where the kernel writes dParam.  Call commit_param_grad afterwards."""
-    slot = grad_slot(p)
-    if p.grad is None:
-        return slot, 0
-    if p.grad.data_ptr() == slot.data_ptr():
-        return slot, 1
-    # a foreign .grad tensor (set by user code): compute into the slot, add afterwards
-    return slot, 2
-
-
-# callbacks fired when a parameter's gradient for this backward pass has been enqueued
-# (dist/ddp.py uses them to launch a bucket's all-reduce as soon as its last gradient exists)
+# callbacks fired when a parameter's gradient for this backward pass has been enqueued (paramgrad.commit; dist/ddp.py uses
+# them to launch a bucket's all-reduce as soon as its last gradient exists)
 param_grad_hooks = []
-
-
-def commit_param_grad(p: torch.nn.Parameter, slot: torch.Tensor, mode: int):
-    if mode == 0:
-        p.grad = slot
-    elif mode == 2:
-        p.grad.add_(slot)
-    for h in param_grad_hooks:
-        h(p)
 
 
 # ---- regions -----------------------------------------------------------------------------------

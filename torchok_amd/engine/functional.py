@@ -21,15 +21,10 @@ from torch import nn
 
 from .. import _C
 from .core import _ms as _core_ms
-from .core import (BF16, Node, Region, TTensor, await_ready, commit_param_grad, donate_grad, grad_target,
-                   is_last_contribution, pad8, param_grad_target, ptr, stream_ptr)
+from . import paramgrad as PG
+from .core import BF16, Node, Region, TTensor, await_ready, donate_grad, grad_target, is_last_contribution, pad8, ptr, stream_ptr
 
 F32 = torch.float32
-
-
-def core_hooks():
-    from . import core
-    return core.param_grad_hooks
 
 
 # ---- packed bf16 operands of the fp32 master weights ------------------------------------------------
@@ -240,13 +235,12 @@ class _ConvBnActNode(Node):
         self.y = self.mask = None
         self.region = None
         self.fused_partial = None   # (partial, rows) when a consumer's dgrad epilogue did our BN-bwd reduce
-        self.coef = None
         self.pool = None            # tap indices of the fused 3x3/s2 max-pool: `out` is the POOLED map, z was never stored
         self.ypool = None           # raw conv output at the winning taps (pooled-domain BatchNorm-backward sums)
 
     def release(self):
         self.x = self.out = self.shortcut = None
-        self.y = self.pk = self.mask = self.fused_partial = self.coef = self.pool = self.ypool = None
+        self.y = self.pk = self.mask = self.fused_partial = self.pool = self.ypool = None
         self.mean = self.rstd = self.scale = self.shift = None
 
     def wants_fused_bwd_stats(self) -> bool:
@@ -254,7 +248,7 @@ class _ConvBnActNode(Node):
         return self.bn is not None and self.batch_stats and (not self.relu or self.mask is not None) and self.pool is None
 
     def _finalize_bwd(self, lib, st, g, mask, m, kp, g_need, b_need):
-        """sum(dz), sum(dz*xhat) -> dgamma, dbeta, apply coefficients (stand-alone reduce / finalize launches)."""
+        """sum(dz), sum(dz*xhat) -> dgamma, dbeta; returns the apply coefficients (stand-alone reduce / finalize launches)."""
         bn = self.bn
         dzy = 0
         if self.fused_partial is not None:
@@ -282,45 +276,11 @@ class _ConvBnActNode(Node):
                                                ptr(self.mean), ptr(self.rstd), int(self.relu), m, kp, ptr(partial), st),
                          'tok_bn_bwd_reduce')
         coef = torch.empty((3, kp), dtype=F32, device=g.device)
-        gs, gm = param_grad_target(bn.weight) if g_need else (None, 0)
-        bs, bm = param_grad_target(bn.bias) if b_need else (None, 0)
-        if gm == 2 or bm == 2 or (gm != bm and g_need and b_need):
-            # rare mixed state: run the accumulate-free form and fix up on the host side
-            gacc = torch.empty_like(gs) if g_need else None
-            bacc = torch.empty_like(bs) if b_need else None
-            _C.check(lib.tok_bn_bwd_finalize(ptr(partial), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(self.mean),
-                                             ptr(self.rstd), ptr(gacc), ptr(bacc), ptr(coef), 0, dzy, st),
-                     'tok_bn_bwd_finalize')
-            for p_, acc_ in ((bn.weight, gacc), (bn.bias, bacc)):
-                if acc_ is not None:
-                    if p_.grad is None:
-                        p_.grad = acc_
-                    else:
-                        p_.grad.add_(acc_)
-                    for h_ in core_hooks():
-                        h_(p_)
-        else:
-            def commit():
-                if g_need:
-                    commit_param_grad(bn.weight, gs, gm)
-                if b_need:
-                    commit_param_grad(bn.bias, bs, bm)
-            _C.check(lib.tok_bn_bwd_finalize(ptr(partial), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(self.mean),
-                                             ptr(self.rstd), ptr(gs), ptr(bs), ptr(coef),
-                                             1 if (gm == 1 or bm == 1) else 0, dzy, st), 'tok_bn_bwd_finalize')
-            commit()
-        self.coef = coef
-        return None
-
-    def _wgrad_goes_side(self, g, m) -> bool:
-        conv = self.conv
-        if conv.weight.dim() != 4:
-            r = s = 1
-        else:
-            r, s = conv.weight.shape[2], conv.weight.shape[3]
-        return bool(WGRAD_SIDE_STREAM and _wgrad_side_ok(r, s, m, conv.weight.shape[0], conv.weight.shape[1])
-                    and _side_for_tag(self.stream_tag, self.region) and g.is_cuda and self.region is not None
-                    and not torch.cuda.is_current_stream_capturing())
+        gbuf, bbuf, acc, finish = PG.pair_sinks(bn.weight if g_need else None, bn.bias if b_need else None)
+        _C.check(lib.tok_bn_bwd_finalize(ptr(partial), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(self.mean),
+                                         ptr(self.rstd), ptr(gbuf), ptr(bbuf), ptr(coef), acc, dzy, st), 'tok_bn_bwd_finalize')
+        finish()
+        return coef
 
     def backward(self):
         lib, st = _C.lib(), stream_ptr()
@@ -336,6 +296,8 @@ class _ConvBnActNode(Node):
         x_need = x.requires_grad
         bias_need = conv.bias is not None and conv.bias.requires_grad
         sc: Optional[TTensor] = self.shortcut
+        # decided ONCE: the BatchNorm apply launch carries the completion event iff the weight gradient forks behind it
+        side = w_need and PG.goes_side(self, g, PG.CONV, m)
 
         if bn is not None:
             g_need = bn.weight.requires_grad
@@ -344,18 +306,16 @@ class _ConvBnActNode(Node):
             mask = self.mask if self.relu else None
             need_dy = w_need or x_need or bias_need
             if self.batch_stats:
-                self._finalize_bwd(lib, st, g, mask, m, kp, g_need, b_need)
-                coef = self.coef
+                coef = self._finalize_bwd(lib, st, g, mask, m, kp, g_need, b_need)
             else:
                 # eval-mode BN: y -> out is a fixed affine map: dy = scale * dz, dgamma/dbeta unsupported
                 if g_need or b_need:
                     raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')
                 coef = torch.zeros((3, kp), dtype=F32, device=g.device)
                 coef[0] = self.scale
-            need_dy = w_need or x_need or bias_need
             if need_dy or sc_need:
                 dy = torch.empty_like(self.y)
-                if w_need and self.pool is None and self._wgrad_goes_side(g, m):
+                if side and self.pool is None:
                     # the weight gradient will be forked to the side stream behind THIS apply pass: the pass carries the
                     # completion event itself (no event-record packet on the main queue)
                     apply_event = self.region.raw_event()     # armed right in front of the launch that carries it (below)
@@ -390,55 +350,20 @@ class _ConvBnActNode(Node):
         if dy is None:
             return
         # the bias gradient (column sums of dy) rides the weight-gradient kernel where that serves the layer
-        bias_in_wgrad = bool(bias_need and w_need and lib.tok_conv_wgrad_bias_ok(d))
+        bias_in_wgrad = bool(bias_need and w_need and PG.wgrad_plan(d)[0])
         if bias_need and not bias_in_wgrad:
-            bs, bm = param_grad_target(conv.bias)
-            if m > 4096 and kp == conv.bias.shape[0]:
-                # tall dy (a conv / token GEMM bias): coalesced row-chunk partials, then a fixed-order fold
-                nrows = lib.tok_colsum_partial_rows(m, kp)
-                part = torch.empty((nrows, kp), dtype=F32, device=g.device)
-                _C.check(lib.tok_colsum_partial(ptr(dy), m, kp, ptr(part), st), 'tok_colsum_partial')
-                _C.check(lib.tok_colsum_f32(ptr(part), nrows, kp, ptr(bs), 1 if bm == 1 else 0, st), 'tok_colsum_f32')
-            else:
-                _C.check(lib.tok_colsum(ptr(dy), m, kp, conv.bias.shape[0], ptr(bs), 1 if bm == 1 else 0, st),
-                         'tok_colsum')
-            commit_param_grad(conv.bias, bs, bm)
-        def launch_wgrad():
-            k, r, s, c = _krsc(conv.weight)
-            ws_bytes = lib.tok_conv_wgrad_bias_ws_bytes(d) if bias_in_wgrad else lib.tok_conv_wgrad_ws_bytes(d)
-
-            def run_wgrad():
-                ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-                slot, mode = param_grad_target(conv.weight)
-                if bias_in_wgrad:
-                    bslot, bmode = param_grad_target(conv.bias)
-                    if bmode == 2:     # foreign .grad tensor on the bias: compute into the slot, commit adds it
-                        bacc = 0
-                    else:
-                        bacc = 1 if bmode == 1 else 0
-                    _C.check(lib.tok_conv_wgrad_bias(d, ptr(x.data), ptr(dy), ptr(slot), k, c, ptr(ws), ws_bytes,
-                                                     1 if mode == 1 else 0, ptr(bslot), bacc, stream_ptr()),
-                             'tok_conv_wgrad_bias')
-                    commit_param_grad(conv.bias, bslot, bmode)
-                else:
-                    _C.check(lib.tok_conv_wgrad(d, ptr(x.data), ptr(dy), ptr(slot), k, c, ptr(ws), ws_bytes,
-                                                1 if mode == 1 else 0, stream_ptr()), 'tok_conv_wgrad')
-                commit_param_grad(conv.weight, slot, mode)
-                return ws
-            # LDS/MFMA-bound (3x3) and short-M weight gradients complement the HBM-bound main chain; the long-M pointwise ones
-            # are HBM-bound themselves and only fight it for bandwidth
-            if WGRAD_SIDE_STREAM and _wgrad_side_ok(r, s, m, k, c) and _side_for_tag(self.stream_tag, self.region) and g.is_cuda and self.region is not None \
-                    and not torch.cuda.is_current_stream_capturing():
-                # nothing on the main chain waits for dW: the weight gradient (LDS/MFMA-bound) runs on the side stream
-                # beside the HBM-bound BatchNorm passes and the dgrad of the units below; joined at the end of the region
-                with self.region.fork_side((x.data, dy), raw_event=apply_event):
-                    self.region.keep_until_join(run_wgrad())
-            else:
-                run_wgrad()
+            bs, bacc = PG.sink(conv.bias)
+            # tall dy (a conv / token GEMM bias): coalesced row-chunk partials, then a fixed-order fold
+            PG.colsum(dy, m, kp, bs, bacc, two_pass=m > 4096 and kp == conv.bias.shape[0], n_real=conv.bias.shape[0])
+            PG.commit(conv.bias, bs, bacc)
         # the weight gradient is started BEFORE its unit's data gradient (started after it: 22.0 vs 21.1 ms/step, the later
-        # start costs more)
+        # start costs more).  Nothing on the main chain waits for dW: the LDS/MFMA-bound (3x3) and short-M ones run on the side
+        # stream beside the HBM-bound BatchNorm passes and the dgrad of the units below, joined at the end of the region; the
+        # long-M pointwise ones are HBM-bound themselves and would only fight the chain for bandwidth (PG.CONV)
         if w_need:
-            launch_wgrad()
+            k, _, _, c = _krsc(conv.weight)
+            PG.run_beside(self, side, (x.data, dy), raw_event=apply_event, fn=lambda: PG.weight_grad(
+                d, x.data, dy, k, c, weight=conv.weight, bias=conv.bias if bias_in_wgrad else None)[1:])
         if x_need:
             prod = x.node
             fuse = (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.wants_fused_bwd_stats()
@@ -502,26 +427,9 @@ def _pointwise_desc(x: TTensor, k: int) -> _C.ConvDesc:
     return _C.ConvDesc(n, h, w, cp, k, 1, 1, h, w, 1, 0, 1)
 
 
-def _colsum_f32(lib, st, t: torch.Tensor, m: int, c: int) -> torch.Tensor:
+def _colsum_f32(t: torch.Tensor, m: int, c: int) -> torch.Tensor:
     out = torch.empty(c, dtype=F32, device=t.device)
-    if m > 4096:
-        nrows = lib.tok_colsum_partial_rows(m, c)
-        part = torch.empty((nrows, c), dtype=F32, device=t.device)
-        _C.check(lib.tok_colsum_partial(ptr(t), m, c, ptr(part), st), 'tok_colsum_partial')
-        _C.check(lib.tok_colsum_f32(ptr(part), nrows, c, ptr(out), 0, st), 'tok_colsum_f32')
-    else:
-        _C.check(lib.tok_colsum(ptr(t), m, c, c, ptr(out), 0, st), 'tok_colsum')
-    return out
-
-
-def _wgrad_f32(lib, st, d: _C.ConvDesc, x: torch.Tensor, dy: torch.Tensor, k: int, c: int, out: torch.Tensor = None,
-               accumulate: int = 0) -> torch.Tensor:
-    """out[k][c] (fp32) = dy^T x through the weight-gradient kernels (also used for the Gram matrix z^T z)."""
-    if out is None:
-        out = torch.empty((k, c), dtype=F32, device=x.device)
-    ws_bytes = lib.tok_conv_wgrad_ws_bytes(d)
-    ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=x.device)
-    _C.check(lib.tok_conv_wgrad(d, ptr(x), ptr(dy), ptr(out), k, c, ptr(ws), ws_bytes, accumulate, st), 'tok_conv_wgrad')
+    PG.colsum(t, m, c, out, 0, two_pass=m > 4096, n_real=c)
     return out
 
 
@@ -577,17 +485,10 @@ class _Unit3Node(Node):
         if not (w_need or x_need or g_need or b_need):
             return
         # 3. G = dz^T x   (the weight-gradient launch, on dz)
-        G = _wgrad_f32(lib, st, d, x.data, dz, kp, p)
+        G = PG.weight_grad(d, x.data, dz, kp, p)[0]
         # 4. dgamma / dbeta / dW, coefficients and the two operands of the data gradient
-        gs, gm = param_grad_target(bn.weight) if g_need else (None, 0)
-        bs, bm = param_grad_target(bn.bias) if b_need else (None, 0)
-        ws_, wm = param_grad_target(conv.weight) if w_need else (torch.empty((kp, p), dtype=F32, device=dev), 0)
-        mixed = g_need and b_need and (gm == 1) != (bm == 1)
-        if mixed:     # one accumulates in its slot, the other does not: take both through temporaries
-            gbuf, bbuf = torch.empty_like(gs), torch.empty_like(bs)
-        else:
-            gbuf, bbuf = gs, bs
-        pacc = 1 if (not mixed and (gm == 1 or bm == 1)) else 0
+        gbuf, bbuf, pacc, finish = PG.pair_sinks(bn.weight if g_need else None, bn.bias if b_need else None)
+        dw, wacc = PG.sink(conv.weight) if w_need else (torch.empty((kp, p), dtype=F32, device=dev), 0)
         coef = torch.empty((3, kp), dtype=F32, device=dev)
         wa = torch.empty((p, kp), dtype=BF16, device=dev)
         wb = torch.empty((p, p), dtype=BF16, device=dev)
@@ -595,19 +496,11 @@ class _Unit3Node(Node):
         scratch = torch.empty(lib.tok_bn3_bwd_prepare_ws_floats(p, kp), dtype=F32, device=dev)
         _C.check(lib.tok_bn3_bwd_prepare(ptr(G), ptr(conv.weight), ptr(self.wz), ptr(self.zsum), ptr(partial), rows, m, p,
                                          kp, ptr(bn.weight), ptr(self.mean), ptr(self.rstd), ptr(gbuf), ptr(bbuf), pacc,
-                                         ptr(coef), ptr(ws_), 1 if wm == 1 else 0, ptr(wa), ptr(wb), ptr(cvec), ptr(scratch),
-                                         st), 'tok_bn3_bwd_prepare')
-        for need, prm, slot, mode, buf in ((g_need, bn.weight, gs, gm, gbuf), (b_need, bn.bias, bs, bm, bbuf)):
-            if not need:
-                continue
-            if mixed:
-                if mode == 1:
-                    slot.add_(buf)
-                else:
-                    slot.copy_(buf)
-            commit_param_grad(prm, slot, mode)
+                                         ptr(coef), ptr(dw), wacc, ptr(wa), ptr(wb), ptr(cvec), ptr(scratch), st),
+                 'tok_bn3_bwd_prepare')
+        finish()
         if w_need:
-            commit_param_grad(conv.weight, ws_, wm)
+            PG.commit(conv.weight, dw, wacc)
         if not x_need:
             return
         # 5. d(x) = dz wa + x wb + cvec  (+ the BatchNorm-backward sums of the unit that produced x)
@@ -656,14 +549,14 @@ def _unit3_forward(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm
     pk = get_packs(conv.weight, None, kp, 1, p, want_dgrad=False, refresh=True)
     # batch statistics of conv(x) from the second moments of x:  Z = x^T x  and  colsum(x)
     dz_ = _pointwise_desc(x, p)
-    zz = _wgrad_f32(lib, st, dz_, x.data, x.data, p, p)
+    zz = PG.weight_grad(dz_, x.data, x.data, p, p)[0]
     if x.colsum_part is not None:
         part, nrows = x.colsum_part        # left behind by the activation pass that produced x
         zsum = torch.empty(p, dtype=F32, device=x.data.device)
         _C.check(lib.tok_colsum_f32(ptr(part), nrows, p, ptr(zsum), 0, st), 'tok_colsum_f32')
         x.colsum_part = None
     else:
-        zsum = _colsum_f32(lib, st, x.data, m, p)
+        zsum = _colsum_f32(x.data, m, p)
     mean, rstd, scale, shift = (torch.empty(kp, dtype=F32, device=dev) for _ in range(4))
     wz = torch.empty((kp, p), dtype=F32, device=dev)       # W Z: the statistics now, the weight gradient later
     track = bn.training and bn.track_running_stats and bn.running_mean is not None
@@ -1078,8 +971,7 @@ class _DwConvBnActNode(_ConvBnActNode):
         w_need, x_need = conv.weight.requires_grad, x.requires_grad
         mask = self.mask if self.relu else None
         if self.batch_stats:
-            self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
-            coef = self.coef
+            coef = self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
         else:
             if bn.weight.requires_grad or bn.bias.requires_grad:
                 raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')
@@ -1094,10 +986,10 @@ class _DwConvBnActNode(_ConvBnActNode):
         if w_need:
             ws_bytes = lib.tok_dwconv_wgrad_ws_bytes(n, h, w, c, k, stride)
             ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-            slot, mode = param_grad_target(conv.weight)
-            _C.check(lib.tok_dwconv_wgrad(ptr(x.data), ptr(dy), n, h, w, c, c, k, stride, ptr(slot), 1 if mode == 1 else 0,
-                                          ptr(ws), ws_bytes, st), 'tok_dwconv_wgrad')
-            commit_param_grad(conv.weight, slot, mode)
+            slot, acc = PG.sink(conv.weight)
+            _C.check(lib.tok_dwconv_wgrad(ptr(x.data), ptr(dy), n, h, w, c, c, k, stride, ptr(slot), acc, ptr(ws), ws_bytes, st),
+                     'tok_dwconv_wgrad')
+            PG.commit(conv.weight, slot, acc)
         if x_need:
             tgt, acc = grad_target(x)
             _C.check(lib.tok_dwconv_dgrad(ptr(dy), ptr(conv.weight), n, h, w, c, c, k, stride, ptr(tgt), acc, st),
@@ -1175,22 +1067,16 @@ class _SqueezeExciteNode(Node):
         n, h, w, c = x.shape
         rd = se.conv_reduce.out_channels
         prm = (se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias)
-        targets, acc_bits = [], 0
-        for bit, p in enumerate(prm):
-            if p.requires_grad:
-                slot, mode = param_grad_target(p)
-                targets.append((p, slot, mode))
-                acc_bits |= (1 << bit) if mode == 1 else 0
-            else:
-                targets.append((p, None, 0))
+        targets = [(p, *(PG.sink(p) if p.requires_grad else (None, 0))) for p in prm]
+        acc_bits = sum(acc << bit for bit, (_, _, acc) in enumerate(targets))
         dx, dx_acc = grad_target(x) if x.requires_grad else (None, 0)
         ws = torch.empty(lib.tok_se_ws_floats(n, h * w, c, rd), dtype=F32, device=g.device)
         _C.check(lib.tok_se_bwd(ptr(g), ptr(x.data), n, h * w, c, c, rd, ptr(prm[0]), ptr(prm[2]), ptr(self.mean),
                                 ptr(self.hid), ptr(self.gate), *(ptr(t[1]) for t in targets), acc_bits, ptr(dx), dx_acc,
                                 ptr(ws), stream_ptr()), 'tok_se_bwd')
-        for p, slot, mode in targets:
+        for p, slot, acc in targets:
             if slot is not None:
-                commit_param_grad(p, slot, mode)
+                PG.commit(p, slot, acc)
         if self.region is not None:
             self.region.keep_until_join(ws)
 

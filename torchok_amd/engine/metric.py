@@ -12,8 +12,8 @@ import torch
 from torch import nn
 
 from .. import _C
-from .core import (BF16, Node, Region, TTensor, commit_param_grad, grad_target, pad8, param_grad_target, ptr,
-                   stream_ptr)
+from . import paramgrad as PG
+from .core import BF16, Node, Region, TTensor, grad_target, pad8, ptr, stream_ptr
 
 F32 = torch.float32
 EPS = 1e-12   # F.normalize default
@@ -64,15 +64,11 @@ class _CosineLinearNode(Node):
         x, w, d = self.x, self.weight, self.desc
         k, c = w.shape
         if w.requires_grad:
-            ws_bytes = lib.tok_conv_wgrad_ws_bytes(d)
-            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-            dwhat = torch.empty((k, c), dtype=F32, device=g.device)
-            _C.check(lib.tok_conv_wgrad(d, ptr(x.data), ptr(g), ptr(dwhat), k, c, ptr(ws), ws_bytes, 0, st),
-                     'tok_conv_wgrad')
-            slot, mode = param_grad_target(w)
-            _C.check(lib.tok_l2norm_bwd(ptr(dwhat), ptr(self.what), ptr(self.winv), ptr(slot), 1 if mode == 1 else 0,
-                                        k, c, c, 1, st), 'tok_l2norm_bwd')
-            commit_param_grad(w, slot, mode)
+            dwhat = PG.weight_grad(d, x.data, g, k, c)[0]
+            slot, acc = PG.sink(w)
+            _C.check(lib.tok_l2norm_bwd(ptr(dwhat), ptr(self.what), ptr(self.winv), ptr(slot), acc, k, c, c, 1, st),
+                     'tok_l2norm_bwd')
+            PG.commit(w, slot, acc)
         if x.requires_grad:
             tgt, acc = grad_target(x)
             _C.check(lib.tok_conv_dgrad(d, ptr(g), ptr(self.w_dgrad), ptr(tgt), acc, st), 'tok_conv_dgrad')

@@ -27,9 +27,9 @@ from torch import nn
 
 from .. import _C
 from . import functional as EF
+from . import paramgrad as PG
 from . import resample as ER
-from .core import (BF16, Region, TTensor, await_ready, commit_param_grad, grad_target, pad8, param_grad_target, ptr,
-                   stream_ptr)
+from .core import BF16, Region, TTensor, await_ready, grad_target, pad8, ptr, stream_ptr
 
 F32 = torch.float32
 NECK_COMMUTE = os.environ.get('TOK_NECK_COMMUTE', '1') != '0'
@@ -56,8 +56,7 @@ class _CommutedNeckNode(EF._ConvBnActNode):
         w_need = conv.weight.requires_grad
         srcs: List[TTensor] = self.srcs
         mask = self.mask if self.relu else None
-        self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
-        coef = self.coef
+        coef = self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
         if not (w_need or any(t.requires_grad for t in srcs)):
             out.grad = None
             return
@@ -84,32 +83,16 @@ class _CommutedNeckNode(EF._ConvBnActNode):
         k_real = conv.weight.shape[0]
 
         def run_wgrads():
-            st2 = stream_ptr()
-            slot, mode = param_grad_target(conv.weight)
+            slot, acc = PG.sink(conv.weight)
             slot2 = torch.as_strided(slot, (k_real, ctot), (ctot, 1), slot.storage_offset())
             keep = []
             for j, (t, d) in enumerate(zip(srcs, self.descs)):
-                ws_bytes = lib.tok_conv_wgrad_ws_bytes(d)
-                ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=dy.device)
-                dwj = torch.empty((k_real, t.cp), dtype=F32, device=dy.device)
-                _C.check(lib.tok_conv_wgrad(d, ptr(t.data), ptr(dys[j]), ptr(dwj), k_real, t.cp, ptr(ws), ws_bytes, 0, st2),
-                         'tok_conv_wgrad')
+                keep += PG.weight_grad(d, t.data, dys[j], k_real, t.cp)
                 off = self.offs[j]
-                if mode == 1:
-                    slot2[:, off:off + t.cp].add_(dwj)
-                else:
-                    slot2[:, off:off + t.cp].copy_(dwj)
-                keep += [ws, dwj]
-            commit_param_grad(conv.weight, slot, mode)
+                PG.store(slot2[:, off:off + t.cp], acc, keep[-2])
+            PG.commit(conv.weight, slot, acc)
             return keep
-
-        side = (EF.WGRAD_SIDE_STREAM and EF._side_for_tag(self.stream_tag, self.region) and dy.is_cuda
-                and self.region is not None and not torch.cuda.is_current_stream_capturing())
-        if side:
-            with self.region.fork_side([t.data for t in srcs] + dys):
-                self.region.keep_until_join(*run_wgrads())
-        else:
-            run_wgrads()
+        PG.run_beside(self, PG.goes_side(self, dy, PG.NECK), [t.data for t in srcs] + dys, run_wgrads)
 
 
 def commuted_ok(srcs: List[TTensor], size: Tuple[int, int], conv: nn.Module, bn: Optional[nn.BatchNorm2d]) -> bool:

@@ -23,17 +23,11 @@ import torch
 from torch import nn
 
 from .. import _C
-from .core import (BF16, Node, Region, TTensor, await_mark, await_ready, commit_param_grad, donate_grad, grad_target,
-                   pad8, param_grad_target, ptr, stream_ptr, written_mark)
+from . import paramgrad as PG
+from .core import BF16, Node, Region, TTensor, await_mark, await_ready, donate_grad, grad_target, pad8, ptr, stream_ptr, written_mark
 from .functional import _krsc, get_packs
 
 F32 = torch.float32
-
-
-def _use_side(node, g: torch.Tensor) -> bool:
-    from . import functional as EF
-    return bool(EF.WGRAD_SIDE_STREAM and g.is_cuda and node.region is not None
-                and not torch.cuda.is_current_stream_capturing())
 
 
 def _rows(t: TTensor) -> int:
@@ -70,19 +64,6 @@ def reshape(region: Region, x: TTensor, shape: Sequence[int]) -> TTensor:
 
 
 # ---- linear --------------------------------------------------------------------------------------------------
-_LIN_PLANS = {}
-
-
-def _linear_plan(lib, d):
-    """(bias gradient rides the weight-gradient kernel?, workspace bytes with / without it) of a token-matrix geometry."""
-    key = (d.n, d.c, d.k, id(lib))
-    p = _LIN_PLANS.get(key)
-    if p is None:
-        p = (bool(lib.tok_conv_wgrad_bias_ok(d)), int(lib.tok_conv_wgrad_bias_ws_bytes(d)), int(lib.tok_conv_wgrad_ws_bytes(d)))
-        _LIN_PLANS[key] = p
-    return p
-
-
 class _LinearNode(Node):
     needs_backward = True
     mlp_first = None        # fc2 of a fused Mlp: the node of its fc1 (tok_mlp_bwd_dx covers both data gradients)
@@ -95,82 +76,41 @@ class _LinearNode(Node):
             return
         x, w, d = self.x, self.weight, self.desc
         m, kp = g.shape
-        side = _use_side(self, g)
+        side = PG.goes_side(self, g, PG.TOKEN)
+        sinks = [(p, start) for p, start in self.bias_sinks if p.requires_grad]
 
         def scatter_bias(tmp):
-            for p, start in self.bias_sinks:
-                if not p.requires_grad:
-                    continue
-                slot, mode = param_grad_target(p)
-                seg = tmp[start:start + p.numel()]
-                if mode == 1:
-                    slot.add_(seg)
-                else:
-                    slot.copy_(seg)
-                commit_param_grad(p, slot, mode)
-        # the column sums of g (bias gradients) come out of the weight-gradient kernel where it serves the layer
-        # (plan facts of the geometry are cached: two library calls less per layer and step on the launch thread)
-        plan = _linear_plan(lib, d)
-        bias_in_wgrad = bool(self.bias_sinks and w.requires_grad and plan[0])
+            for p, start in sinks:
+                slot, acc = PG.sink(p)
+                PG.store(slot, acc, tmp[start:start + p.numel()])
+                PG.commit(p, slot, acc)
+        # the column sums of g (bias gradients) come out of the weight-gradient kernel where it serves the layer; the
+        # parameter gradients are enqueued before the data gradient (the other order measured neutral: SwinV2-T 24.98 vs
+        # 24.97, DaViT-T 24.33 vs 24.20 ms/step), off the main chain and beside it (PG.TOKEN)
+        bias_in_wgrad = bool(self.bias_sinks and w.requires_grad and PG.wgrad_plan(d)[0])
         if self.bias_sinks and not bias_in_wgrad:
             def run_bias():
                 tmp = torch.empty(kp, dtype=F32, device=g.device)
-                nrows = lib.tok_colsum_partial_rows(m, kp)
-                part = torch.empty((nrows, kp), dtype=F32, device=g.device)
-                st_ = stream_ptr()
-                _C.check(lib.tok_colsum_partial(ptr(g), m, kp, ptr(part), st_), 'tok_colsum_partial')
-                _C.check(lib.tok_colsum_f32(ptr(part), nrows, kp, ptr(tmp), 0, st_), 'tok_colsum_f32')
+                part = PG.colsum(g, m, kp, tmp, 0, two_pass=True)
                 scatter_bias(tmp)
                 return tmp, part
-            bias_fn = run_bias
-        else:
-            bias_fn = None
-        wgrad_fn = None
+            PG.run_beside(self, side, (g,), run_bias)
         if w.requires_grad:
-            k, r, s, c = _krsc(w)
-            ws_bytes = plan[1] if bias_in_wgrad else plan[2]
-            # one bias parameter spanning all output features (fc1 / fc2 / proj): the kernel writes its gradient slot itself
-            sole = None
-            if bias_in_wgrad and len(self.bias_sinks) == 1:
-                bp, bstart = self.bias_sinks[0]
-                if bstart == 0 and bp.numel() == k and bp.requires_grad:
-                    sole = bp
+            k, _, _, c = _krsc(w)
 
             def run_wgrad():
-                ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-                slot, mode = param_grad_target(w)
-                if bias_in_wgrad and sole is not None:
-                    bslot, bmode = param_grad_target(sole)
-                    _C.check(lib.tok_conv_wgrad_bias(d, ptr(x.data), ptr(g), ptr(slot), k, c, ptr(ws), ws_bytes,
-                                                     1 if mode == 1 else 0, ptr(bslot), 1 if bmode == 1 else 0, stream_ptr()),
-                             'tok_conv_wgrad_bias')
-                    commit_param_grad(sole, bslot, bmode)
-                elif bias_in_wgrad:
-                    tmp = torch.empty(kp, dtype=F32, device=g.device)
-                    _C.check(lib.tok_conv_wgrad_bias(d, ptr(x.data), ptr(g), ptr(slot), k, c, ptr(ws), ws_bytes,
-                                                     1 if mode == 1 else 0, ptr(tmp), 0, stream_ptr()), 'tok_conv_wgrad_bias')
-                    scatter_bias(tmp)
-                else:
-                    _C.check(lib.tok_conv_wgrad(d, ptr(x.data), ptr(g), ptr(slot), k, c, ptr(ws), ws_bytes,
-                                                1 if mode == 1 else 0, stream_ptr()), 'tok_conv_wgrad')
-                commit_param_grad(w, slot, mode)
-                return ws
-            wgrad_fn = run_wgrad
-
-        # the parameter gradients are enqueued before the data gradient (the other order measured neutral: SwinV2-T 24.98 vs
-        # 24.97, DaViT-T 24.33 vs 24.20 ms/step)
-        if bias_fn is not None:
-            if side:       # parameter gradients only: off the main chain, beside it (see functional.py)
-                with self.region.fork_side((g,)):
-                    self.region.keep_until_join(*bias_fn())
-            else:
-                bias_fn()
-        if wgrad_fn is not None:
-            if side:
-                with self.region.fork_side((x.data, g)):       # dW beside the main chain (see functional.py)
-                    self.region.keep_until_join(wgrad_fn())
-            else:
-                wgrad_fn()
+                if not bias_in_wgrad:
+                    return PG.weight_grad(d, x.data, g, k, c, weight=w)[1:]
+                if len(self.bias_sinks) == 1 and len(sinks) == 1 and sinks[0][1] == 0 and sinks[0][0].numel() == k:
+                    # one bias parameter spanning all output features (fc1 / fc2 / proj): the kernel writes its sink itself
+                    return PG.weight_grad(d, x.data, g, k, c, weight=w, bias=sinks[0][0])[1:]
+                slot, acc = PG.sink(w)
+                tmp = torch.empty(kp, dtype=F32, device=g.device)
+                ws = PG.weight_grad(d, x.data, g, k, c, out=slot, accumulate=acc, bias_out=tmp)[1]
+                scatter_bias(tmp)
+                PG.commit(w, slot, acc)
+                return (ws,)
+            PG.run_beside(self, side, (x.data, g), run_wgrad)
         if x.requires_grad and self.dx_done:
             pass            # fc1 of a fused Mlp: fc2's backward launch already sent this gradient on (tok_mlp_bwd_dx)
         elif x.requires_grad:
@@ -336,34 +276,18 @@ class _LayerNormNode(Node):
                      'tok_layernorm_bwd')
             def run_param_grads():
                 st_ = stream_ptr()
-                keep = []
-                if ln.weight.requires_grad and ln.bias.requires_grad:
-                    (sw, mw), (sb, mb) = param_grad_target(ln.weight), param_grad_target(ln.bias)
-                    if mw != 2 and mb != 2:        # both folds in one launch
-                        _C.check(lib.tok_colsum_f32_pair(ptr(partial[0]), ptr(partial[1]), nrows, c, ptr(sw), 1 if mw == 1 else 0,
-                                                         ptr(sb), 1 if mb == 1 else 0, st_), 'tok_colsum_f32_pair')
-                        commit_param_grad(ln.weight, sw, mw)
-                        commit_param_grad(ln.bias, sb, mb)
-                        return keep
-                for p, part in ((ln.weight, partial[0]), (ln.bias, partial[1])):
-                    if p.requires_grad:
-                        slot, mode = param_grad_target(p)
-                        if mode == 2:
-                            tmp = torch.empty_like(slot)
-                            _C.check(lib.tok_colsum_f32(ptr(part), nrows, c, ptr(tmp), 0, st_), 'tok_colsum_f32')
-                            p.grad.add_(tmp)
-                            keep.append(tmp)
-                            commit_param_grad(p, slot, 1)
-                        else:
-                            _C.check(lib.tok_colsum_f32(ptr(part), nrows, c, ptr(slot), 1 if mode == 1 else 0, st_),
-                                     'tok_colsum_f32')
-                            commit_param_grad(p, slot, mode)
-                return keep
-            if _use_side(self, g):
-                with self.region.fork_side((partial,)):
-                    self.region.keep_until_join(*run_param_grads())
-            else:
-                run_param_grads()
+                (sw, aw), (sb, ab) = (PG.sink(p) if p.requires_grad else (None, 0) for p in (ln.weight, ln.bias))
+                if sw is not None and sb is not None:        # both folds in one launch
+                    _C.check(lib.tok_colsum_f32_pair(ptr(partial[0]), ptr(partial[1]), nrows, c, ptr(sw), aw, ptr(sb), ab, st_),
+                             'tok_colsum_f32_pair')
+                else:
+                    for slot, acc, part in ((sw, aw, partial[0]), (sb, ab, partial[1])):
+                        if slot is not None:
+                            _C.check(lib.tok_colsum_f32(ptr(part), nrows, c, ptr(slot), acc, st_), 'tok_colsum_f32')
+                for p, slot, acc in ((ln.weight, sw, aw), (ln.bias, sb, ab)):
+                    if slot is not None:
+                        PG.commit(p, slot, acc)
+            PG.run_beside(self, PG.goes_side(self, g, PG.TOKEN), (partial,), run_param_grads)
         if sc is not None and sc.requires_grad:
             # the residual branch passes the gradient through: hand the buffer over when we own it
             if not (self.out.grad_owned and donate_grad(sc, g.view(sc.data.shape))):
@@ -460,16 +384,9 @@ class _CpbBiasNode(Node):
         dev = self.scratch.device
         ls = self.logit_scale
         if ls is not None and ls.requires_grad:
-            slot, mode = param_grad_target(ls)
-            if mode == 2:
-                tmp = torch.empty_like(slot)
-                _C.check(lib.tok_colsum_f32(ptr(self.dscale), rows, heads, ptr(tmp), 0, st), 'tok_colsum_f32')
-                ls.grad.add_(tmp)
-                commit_param_grad(ls, slot, 1)
-            else:
-                _C.check(lib.tok_colsum_f32(ptr(self.dscale), rows, heads, ptr(slot), 1 if mode == 1 else 0, st),
-                         'tok_colsum_f32')
-                commit_param_grad(ls, slot, mode)
+            slot, acc = PG.sink(ls)
+            _C.check(lib.tok_colsum_f32(ptr(self.dscale), rows, heads, ptr(slot), acc, st), 'tok_colsum_f32')
+            PG.commit(ls, slot, acc)
         if not self.table.requires_grad:
             return
         dbias = torch.empty(heads * n * n, dtype=F32, device=dev)
@@ -540,16 +457,9 @@ class _WindowAttnNode(Node):
             # folds and parameter gradients happen in the position-bias unit's backward (its own stream)
             bn.scratch, bn.dscale, bn.logit_scale, bn.mark = scratch, dscale, ls, written_mark()
         elif ls.requires_grad:
-            slot, mode = param_grad_target(ls)
-            if mode == 2:
-                tmp = torch.empty_like(slot)
-                _C.check(lib.tok_colsum_f32(ptr(dscale), rows, heads, ptr(tmp), 0, st), 'tok_colsum_f32')
-                ls.grad.add_(tmp)
-                commit_param_grad(ls, slot, 1)
-            else:
-                _C.check(lib.tok_colsum_f32(ptr(dscale), rows, heads, ptr(slot), 1 if mode == 1 else 0, st),
-                         'tok_colsum_f32')
-                commit_param_grad(ls, slot, mode)
+            slot, acc = PG.sink(ls)
+            _C.check(lib.tok_colsum_f32(ptr(dscale), rows, heads, ptr(slot), acc, st), 'tok_colsum_f32')
+            PG.commit(ls, slot, acc)
         self.out.grad = None
 
     def release(self):
@@ -749,16 +659,10 @@ class _DwConvNode(Node):
         if w_need or b_need:
             blocks = lib.tok_dwconv3x3_wgrad_blocks(n, h)
             partial = torch.empty((blocks, x.c, 10), dtype=F32, device=g.device)
-            ws, wm = param_grad_target(conv.weight) if w_need else (None, 0)
-            bs, bm = param_grad_target(conv.bias) if b_need else (None, 0)
-            if wm == 2 or bm == 2 or (w_need and b_need and wm != bm):
-                raise NotImplementedError('dwconv3x3: foreign .grad tensors on the depthwise parameters')
-            _C.check(lib.tok_dwconv3x3_wgrad(ptr(x.data), ptr(g), n, h, w, x.c, ld, ptr(partial), ptr(ws), ptr(bs),
-                                             1 if (wm == 1 or bm == 1) else 0, st), 'tok_dwconv3x3_wgrad')
-            if w_need:
-                commit_param_grad(conv.weight, ws, wm)
-            if b_need:
-                commit_param_grad(conv.bias, bs, bm)
+            ws, bs, acc, finish = PG.pair_sinks(conv.weight if w_need else None, conv.bias if b_need else None)
+            _C.check(lib.tok_dwconv3x3_wgrad(ptr(x.data), ptr(g), n, h, w, x.c, ld, ptr(partial), ptr(ws), ptr(bs), acc, st),
+                     'tok_dwconv3x3_wgrad')
+            finish()
         if x.requires_grad:
             tgt, acc = grad_target(x)
             _C.check(lib.tok_dwconv3x3(ptr(g), ptr(conv.weight), None, ptr(tgt), acc, 1, n, h, w, x.c, ld, st), 'tok_dwconv3x3')
@@ -856,26 +760,15 @@ class _PatchEmbedNode(Node):
         m, kp = g.shape
         k, p = conv.out_channels, conv.kernel_size[0]
         if conv.bias is not None and conv.bias.requires_grad:
-            nrows = lib.tok_colsum_partial_rows(m, kp)
-            part = torch.empty((nrows, kp), dtype=F32, device=g.device)
-            _C.check(lib.tok_colsum_partial(ptr(g), m, kp, ptr(part), st), 'tok_colsum_partial')
-            slot, mode = param_grad_target(conv.bias)
-            tmp = torch.empty_like(slot) if mode == 2 else slot
-            _C.check(lib.tok_colsum_f32(ptr(part), nrows, kp, ptr(tmp), 1 if mode == 1 else 0, st), 'tok_colsum_f32')
-            commit_param_grad(conv.bias, tmp if mode == 2 else slot, mode)
+            slot, acc = PG.sink(conv.bias)
+            PG.colsum(g, m, kp, slot, acc, two_pass=True)
+            PG.commit(conv.bias, slot, acc)
         if conv.weight.requires_grad:
             # the GEMM's weight gradient over the gathered rows is [K][p][p][4]; the master's channels-last slot is [K][p][p][3]
-            ws_bytes = int(lib.tok_conv_wgrad_ws_bytes(d))
-            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-            full = torch.empty((k, p, p, 4), dtype=F32, device=g.device)
-            _C.check(lib.tok_conv_wgrad(d, ptr(rows), ptr(g), ptr(full), k, d.c, ptr(ws), ws_bytes, 0, st), 'tok_conv_wgrad')
-            slot, mode = param_grad_target(conv.weight)
-            dst = slot.permute(0, 2, 3, 1)
-            if mode == 1:
-                dst.add_(full[..., :conv.in_channels])
-            else:
-                dst.copy_(full[..., :conv.in_channels])
-            commit_param_grad(conv.weight, slot, mode)
+            full = PG.weight_grad(d, rows, g, k, d.c, out=torch.empty((k, p, p, 4), dtype=F32, device=g.device))[0]
+            slot, acc = PG.sink(conv.weight)
+            PG.store(slot.permute(0, 2, 3, 1), acc, full[..., :conv.in_channels])
+            PG.commit(conv.weight, slot, acc)
         self.out.grad = None
 
     def release(self):
@@ -931,16 +824,14 @@ class _VitEmbedNode(Node):
         has_cls = cls is not None
         pos_need, cls_need = pos.requires_grad, has_cls and cls.requires_grad
         if pos_need or cls_need:       # a frozen parameter takes no fold at all
-            (ps, pm) = param_grad_target(pos) if pos_need else (None, 0)
-            (cs, cm) = param_grad_target(cls) if cls_need else (None, 0)
-            pt = torch.empty_like(ps) if pm == 2 else ps
-            ct = torch.empty_like(cs) if cm == 2 else cs
-            _C.check(lib.tok_vit_embed_bwd(ptr(g), b, n_p, dim, 1 if has_cls else 0, 1 if no_embed_class else 0, ptr(pt),
-                                           1 if pm == 1 else 0, ptr(ct), 1 if cm == 1 else 0, st), 'tok_vit_embed_bwd')
+            ps, pa = PG.sink(pos) if pos_need else (None, 0)
+            cs, ca = PG.sink(cls) if cls_need else (None, 0)
+            _C.check(lib.tok_vit_embed_bwd(ptr(g), b, n_p, dim, 1 if has_cls else 0, 1 if no_embed_class else 0, ptr(ps), pa,
+                                           ptr(cs), ca, st), 'tok_vit_embed_bwd')
             if pos_need:
-                commit_param_grad(pos, pt if pm == 2 else ps, pm)
+                PG.commit(pos, ps, pa)
             if cls_need:
-                commit_param_grad(cls, ct if cm == 2 else cs, cm)
+                PG.commit(cls, cs, ca)
         if x.requires_grad:
             tgt, acc = grad_target(x)
             prefix = 1 if has_cls else 0
