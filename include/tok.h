@@ -109,7 +109,12 @@ int tok_pack_weights_batched(const tok_pack_item* items_dev, int n_items, int to
  * (a linear layer is the 1x1 case with h = w = 1).                                        */
 
 /* Rows of the per-channel partial-statistics buffer tok_conv_fwd fills: the buffer is
- * float[2][rows][k] (sum, then sum of squares, of the bf16-rounded outputs).              */
+ * float[2][rows][k] (sum, then sum of squares, of the bf16-rounded outputs).
+ * Statistics contract, the same on every route (two-buffer implicit GEMM, pointwise ring, 256 x 256 tiles, shared-window
+ * 3x3 kernel, stem window kernel): a row holds fp32 sums of the values AS STORED in y - each output is rounded to bf16
+ * first, then that rounded value (and its square, one fma) is added - never of the fp32 accumulators.  Folding the rows
+ * therefore gives the sums of the tensor BatchNorm normalises, to fp32 summation error only.  Every one of the `rows` rows
+ * is written by the call (rows that own no pixels are written as zeros), nothing behind them.                            */
 int tok_conv_fwd_stat_rows(const tok_conv_desc* d);
 /* y = conv(x, w) (+ bias[k] if bias != NULL).  stats may be NULL.                         */
 int tok_conv_fwd(const tok_conv_desc* d, const void* x, const void* w, const float* bias,
@@ -123,7 +128,12 @@ int tok_conv_dgrad(const tok_conv_desc* d, const void* dy, const void* w_dgrad, 
  * registers, also loads that unit's raw conv output bn_y (same NHWC shape as dx) and its ReLU
  * bit mask (nullable = no ReLU) and accumulates sum(dz), sum(dz*y), dz = dx*mask, into
  * partial[2][tok_conv_dgrad_stat_rows(d)][c] — replacing a separate tok_bn_bwd_reduce pass over
- * dx and y (feed the result to tok_bn_bwd_finalize with dzy_form = 1).                     */
+ * dx and y (feed the result to tok_bn_bwd_finalize with dzy_form = 1).
+ * Statistics contract (tok_conv_dgrad_bnstats, _bias, _subacc, tok_conv_dgrad2; every route: two-buffer kernel, ring,
+ * 256 x 256 tiles, both window kernels): dx here is the bf16 value AS STORED (after +=, bias and dsub), so the rows fold
+ * to the fp32 sums of mask ? dx : 0 and of that times bn_y over the stored tensor.  tok_conv_dgrad_maskstore and the
+ * mask_store form of tok_conv_dgrad_subacc sum the stored dz into the first half and write zeros into the second.
+ * Every announced row is written, nothing behind them.                                                                  */
 int tok_conv_dgrad_stat_rows(const tok_conv_desc* d);
 int tok_conv_dgrad_bnstats(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                            int accumulate, const void* bn_y, const uint8_t* bn_mask, float* partial,

@@ -135,9 +135,10 @@ def assert_bounded(mine, ref, mag, a, b, what='', test=None):
     return worst
 
 
-_INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32}
-SENTINEL = {torch.bfloat16: 0x5A5B, torch.float32: 0x5A5B5C5D}   # finite, ~1e16: no kernel here produces these bits
+_INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8}
+SENTINEL = {torch.bfloat16: 0x5A5B, torch.float32: 0x5A5B5C5D, torch.uint8: 0x5A}   # finite, ~1e16: no kernel here produces these bits
 BF16_NAN = 0x7FC1
+NAN_BITS = {torch.bfloat16: BF16_NAN, torch.float32: 0x7FC00001, torch.uint8: 0xFF}   # (bytes: every mask bit set)
 
 
 class Guarded:
@@ -170,3 +171,88 @@ class Guarded:
         bad_pad = int((pads != self.bits).sum()) if pads.numel() else 0
         bad_guard = int((iv[self.rows] != self.bits).sum())
         assert bad_pad == 0 and bad_guard == 0, f'{what}: {bad_pad} pad and {bad_guard} guard-row elements overwritten'
+
+
+def halo_guard(pad, w, c, pitch):
+    """Elements of one guard of a convolution operand of row pitch `pitch`: a full halo — `pad` rows of w pixels, `pad` pixels
+    and one more, (pad (w + 1) + 1) c elements — or one 128-row tile, whichever is larger."""
+    return max((pad * (w + 1) + 1) * c, 128 * pitch)
+
+
+class GuardedSpan:
+    """`numel` contiguous elements with a guard region IN FRONT and another BEHIND (convolution halos reach backwards: row -1 of
+    image 0).  Each guard holds at least `guard` elements, rounded up to whole 256-byte blocks so that the operand keeps the
+    allocation's alignment; the guard behind starts at the operand's last element + 1 exactly (a workspace of `ws_bytes` bytes
+    is GuardedSpan(ws_bytes, torch.uint8, ...)).  Outputs carry SENTINEL bits, inputs (nan_guard=True) NaN; `check()` asserts both
+    guards unchanged, `untouched()` that the operand itself still holds its fill (a refused call writes nothing)."""
+
+    def __init__(self, numel, dtype, guard, init=None, nan_guard=False, device='cuda'):
+        esz = torch.empty((), dtype=dtype).element_size()
+        g = -(-max(int(guard), 1) * esz // 256) * 256 // esz
+        self.numel, self.g, self.dtype = int(numel), g, dtype
+        self.bits = (NAN_BITS if nan_guard else SENTINEL)[dtype]
+        self.buf = torch.empty(g + self.numel + g, dtype=dtype, device=device)
+        self.buf.view(_INT_OF[dtype]).fill_(self.bits)
+        self.view = self.buf[g:g + self.numel]
+        assert self.view.data_ptr() % 16 == 0
+        if init is not None:
+            self.view.copy_(init.reshape(-1))
+
+    @property
+    def ptr(self):
+        return self.view.data_ptr()
+
+    def value(self):
+        return self.view.detach().cpu()
+
+    def check(self, what=''):
+        iv = self.buf.view(_INT_OF[self.dtype])
+        front = int((iv[:self.g] != self.bits).sum())
+        back = int((iv[self.g + self.numel:] != self.bits).sum())
+        assert front == 0 and back == 0, f'{what}: {front} elements of the guard in front and {back} of the guard behind overwritten'
+
+    def untouched(self):
+        return bool((self.view.view(_INT_OF[self.dtype]) == self.bits).all())
+
+
+# ---- shared by the convolution contract modules (tests/test_conv_contract_gpu.py, tests/test_conv_wgrad_contract_gpu.py) --------
+BF, F32, U8 = torch.bfloat16, torch.float32, torch.uint8
+U32 = 2.0 ** -24            # fp32 unit roundoff
+A_BF = 2.0 ** -8            # one bf16 rounding
+ERR_INVALID, ERR_WORKSPACE = -1, -3
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def conv_desc(n, h, w, c, k, r, stride, pad):
+    """tok_conv_desc of a square filter (c == 4: the stem form, taps stored 8 wide)"""
+    from torchok_amd import _C
+    p, q = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - r) // stride + 1
+    return _C.ConvDesc(n, h, w, c, k, r, r, p, q, stride, pad, 8 if c == 4 else r)
+
+
+def last_error():
+    from torchok_amd import _C
+    e = _C.lib().tok_last_error()
+    return e.decode() if isinstance(e, bytes) else e
+
+
+def gin(t, guard):
+    """an input operand: NaN in both guards"""
+    return GuardedSpan(t.numel(), t.dtype, guard, init=t, nan_guard=True)
+
+
+def gout(numel, dtype, guard, init=None):
+    """an output operand: sentinels in both guards (and in the operand itself unless `init` fills it)"""
+    return GuardedSpan(numel, dtype, guard, init=init)
+
+
+def unpack_bits(mask_bytes, rows, c):
+    return ((mask_bytes.view(rows, c // 8).long().unsqueeze(-1) >> torch.arange(8)) & 1).reshape(rows, c).bool()
+
+
+def pack_bits(bits):
+    rows, c = bits.shape
+    return (bits.view(rows, c // 8, 8).long() << torch.arange(8)).sum(-1).to(torch.uint8)

@@ -117,8 +117,8 @@ def test_conv_fwd(libs, case):
     yd, sd = dv[id(y)], dv[id(stats)][:2 * rows_dev * k].view(2, rows_dev, k)
     assert relerr(yd.float(), y.float()) < 4e-3
     assert maxrel(yd.float(), y.float(), 0.05) < 3e-2
-    # the partial sums are taken over the fp32 accumulators (before the bf16 store): against the
-    # sums of the stored values they may differ by the rounding noise, <= 2^-8 relative per element
+    # the partial sums are taken over the STORED bf16 values on every route (include/tok.h; asserted to the summation bound
+    # in tests/test_conv_contract_gpu.py): this older gate is looser than the contract
     f = yd.float().reshape(-1, k)
     assert relerr(sd[0].sum(0), f.sum(0)) < 4e-3 or float((sd[0].sum(0).cpu() - f.sum(0).cpu()).abs().max()) < 2e-2
     assert relerr(sd[1].sum(0), (f * f).sum(0)) < 4e-3

@@ -884,6 +884,9 @@ int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const fl
                   void* stream, void* y_act, int act, const BnEpilogue* ep) {
   if (int e = check_desc(d, "tok_conv_fwd")) return e;
   TOK_CHECK_ARG(x && w && y, "tok_conv_fwd: null pointer");
+  // (refused here, by name: launch<>() below knows the mode, not the entry point)
+  TOK_CHECK_ARG(y_act == nullptr || (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->c != 4),
+                "tok_conv_fwd_act: 1x1 / stride 1 / no padding layers only");
   ConvArgs a = {};
   a.x = (const bf16*)x; a.w = (const bf16*)w; a.y = (bf16*)y; a.bias = bias; a.stats = stats;
   a.y2 = (bf16*)y_act; a.act = act;
@@ -992,6 +995,9 @@ int dgrad_impl(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void
                int mask_store = 0, const void* sub = nullptr) {
   if (int e = check_desc(d, who)) return e;
   TOK_CHECK_ARG(dy && w_dgrad && dx, "%s: null pointer", who);
+  // (refused here, by name: launch<>() below knows the mode, not the entry point)
+  TOK_CHECK_ARG((act_x == nullptr && sub == nullptr) || (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0),
+                "%s: 1x1 / stride 1 / no padding layers only", who);
   ConvArgs a = {};
   DgradPlan pl;
   if (int e = dgrad_fill(d, a, pl)) return e;
