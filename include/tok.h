@@ -280,6 +280,18 @@ int tok_bn_bwd_apply(const void* dout, const void* y, const uint8_t* mask,
                      const float* scale, const float* shift, const float* coef, int relu,
                      void* dy, void* dshortcut, int dshortcut_accumulate,
                      int64_t m, int c, void* stream);
+/* BatchNorm + hard-swish without a mask (MobileNetV3; csrc/act.hip): z = y*scale + shift is recomputed from the stored bf16 y
+ * in every pass.  out = z * min(max(z + 3, 0), 6) / 6;  dz = dout * hswish'(z), hswish'(z) = 0 (z < -3), z/3 + 0.5
+ * (-3 <= z <= 3), 1 (z > 3): what torch.nn.functional.hardswish differentiates to.
+ * tok_bn_hswish_bwd_reduce: partial[2][tok_bn_bwd_rows(m, c)][c] = sum(dz), sum(dz * xhat) in the row layout of
+ *   tok_bn_bwd_reduce -> tok_bn_bwd_finalize with dzy_form = 0.
+ * tok_bn_hswish_bwd_apply: dy = a1*dz + a2*y + a3 from coef[3][c] (eval-mode BatchNorm: coef = (scale, 0, 0)).
+ * No shortcut, no mask; c % 8 == 0.                                                                              */
+int tok_bn_hswish_fwd(const void* y, const float* scale, const float* shift, void* out, int64_t m, int c, void* stream);
+int tok_bn_hswish_bwd_reduce(const void* dout, const void* y, const float* scale, const float* shift, const float* mean,
+                             const float* rstd, int64_t m, int c, float* partial, void* stream);
+int tok_bn_hswish_bwd_apply(const void* dout, const void* y, const float* scale, const float* shift, const float* coef,
+                            void* dy, int64_t m, int c, void* stream);
 
 
 /* ---- pooling ----------------------------------------------------------------------------
@@ -665,6 +677,14 @@ int tok_se_fwd(const void* x, int n, int hw, int c, int ld, int rd, const float*
 int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, const float* w1, const float* w2,
                const float* mean, const float* hid, const float* gate, float* dw1, float* db1, float* dw2, float* db2,
                int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
+/* The same two entry points with the gate as an argument (MobileNetV3): gate_kind 0 = sigmoid (tok_se_fwd / tok_se_bwd, bit for
+ * bit), 1 = hard sigmoid min(max(a + 3, 0), 6) / 6, whose derivative is 1/6 where the stored gate lies strictly between 0 and 1
+ * and 0 elsewhere.  Buffers, workspace, accumulate bits and size limits are those of tok_se_fwd / tok_se_bwd.           */
+int tok_se_gate_fwd(const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, const float* w1, const float* b1,
+                    const float* w2, const float* b2, float* mean, float* hid, float* gate, float* ws, void* stream);
+int tok_se_gate_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, const float* w1,
+                    const float* w2, const float* mean, const float* hid, const float* gate, float* dw1, float* db1, float* dw2,
+                    float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
 
 /* ---- Vision Transformer: global self-attention and token embedding ([timm 0.6.13] vision_transformer.Attention.forward,
  * PatchEmbed, VisionTransformer._pos_embed; reached from torchok/models/backbones/vit.py:202-357) -------------------------------

@@ -73,6 +73,9 @@ PROTOTYPES = {
     'tok_bn_bwd_reduce': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int, _P, _P]),
     'tok_bn_bwd_finalize': (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     'tok_bn_bwd_apply': (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int64, c_int, _P]),
+    'tok_bn_hswish_fwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, _P]),
+    'tok_bn_hswish_bwd_reduce': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P]),
+    'tok_bn_hswish_bwd_apply': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
     'tok_maxpool3x3s2_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     'tok_maxpool3x3s2_bwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     'tok_avgpool2x2_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
@@ -183,6 +186,9 @@ PROTOTYPES = {
     'tok_se_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tok_se_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int,
                            _P, _P]),
+    'tok_se_gate_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'tok_se_gate_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P,
+                                c_int, _P, _P]),
     'tok_global_attn_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     'tok_global_attn_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'tok_global_attn_bwd': (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),

@@ -1,5 +1,8 @@
-// Squeeze-excite of the MnasNet-A1 blocks ([timm] efficientnet_blocks.SqueezeExcite with ReLU and a sigmoid gate):
-//   s[n][c] = sigmoid(b2 + W2 relu(b1 + W1 mean_hw(x[n])))      out = x * s   (the product: tok_channel_scale)
+// Squeeze-excite of the MnasNet-A1 and MobileNetV3 blocks ([timm] efficientnet_blocks.SqueezeExcite with ReLU and a sigmoid
+// or hard-sigmoid gate):
+//   s[n][c] = gate(b2 + W2 relu(b1 + W1 mean_hw(x[n])))      out = x * s   (the product: tok_channel_scale)
+//   gate 0: sigmoid(a), s' = s (1 - s);  gate 1: hard sigmoid min(max(a + 3, 0), 6) / 6, s' = 1/6 where 0 < s < 1, else 0
+// The gate is a compile-time parameter of the two per-image kernels: the sigmoid instantiation is the MnasNet code.
 // x / dout / dx bf16 [n][hw][ld] (c % 8 == 0), W1 fp32 [rd][c] (conv_reduce), W2 fp32 [c][rd] (conv_expand), 1 <= rd <= 256.
 //
 // Forward : per-(image, chunk) channel sums -> one block per image folds them in chunk order and runs the two 1x1 layers.
@@ -70,8 +73,10 @@ __global__ __launch_bounds__(256) void se_sum_kernel(const bf16* __restrict__ a,
 }
 
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + __expf(-v)); }
+__device__ __forceinline__ float hard_sigmoid_f(float v) { return fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f; }
 
-// one block per image: mean, hidden = relu(W1 mean + b1), gate = sigmoid(W2 hidden + b2)
+// one block per image: mean, hidden = relu(W1 mean + b1), gate = GATE(W2 hidden + b2)
+template <int GATE>
 __global__ __launch_bounds__(256) void se_fwd_image_kernel(const float* __restrict__ part, int chunks, int hw, int C, int rd,
                                                            const float* __restrict__ w1, const float* __restrict__ b1,
                                                            const float* __restrict__ w2, const float* __restrict__ b2,
@@ -102,11 +107,12 @@ __global__ __launch_bounds__(256) void se_fwd_image_kernel(const float* __restri
   for (int c = tid; c < C; c += 256) {
     float a = b2[c];
     for (int j = 0; j < rd; ++j) a = fmaf(w2[(size_t)c * rd + j], h[j], a);
-    gate[(size_t)img * C + c] = sigmoid_f(a);
+    gate[(size_t)img * C + c] = GATE == 0 ? sigmoid_f(a) : hard_sigmoid_f(a);
   }
 }
 
-// one block per image: ds = g s (1 - s), dh = relu'(hidden) W2^T ds, dmean = W1^T dh
+// one block per image: ds = g s' (s' from the stored gate, see the top), dh = relu'(hidden) W2^T ds, dmean = W1^T dh
+template <int GATE>
 __global__ __launch_bounds__(256) void se_bwd_image_kernel(const float* __restrict__ part, int chunks, int C, int rd,
                                                            const float* __restrict__ w1, const float* __restrict__ w2,
                                                            const float* __restrict__ hid, const float* __restrict__ gate,
@@ -119,7 +125,7 @@ __global__ __launch_bounds__(256) void se_bwd_image_kernel(const float* __restri
     float a = 0.f;
     for (int k = 0; k < chunks; ++k) a += part[((size_t)img * chunks + k) * C + c];
     const float s = gate[(size_t)img * C + c];
-    const float d = a * s * (1.f - s);
+    const float d = GATE == 0 ? a * s * (1.f - s) : ((s > 0.f && s < 1.f) ? a * (1.f / 6.f) : 0.f);
     ds[c] = d;
     ds_out[(size_t)img * C + c] = d;
   }
@@ -220,24 +226,29 @@ extern "C" size_t tok_se_ws_floats(int n, int hw, int c, int rd) {
   return (size_t)n * g.chunks * c + 2 * (size_t)n * c + (size_t)n * rd;
 }
 
-extern "C" int tok_se_fwd(const void* x, int n, int hw, int c, int ld, int rd, const float* w1, const float* b1, const float* w2,
-                          const float* b2, float* mean, float* hid, float* gate, float* ws, void* stream) {
-  TOK_CHECK_ARG(x && w1 && b1 && w2 && b2 && mean && hid && gate && ws, "tok_se_fwd: null pointer");
-  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_fwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+namespace {
+
+int se_fwd_launch(const char* name, int gate_kind, const void* x, int n, int hw, int c, int ld, int rd, const float* w1,
+                  const float* b1, const float* w2, const float* b2, float* mean, float* hid, float* gate, float* ws,
+                  void* stream) {
   const SeGeo g = se_geo(n, hw, c);
   hipStream_t st = tok_stream(stream);
   hipLaunchKernelGGL(se_sum_kernel, dim3(g.chunks, n), dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, hw, c, ld, g.cge,
                      g.rpb, ws);
-  hipLaunchKernelGGL(se_fwd_image_kernel, dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid, gate);
-  TOK_CHECK_LAUNCH("tok_se_fwd");
+  if (gate_kind == 0)
+    hipLaunchKernelGGL(se_fwd_image_kernel<0>, dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid,
+                       gate);
+  else
+    hipLaunchKernelGGL(se_fwd_image_kernel<1>, dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid,
+                       gate);
+  TOK_CHECK_LAUNCH(name);
   return TOK_OK;
 }
 
-extern "C" int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, const float* w1,
-                          const float* w2, const float* mean, const float* hid, const float* gate, float* dw1, float* db1,
-                          float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream) {
-  TOK_CHECK_ARG(dout && x && w1 && w2 && mean && hid && gate && ws, "tok_se_bwd: null pointer");
-  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_bwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+int se_bwd_launch(const char* name, int gate_kind, const void* dout, const void* x, int n, int hw, int c, int ld, int rd,
+                  const float* w1, const float* w2, const float* mean, const float* hid, const float* gate, float* dw1,
+                  float* db1, float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws,
+                  void* stream) {
   const SeGeo g = se_geo(n, hw, c);
   hipStream_t st = tok_stream(stream);
   float* part = ws;
@@ -246,13 +257,56 @@ extern "C" int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c,
   float* dh = dmean + (size_t)n * c;
   hipLaunchKernelGGL(se_sum_kernel, dim3(g.chunks, n), dim3(256), 0, st, (const bf16*)dout, (const bf16*)x, hw, c, ld, g.cge,
                      g.rpb, part);
-  hipLaunchKernelGGL(se_bwd_image_kernel, dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh, dmean);
+  if (gate_kind == 0)
+    hipLaunchKernelGGL(se_bwd_image_kernel<0>, dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh,
+                       dmean);
+  else
+    hipLaunchKernelGGL(se_bwd_image_kernel<1>, dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh,
+                       dmean);
   if (dw1 || db1 || dw2 || db2)
     hipLaunchKernelGGL(se_param_grad_kernel, dim3(blocks_for(2 * (size_t)c * rd + c + rd)), dim3(256), 0, st, ds, dh, hid, mean,
                        n, c, rd, dw1, db1, dw2, db2, param_accumulate);
   if (dx != nullptr)
     hipLaunchKernelGGL(se_dx_kernel, dim3(blocks_for((size_t)n * hw * (c >> 3))), dim3(256), 0, st, (const bf16*)dout, gate,
                        dmean, n, hw, c, ld, (bf16*)dx, dx_accumulate);
-  TOK_CHECK_LAUNCH("tok_se_bwd");
+  TOK_CHECK_LAUNCH(name);
   return TOK_OK;
+}
+
+}  // namespace
+
+extern "C" int tok_se_fwd(const void* x, int n, int hw, int c, int ld, int rd, const float* w1, const float* b1, const float* w2,
+                          const float* b2, float* mean, float* hid, float* gate, float* ws, void* stream) {
+  TOK_CHECK_ARG(x && w1 && b1 && w2 && b2 && mean && hid && gate && ws, "tok_se_fwd: null pointer");
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_fwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+  return se_fwd_launch("tok_se_fwd", 0, x, n, hw, c, ld, rd, w1, b1, w2, b2, mean, hid, gate, ws, stream);
+}
+
+extern "C" int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, const float* w1,
+                          const float* w2, const float* mean, const float* hid, const float* gate, float* dw1, float* db1,
+                          float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream) {
+  TOK_CHECK_ARG(dout && x && w1 && w2 && mean && hid && gate && ws, "tok_se_bwd: null pointer");
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_bwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+  return se_bwd_launch("tok_se_bwd", 0, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2,
+                       param_accumulate, dx, dx_accumulate, ws, stream);
+}
+
+extern "C" int tok_se_gate_fwd(const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, const float* w1,
+                               const float* b1, const float* w2, const float* b2, float* mean, float* hid, float* gate,
+                               float* ws, void* stream) {
+  TOK_CHECK_ARG(x && w1 && b1 && w2 && b2 && mean && hid && gate && ws, "tok_se_gate_fwd: null pointer");
+  TOK_CHECK_ARG(gate_kind == 0 || gate_kind == 1, "tok_se_gate_fwd: gate 0 (sigmoid) or 1 (hard sigmoid)");
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_gate_fwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+  return se_fwd_launch("tok_se_gate_fwd", gate_kind, x, n, hw, c, ld, rd, w1, b1, w2, b2, mean, hid, gate, ws, stream);
+}
+
+extern "C" int tok_se_gate_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, int gate_kind,
+                               const float* w1, const float* w2, const float* mean, const float* hid, const float* gate,
+                               float* dw1, float* db1, float* dw2, float* db2, int param_accumulate, void* dx,
+                               int dx_accumulate, float* ws, void* stream) {
+  TOK_CHECK_ARG(dout && x && w1 && w2 && mean && hid && gate && ws, "tok_se_gate_bwd: null pointer");
+  TOK_CHECK_ARG(gate_kind == 0 || gate_kind == 1, "tok_se_gate_bwd: gate 0 (sigmoid) or 1 (hard sigmoid)");
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_gate_bwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
+  return se_bwd_launch("tok_se_gate_bwd", gate_kind, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2,
+                       param_accumulate, dx, dx_accumulate, ws, stream);
 }

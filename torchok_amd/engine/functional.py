@@ -9,7 +9,10 @@ max_pool_3x3_s2           nn.MaxPool2d(3, 2, 1)                          (resnet
 global_avg_pool           SelectAdaptivePool2d('avg', flatten=True)      (pooling.py:7-12)
 linear                    nn.Linear                                      (linear_head.py:31)
 dwconv_bn_act             depthwise conv -> batch_norm -> relu           ([timm] DepthwiseSeparableConv / InvertedResidual)
-squeeze_excite            x * sigmoid(expand(relu(reduce(mean(x)))))     ([timm] efficientnet_blocks.SqueezeExcite)
+squeeze_excite            x * gate(expand(relu(reduce(mean(x)))))        ([timm] efficientnet_blocks.SqueezeExcite;
+                          gate = sigmoid or hard sigmoid)
+
+conv_bn_act / dwconv_bn_act take act='hard_swish' (MobileNetV3): the mask-less activation path of csrc/act.hip.
 """
 import weakref
 from typing import Optional
@@ -227,8 +230,24 @@ def _check_conv(conv: nn.Conv2d):
 
 # ---- conv + bn + (add) + relu ------------------------------------------------------------------------
 
+HARD_SWISH = 'hard_swish'
+
+
+def _check_act(act, bn, shortcut=None, pool=False, defer_apply=False) -> bool:
+    """act=None: the unit's activation is what `relu` says.  act='hard_swish': BatchNorm + hard-swish on tok_bn_hswish_*, which
+    keeps no mask and knows no shortcut, pooled or deferred form (MobileNetV3 never activates after a residual add)."""
+    if act is None:
+        return False
+    if act != HARD_SWISH:
+        raise NotImplementedError(f'torchok_amd activation {act!r}: None (ReLU / identity by `relu`) or {HARD_SWISH!r}')
+    if bn is None or shortcut is not None or pool or defer_apply:
+        raise NotImplementedError(f"act={HARD_SWISH!r}: BatchNorm units without shortcut, pool or defer_apply only")
+    return True
+
+
 class _ConvBnActNode(Node):
     needs_backward = True
+    act = None                      # 'hard_swish': dz is recomputed from y in tok_bn_hswish_bwd_* (no mask, relu is False)
 
     def __init__(self):
         self.x = self.out = self.shortcut = None
@@ -245,7 +264,18 @@ class _ConvBnActNode(Node):
 
     def wants_fused_bwd_stats(self) -> bool:
         """Can the kernel that completes d(out) also reduce sum(dz), sum(dz*y) for this unit?"""
-        return self.bn is not None and self.batch_stats and (not self.relu or self.mask is not None) and self.pool is None
+        # (the dgrad epilogues know the ReLU mask only: a hard-swish producer takes the stand-alone reduce)
+        return (self.bn is not None and self.batch_stats and (not self.relu or self.mask is not None) and self.pool is None
+                and self.act is None)
+
+    def _apply_bwd(self, lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp):
+        """dy = c1*dz + c2*y + c3 (and the shortcut's dz) for the unit's activation."""
+        if self.act is not None:
+            _C.check(lib.tok_bn_hswish_bwd_apply(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(coef), ptr(dy), m, kp,
+                                                 st), 'tok_bn_hswish_bwd_apply')
+        else:
+            _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift), ptr(coef),
+                                          int(self.relu), ptr(dy), ds_ptr, ds_acc, m, kp, st), 'tok_bn_bwd_apply')
 
     def _finalize_bwd(self, lib, st, g, mask, m, kp, g_need, b_need):
         """sum(dz), sum(dz*xhat) -> dgamma, dbeta; returns the apply coefficients (stand-alone reduce / finalize launches)."""
@@ -270,6 +300,10 @@ class _ConvBnActNode(Node):
                 _C.check(lib.tok_bn_pool_bwd_reduce(ptr(g), ptr(self.pool), ptr(self.y), ptr(self.scale), ptr(self.shift),
                                                     ptr(self.mean), ptr(self.rstd), n_, h_, w_, kp, ptr(partial), st),
                          'tok_bn_pool_bwd_reduce')
+            elif self.act is not None:
+                partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
+                _C.check(lib.tok_bn_hswish_bwd_reduce(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(self.mean),
+                                                      ptr(self.rstd), m, kp, ptr(partial), st), 'tok_bn_hswish_bwd_reduce')
             else:
                 partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
                 _C.check(lib.tok_bn_bwd_reduce(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift),
@@ -315,7 +349,7 @@ class _ConvBnActNode(Node):
                 coef[0] = self.scale
             if need_dy or sc_need:
                 dy = torch.empty_like(self.y)
-                if side and self.pool is None:
+                if side and self.pool is None and self.act is None:
                     # the weight gradient will be forked to the side stream behind THIS apply pass: the pass carries the
                     # completion event itself (no event-record packet on the main queue)
                     apply_event = self.region.raw_event()     # armed right in front of the launch that carries it (below)
@@ -336,9 +370,7 @@ class _ConvBnActNode(Node):
                     if apply_event is not None:
                         lib.tok_next_launch_event(apply_event)
                     try:
-                        _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale),
-                                                      ptr(self.shift), ptr(coef), int(self.relu), ptr(dy), ds_ptr,
-                                                      ds_acc, m, kp, st), 'tok_bn_bwd_apply')
+                        self._apply_bwd(lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp)
                     finally:
                         if apply_event is not None:
                             lib.tok_next_launch_event(None)   # never left armed for an unrelated later launch
@@ -591,9 +623,13 @@ STEM_POOLED_STATS = os.environ.get('TOK_STEM_POOLED_STATS', '1') != '0'   # Batc
 
 
 def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.BatchNorm2d] = None,
-                relu: bool = False, shortcut: Optional[TTensor] = None, pool: bool = False, defer_apply: bool = False) -> TTensor:
+                relu: bool = False, shortcut: Optional[TTensor] = None, pool: bool = False, defer_apply: bool = False,
+                act: Optional[str] = None) -> TTensor:
     """out = act(bn(conv(x)) (+ shortcut)).  `conv` is an nn.Conv2d or nn.Linear used purely as
     the parameter container (state_dict names stay those of the reference).
+    act=None: ReLU or no activation, as `relu` says.  act='hard_swish' (BatchNorm, no shortcut / pool / defer_apply): the
+    activation is hard-swish and `relu` is not looked at; the unit keeps y and no mask, its backward recomputes z from y, it never
+    becomes the fused unit 3 and its BatchNorm-backward sums are never taken by a consumer's data gradient.
     pool=True (BatchNorm + ReLU, no shortcut): out = maxpool3x3/s2/p1(act(bn(conv(x)))) with the activated map never
     stored (the ResNet stem when only the pooled map is consumed).
     defer_apply=True (BatchNorm, no activation, no shortcut — the last unit of an HRNet fuse path): the apply pass is NOT run;
@@ -602,6 +638,9 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     the unit's usual one (it never reads the normalised values of a unit without activation)."""
     if pool and (bn is None or not relu or shortcut is not None or x.data.dim() != 4):
         raise ValueError('conv_bn_act(pool=True): BatchNorm + ReLU on a 4-D input, no shortcut')
+    hswish = _check_act(act, bn, shortcut, pool, defer_apply)
+    if hswish:
+        relu = False
     await_ready(x, shortcut)
     lib, st = _C.lib(), stream_ptr()
     if isinstance(conv, nn.Linear):
@@ -622,7 +661,8 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     kp = pad8(k_real)
     if bn is not None and bn.num_features != k_real:
         raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {k_real}')
-    if (FUSE_UNIT3 and bn is not None and (relu == (shortcut is not None)) and not pool and isinstance(conv, nn.Conv2d)
+    if (FUSE_UNIT3 and bn is not None and not hswish and (relu == (shortcut is not None)) and not pool
+            and isinstance(conv, nn.Conv2d)
             and r == 1 and s == 1 and stride == 1 and pad == 0 and conv.bias is None and x.data.dim() == 4
             and x.c == x.cp and kp == k_real and x.cp <= 1024 and (shortcut is None or shortcut.cp == kp)
             and x.rows() >= UNIT3_MIN_ROWS and kp >= 2 * x.cp
@@ -680,6 +720,10 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
                 node.ypool = torch.empty_like(out_data)
             _C.check(lib.tok_bn_relu_maxpool_fwd(ptr(y), ptr(scale), ptr(shift), d.n, d.p, d.q, kp, ptr(out_data),
                                                  ptr(node.pool), ptr(node.ypool), st), 'tok_bn_relu_maxpool_fwd')
+        elif hswish:
+            out_data = torch.empty_like(y)
+            cs_part = None
+            _C.check(lib.tok_bn_hswish_fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, kp, st), 'tok_bn_hswish_fwd')
         else:
             out_data = torch.empty_like(y)
             if relu and region.grad_mode:
@@ -721,6 +765,8 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
         node.x, node.out, node.shortcut, node.y = x, out, shortcut, y
         node.conv, node.bn, node.desc, node.pk = conv, bn, d, pk
         node.relu, node.batch_stats = relu, batch_stats
+        if hswish:
+            node.act = act
         out.node = node
         node.sub_capable = False
         if x.requires_grad:
@@ -981,8 +1027,7 @@ class _DwConvBnActNode(_ConvBnActNode):
         if not (w_need or x_need):
             return
         dy = torch.empty_like(self.y)
-        _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift), ptr(coef),
-                                      int(self.relu), ptr(dy), None, 0, m, kp, st), 'tok_bn_bwd_apply')
+        self._apply_bwd(lib, st, g, mask, coef, dy, None, 0, m, kp)
         if w_need:
             ws_bytes = lib.tok_dwconv_wgrad_ws_bytes(n, h, w, c, k, stride)
             ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
@@ -996,10 +1041,14 @@ class _DwConvBnActNode(_ConvBnActNode):
                      'tok_dwconv_dgrad')
 
 
-def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True) -> TTensor:
+def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True,
+                  act: Optional[str] = None) -> TTensor:
     """out = act(bn(conv(x))) for a depthwise `conv` ([timm] create_conv2d(depthwise=True) + BatchNormAct2d of the MnasNet
-    blocks).  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
+    and MobileNetV3 blocks).  act=None: `relu` decides; act='hard_swish': as in conv_bn_act.  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
     rows tok_bn_finalize folds); eval mode uses the running statistics; track_running_stats=False uses batch statistics."""
+    hswish = _check_act(act, bn)
+    if hswish:
+        relu = False
     await_ready(x)
     _check_dwconv(conv, x)
     if bn.num_features != conv.out_channels:
@@ -1037,11 +1086,16 @@ def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2
                                      or bn.bias.requires_grad)
     mask = torch.empty((m, c // 8), dtype=torch.uint8, device=dev) if (relu and training) else None
     out_data = torch.empty_like(y)
-    _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), None, int(relu), ptr(out_data), ptr(mask), m, c, st),
-             'tok_bn_act_fwd')
+    if hswish:
+        _C.check(lib.tok_bn_hswish_fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, c, st), 'tok_bn_hswish_fwd')
+    else:
+        _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), None, int(relu), ptr(out_data), ptr(mask), m, c, st),
+                 'tok_bn_act_fwd')
     out = TTensor(out_data, c, requires_grad=bool(training))
     if training:
         node = _DwConvBnActNode()
+        if hswish:
+            node.act = act
         node.x, node.out, node.y, node.mask = x, out, y, mask
         node.conv, node.bn, node.relu, node.batch_stats = conv, bn, relu, batch_stats
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
@@ -1054,8 +1108,12 @@ def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2
 
 # ---- squeeze-excite (MnasNet-A1) -----------------------------------------------------------------------------------------
 
+SE_GATES = {'sigmoid': 0, 'hard_sigmoid': 1}      # gate_kind of tok_se_gate_fwd / _bwd
+
+
 class _SqueezeExciteNode(Node):
     needs_backward = True
+    gate_kind = 0
 
     def backward(self):
         g = self.out.grad
@@ -1071,9 +1129,14 @@ class _SqueezeExciteNode(Node):
         acc_bits = sum(acc << bit for bit, (_, _, acc) in enumerate(targets))
         dx, dx_acc = grad_target(x) if x.requires_grad else (None, 0)
         ws = torch.empty(lib.tok_se_ws_floats(n, h * w, c, rd), dtype=F32, device=g.device)
-        _C.check(lib.tok_se_bwd(ptr(g), ptr(x.data), n, h * w, c, c, rd, ptr(prm[0]), ptr(prm[2]), ptr(self.mean),
-                                ptr(self.hid), ptr(self.gate), *(ptr(t[1]) for t in targets), acc_bits, ptr(dx), dx_acc,
-                                ptr(ws), stream_ptr()), 'tok_se_bwd')
+        if self.gate_kind:
+            _C.check(lib.tok_se_gate_bwd(ptr(g), ptr(x.data), n, h * w, c, c, rd, self.gate_kind, ptr(prm[0]), ptr(prm[2]),
+                                         ptr(self.mean), ptr(self.hid), ptr(self.gate), *(ptr(t[1]) for t in targets), acc_bits,
+                                         ptr(dx), dx_acc, ptr(ws), stream_ptr()), 'tok_se_gate_bwd')
+        else:
+            _C.check(lib.tok_se_bwd(ptr(g), ptr(x.data), n, h * w, c, c, rd, ptr(prm[0]), ptr(prm[2]), ptr(self.mean),
+                                    ptr(self.hid), ptr(self.gate), *(ptr(t[1]) for t in targets), acc_bits, ptr(dx), dx_acc,
+                                    ptr(ws), stream_ptr()), 'tok_se_bwd')
         for p, slot, acc in targets:
             if slot is not None:
                 PG.commit(p, slot, acc)
@@ -1084,9 +1147,13 @@ class _SqueezeExciteNode(Node):
         self.x = self.out = self.mean = self.hid = self.gate = None
 
 
-def squeeze_excite(region: Region, x: TTensor, se: nn.Module) -> TTensor:
-    """x * sigmoid(conv_expand(relu(conv_reduce(mean_hw(x)))))  ([timm] efficientnet_blocks.SqueezeExcite with ReLU and the
-    sigmoid gate).  `se` holds conv_reduce / conv_expand (1x1, with bias) as parameter containers."""
+def squeeze_excite(region: Region, x: TTensor, se: nn.Module, gate: str = 'sigmoid') -> TTensor:
+    """x * gate(conv_expand(relu(conv_reduce(mean_hw(x)))))  ([timm] efficientnet_blocks.SqueezeExcite with ReLU inside and
+    the 'sigmoid' (MnasNet) or 'hard_sigmoid' (MobileNetV3) gate).  `se` holds conv_reduce / conv_expand (1x1, with bias) as
+    parameter containers."""
+    if gate not in SE_GATES:
+        raise NotImplementedError(f'torchok_amd squeeze-excite gate {gate!r}: one of {sorted(SE_GATES)}')
+    gate_kind = SE_GATES[gate]
     await_ready(x)
     red, exp = se.conv_reduce, se.conv_expand
     if x.data.dim() != 4 or x.c != x.cp or red.in_channels != x.c or exp.out_channels != x.c \
@@ -1102,17 +1169,23 @@ def squeeze_excite(region: Region, x: TTensor, se: nn.Module) -> TTensor:
         raise NotImplementedError('torchok_amd squeeze-excite: dense 1x1 weights')
     mean = torch.empty((n, c), dtype=F32, device=dev)
     hid = torch.empty((n, rd), dtype=F32, device=dev)
-    gate = torch.empty((n, c), dtype=F32, device=dev)
+    gate_v = torch.empty((n, c), dtype=F32, device=dev)
     ws = torch.empty(lib.tok_se_ws_floats(n, h * w, c, rd), dtype=F32, device=dev)
-    _C.check(lib.tok_se_fwd(ptr(x.data), n, h * w, c, c, rd, ptr(w1), ptr(red.bias), ptr(w2), ptr(exp.bias), ptr(mean),
-                            ptr(hid), ptr(gate), ptr(ws), st), 'tok_se_fwd')
+    if gate_kind:
+        _C.check(lib.tok_se_gate_fwd(ptr(x.data), n, h * w, c, c, rd, gate_kind, ptr(w1), ptr(red.bias), ptr(w2), ptr(exp.bias),
+                                     ptr(mean), ptr(hid), ptr(gate_v), ptr(ws), st), 'tok_se_gate_fwd')
+    else:
+        _C.check(lib.tok_se_fwd(ptr(x.data), n, h * w, c, c, rd, ptr(w1), ptr(red.bias), ptr(w2), ptr(exp.bias), ptr(mean),
+                                ptr(hid), ptr(gate_v), ptr(ws), st), 'tok_se_fwd')
     out_data = torch.empty_like(x.data)
-    _C.check(lib.tok_channel_scale(ptr(x.data), ptr(gate), ptr(out_data), 0, n, h * w, c, c, st), 'tok_channel_scale')
+    _C.check(lib.tok_channel_scale(ptr(x.data), ptr(gate_v), ptr(out_data), 0, n, h * w, c, c, st), 'tok_channel_scale')
     req = region.grad_mode and (x.requires_grad or any(p.requires_grad for p in se.parameters()))
     out = TTensor(out_data, c, requires_grad=bool(req))
     if req:
         node = _SqueezeExciteNode()
-        node.x, node.out, node.se, node.mean, node.hid, node.gate = x, out, se, mean, hid, gate
+        node.x, node.out, node.se, node.mean, node.hid, node.gate = x, out, se, mean, hid, gate_v
+        if gate_kind:
+            node.gate_kind = gate_kind
         out.node = node
         if x.requires_grad:
             x.uses += 1

@@ -8,8 +8,8 @@ Mirrors the reference wiring ``torchok/models/backbones/efficientnet.py``: ``Eff
 Each ``conv -> bn -> act`` group is one engine unit: the 1x1 expansion / projection, the stem and the head run on
 ``conv_bn_act`` (the projection of a block with a skip connection adds the block input before nothing else: ``relu=False,
 shortcut=x``), the depthwise convolution on ``dwconv_bn_act`` and the squeeze-excite on ``squeeze_excite``.  Only what the
-MnasNet family needs is built: ReLU, BatchNorm, 'ds' / 'ir' blocks; the SiLU / ReLU6 / hard-swish families (EfficientNet,
-MobileNet, FBNet) stay unregistered.
+MnasNet family needs is built here: ReLU, BatchNorm, 'ds' / 'ir' blocks; the SiLU / ReLU6 families (EfficientNet,
+MobileNetV2, FBNet) stay unregistered.  The hard-swish family (MobileNetV3) has its own file, ``mobilenetv3.py``.
 """
 import math
 import re
