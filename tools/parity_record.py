@@ -8,7 +8,9 @@ single-unit HIP-vs-autocast distance (the tests gate it at 1e-2; VERDICT r02 ask
 
 Records of the kernel contract tests (helpers.assert_bounded) carry `err_over_bound` instead: the worst |err| / bound of a tensor
 against its fp64 reference, bound derived in the test (<= 1 passes).  They get their own median / maximum per test and the
-largest one at the top; a file made of such records only says so in `source` and leaves the relative-L2 fields out."""
+largest one at the top; a file made of such records only says so in `source` and leaves the relative-L2 fields out.
+`row_rel_err` records (the worst per-row error of a gradient against max(|ref row|, |magnitude row| / 4), gated at 3e-2 in the
+test) belong to the same family and are summarised the same way."""
 import json
 import statistics
 import sys
@@ -29,10 +31,11 @@ def main():
     out = OrderedDict()
     unit_worst = (0.0, None)
     bound_worst = (0.0, None)         # contract tests: largest |err| / derived bound
+    row_worst = (0.0, None)           # contract tests: largest per-row relative error of a gradient
     real_worst = (0.0, None)          # units at the real widths (tests/test_units_real_gpu.py): largest HIP-vs-fp32 / autocast-vs-fp32
     for t, tensors in tests.items():
         summ = {'tensors': len(tensors)}
-        for k in ('hip_vs_autocast', 'hip_vs_fp32', 'autocast_vs_fp32', 'err_over_bound'):
+        for k in ('hip_vs_autocast', 'hip_vs_fp32', 'autocast_vs_fp32', 'err_over_bound', 'row_rel_err'):
             v = [x[k] for x in tensors.values() if k in x]
             if v:
                 summ[k] = {'median': statistics.median(v), 'max': max(v)}
@@ -40,6 +43,8 @@ def main():
         for name, x in tensors.items():
             if x.get('err_over_bound', 0) > bound_worst[0]:
                 bound_worst = (x['err_over_bound'], f'{t} :: {name}')
+            if x.get('row_rel_err', 0) > row_worst[0]:
+                row_worst = (x['row_rel_err'], f'{t} :: {name}')
         if t.startswith('units_real/'):
             for name, x in tensors.items():
                 if x.get('autocast_vs_fp32', 0) > 0 and 'hip_vs_fp32' in x:
@@ -60,10 +65,17 @@ def main():
                              'shortcut / bias in fp32 and round once where torch rounds each tensor first. autocast_vs_fp32 next to every entry is the '
                              'same quantity for torch itself.', 'tests': out}
     bounded = {'value': bound_worst[0], 'where': bound_worst[1]}
-    if all('err_over_bound' in x for v in tests.values() for x in v.values()):
+    if all('err_over_bound' in x or 'row_rel_err' in x for v in tests.values() for x in v.values()):
         doc = {'source': 'kernel contract tests (python -m pytest tests -m gpu on MI355X); every entry is err_over_bound = worst '
-                         '|err| / bound over a tensor against its fp64 reference, the bound derived in the test (<= 1 passes)',
-               'largest_err_over_bound': bounded, 'tests': out}
+                         '|err| / bound over a tensor against its fp64 reference, the bound derived in the test (<= 1 passes), or '
+                         'row_rel_err = worst per-row error of a gradient against max(|ref row|, |magnitude row| / 4) (the test '
+                         'gates it at 3e-2)',
+               'note': 'a bound whose first term is one bf16 rounding of the result (2^-8 |ref|) is used up entirely by an exact '
+                       'kernel whenever a result falls half way between two bf16 values: err_over_bound of 0.9 - 1.0 on a bf16 '
+                       'output (LayerNorm out / dx) is that rounding, not a near-failure; the margin of the accumulation term is '
+                       'what the CPU tests of the references establish (an fp32 run stays inside half of it)',
+               'largest_err_over_bound': bounded, 'largest_row_rel_err': {'value': row_worst[0], 'where': row_worst[1]},
+               'tests': out}
     elif bound_worst[1] is not None:
         doc['largest_err_over_bound'] = bounded
     with open(dst, 'w') as f:

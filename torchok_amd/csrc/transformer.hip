@@ -1174,12 +1174,17 @@ inline int blocks_for(size_t total) {
   return (int)(b > 65536 ? 65536 : (b < 1 ? 1 : b));
 }
 
-bool fill_attn(AttnArgs& a, int B, int H, int W, int C, int heads, int ws, int shift, int ld) {
-  if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || ws <= 0 || C != heads * HD || H % ws || W % ws || shift < 0 ||
-      shift >= ws || ld < 3 * C || (ld & 7)) return false;
+// nullptr when the geometry is accepted, otherwise the reason of the refusal (what tok_last_error() reports)
+const char* fill_attn(AttnArgs& a, int B, int H, int W, int C, int heads, int ws, int shift, int ld) {
+  if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || ws <= 0) return "batch, h, w, heads and ws must be positive";
+  if (C != heads * HD) return "c must be heads * 32 (head_dim 32)";
+  if (H % ws || W % ws) return "h and w must be multiples of the window";
+  if (shift < 0 || shift >= ws) return "shift must be in [0, ws)";
+  if (ld < 3 * C) return "ld must be at least 3c";
+  if (ld & 7) return "ld must be a multiple of 8";
   a.B = B; a.H = H; a.W = W; a.C = C; a.heads = heads; a.ws = ws; a.shift = shift;
   a.nWx = W / ws; a.nW = (H / ws) * a.nWx; a.N = ws * ws; a.ld = ld; a.plain = 0;
-  return true;
+  return nullptr;
 }
 
 }  // namespace
@@ -1310,8 +1315,9 @@ extern "C" int tok_window_attn_fwd(const void* qkv, int batch, int h, int w, int
                                    const float* logit_scale, const float* bias, const float* mask, void* out,
                                    float* lse, void* stream) {
   AttnArgs a;
-  TOK_CHECK_ARG(qkv && out && lse && fill_attn(a, batch, h, w, c, heads, ws, shift, ld),
-                "tok_window_attn_fwd: bad args (head_dim must be 32, h/w multiples of the window)");
+  TOK_CHECK_ARG(qkv && out && lse, "tok_window_attn_fwd: bad args (null qkv / out / lse)");
+  const char* why = fill_attn(a, batch, h, w, c, heads, ws, shift, ld);
+  TOK_CHECK_ARG(why == nullptr, "tok_window_attn_fwd: bad args: %s", why);
   TOK_CHECK_ARG((logit_scale == nullptr) == (bias == nullptr), "tok_window_attn_fwd: logit_scale and bias go together");
   a.plain = logit_scale == nullptr;
   TOK_CHECK_ARG(!a.plain || (a.N <= 64 && !mask && shift == 0),
@@ -1341,7 +1347,7 @@ extern "C" int tok_window_attn_fwd(const void* qkv, int batch, int h, int w, int
 
 extern "C" int tok_window_attn_bwd_rows(int batch, int h, int w, int heads, int ws) {
   AttnArgs a;
-  if (!fill_attn(a, batch, h, w, heads * HD, heads, ws, 0, 3 * heads * HD)) return TOK_ERR_INVALID;
+  if (fill_attn(a, batch, h, w, heads * HD, heads, ws, 0, 3 * heads * HD) != nullptr) return TOK_ERR_INVALID;
   if (a.N <= 64) return tok_cdiv(batch, attn_bpw(a)) * a.nW;
   return batch * a.nW;
 }
@@ -1350,11 +1356,14 @@ extern "C" int tok_window_attn_bwd(const void* qkv, const void* dout, int batch,
                                    int shift, int ld, const float* logit_scale, const float* bias, const float* mask,
                                    const float* lse, void* dqkv, float* ds_scratch, float* dscale_part, void* stream) {
   AttnArgs a;
-  TOK_CHECK_ARG(qkv && dout && lse && dqkv && fill_attn(a, batch, h, w, c, heads, ws, shift, ld),
-                "tok_window_attn_bwd: bad args");
+  TOK_CHECK_ARG(qkv && dout && lse && dqkv, "tok_window_attn_bwd: bad args (null qkv / dout / lse / dqkv)");
+  const char* why = fill_attn(a, batch, h, w, c, heads, ws, shift, ld);
+  TOK_CHECK_ARG(why == nullptr, "tok_window_attn_bwd: bad args: %s", why);
   a.plain = logit_scale == nullptr;
-  TOK_CHECK_ARG(a.plain ? (!bias && !mask && shift == 0 && a.N <= 64) : (bias && ds_scratch && dscale_part),
-                "tok_window_attn_bwd: bad args (plain mode: no bias / mask / shift, windows of up to 64 tokens)");
+  TOK_CHECK_ARG(a.plain || bias, "tok_window_attn_bwd: logit_scale and bias go together");
+  TOK_CHECK_ARG(a.plain || (ds_scratch && dscale_part), "tok_window_attn_bwd: SwinV2 mode needs ds_scratch and dscale_part");
+  TOK_CHECK_ARG(!a.plain || (!bias && !mask && shift == 0 && a.N <= 64),
+                "tok_window_attn_bwd: the plain mode covers unshifted windows of up to 64 tokens (no bias / mask)");
   if (a.N <= 64) {
     const int bpw = attn_bpw(a);
     const int waves = tok_cdiv(batch, bpw) * a.nW * heads;
