@@ -52,13 +52,17 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* __restrict_
   const int cgl = tid % cge, rl = tid / cge;
   if (rl >= rpb && csum == nullptr) return;
   const int cg_total = C >> 3;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
+  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
+  for (int cg = cgl; cg < cg_end; cg += cge) {
+    const bool live = cg < cg_total;
     float sc[8], sh[8], cs[8];
-    load8f(scale + cg * 8, sc);
-    load8f(shift + cg * 8, sh);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) cs[e] = 0.f;
-    if (rl < rpb)
+    for (int e = 0; e < 8; ++e) { sc[e] = 0.f; sh[e] = 0.f; cs[e] = 0.f; }
+    if (live) {
+      load8f(scale + cg * 8, sc);
+      load8f(shift + cg * 8, sh);
+    }
+    if (rl < rpb && live)
     for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
       const size_t off = (size_t)m * C + cg * 8;
       const bf16x8 v = ldg16(y + off);
@@ -97,7 +101,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* __restrict_
 #pragma unroll
       for (int e = 0; e < 8; ++e) cred[tid][e] = cs[e];
       __syncthreads();
-      if (rl == 0) {
+      if (rl == 0 && live) {
         for (int r = 1; r < rpb; ++r)
 #pragma unroll
           for (int e = 0; e < 8; ++e) cs[e] += cred[r * cge + cgl][e];
@@ -116,11 +120,13 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const bf16* __restrict__ 
   const int tid = threadIdx.x;
   const int cgl = tid % cge, rl = tid / cge;
   const int cg_total = C >> 3;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
+  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
+  for (int cg = cgl; cg < cg_end; cg += cge) {
+    const bool live = cg < cg_total;
     float s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb) {
+    if (rl < rpb && live) {
       for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
         const bf16x8 v = ldg16(y + (size_t)m * C + cg * 8);
 #pragma unroll
@@ -130,7 +136,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
     __syncthreads();
-    if (rl == 0) {
+    if (rl == 0 && live) {
       for (int r = 1; r < rpb; ++r)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
@@ -288,11 +294,13 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
   const int tid = threadIdx.x;
   const int cgl = tid % cge, rl = tid / cge;
   const int cg_total = C >> 3;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
+  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
+  for (int cg = cgl; cg < cg_end; cg += cge) {
+    const bool live = cg < cg_total;
     float s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb) {
+    if (rl < rpb && live) {
       float sc[8], sh[8], mu[8], rs[8];
       load8f(scale + cg * 8, sc);
       load8f(shift + cg * 8, sh);
@@ -326,7 +334,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
 #pragma unroll
     for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
     __syncthreads();
-    if (rl == 0) {
+    if (rl == 0 && live) {
       for (int r = 1; r < rpb; ++r)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
@@ -559,11 +567,13 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const bf16* __restrict
   const int tid = threadIdx.x;
   const int cgl = tid % cge, rl = tid / cge;
   const int cg_total = C >> 3;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
+  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
+  for (int cg = cgl; cg < cg_end; cg += cge) {
+    const bool live = cg < cg_total;
     float s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb) {
+    if (rl < rpb && live) {
       float sc[8], sh[8], a[8], b[8], c3[8];
       load8f(scale + cg * 8, sc);
       load8f(shift + cg * 8, sh);
@@ -607,7 +617,7 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const bf16* __restrict
 #pragma unroll
       for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
       __syncthreads();
-      if (rl == 0) {
+      if (rl == 0 && live) {
         for (int r = 1; r < rpb; ++r)
 #pragma unroll
           for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
@@ -638,11 +648,13 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_pooled_kernel(const bf
   const int tid = threadIdx.x;
   const int cgl = tid % cge, rl = tid / cge;
   const int cg_total = C >> 3;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
+  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
+  for (int cg = cgl; cg < cg_end; cg += cge) {
+    const bool live = cg < cg_total;
     float s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb) {
+    if (rl < rpb && live) {
       float mu[8], rs[8];
       load8f(mean + cg * 8, mu);
       load8f(rstd + cg * 8, rs);
@@ -660,7 +672,7 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_pooled_kernel(const bf
 #pragma unroll
     for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
     __syncthreads();
-    if (rl == 0) {
+    if (rl == 0 && live) {
       for (int r = 1; r < rpb; ++r)
 #pragma unroll
         for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
@@ -783,7 +795,7 @@ extern "C" int tok_bn_bwd_finalize(const float* partial, int rows, int64_t m, in
                                    float* coef, int accumulate, int dzy_form, void* stream) {
   TOK_CHECK_ARG(partial && gamma && mean && rstd && coef, "tok_bn_bwd_finalize: null pointer");
   if (tok_dbg_skip(1)) return TOK_OK;
-  TOK_CHECK_ARG(c > 0 && c_real > 0 && c_real <= c, "tok_bn_bwd_finalize: bad sizes");
+  TOK_CHECK_ARG(rows > 0 && m > 0 && c > 0 && c_real > 0 && c_real <= c, "tok_bn_bwd_finalize: bad sizes");
   if (c >= 512)
     hipLaunchKernelGGL(bn_bwd_finalize_kernel<16>, dim3((c + 15) / 16), dim3(256), 0, tok_stream(stream), partial,
                        rows, 1.0 / (double)m, c, c_real, gamma, mean, rstd, dgamma, dbeta, coef, accumulate, dzy_form);
