@@ -701,6 +701,40 @@ int tok_global_attn_fwd(const void* qkv, int ldq, int batch, int n, int heads, i
 size_t tok_global_attn_bwd_ws_bytes(int batch, int n, int heads);
 int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse, int batch, int n,
                         int heads, int head_dim, void* dqkv, int ldd, void* ws, size_t ws_bytes, void* stream);
+/* The same attention with an additive bias on the scaled logits (BEiT: [timm 0.6.13] beit.Attention):
+ *   O = softmax(Q K^T * 64^-0.5 + bias[h]) V.  bias fp32 [heads][n][ldb], shared by every image, 16-byte aligned, ldb >= n and
+ *   ldb % 4 == 0; columns >= n of a bias row are never read as values.  lse is the log-sum-exp of the biased logits.  Every other
+ *   argument rule is that of tok_global_attn_fwd / _bwd; an all-zero bias gives their bits.
+ * tok_global_attn_bias_bwd: dq / dk / dv from P recomputed with the bias, and (dbias != NULL)
+ *   dbias[h][i][j] (= | += with dbias_accumulate) sum_b P_b[i][j] (dP_b[i][j] - delta_b[i]), fp32 [heads][n][ldb], columns >= n
+ *   not written.  The images are split into tok_global_attn_bias_bwd_chunks(...) chunks, summed in image order inside a chunk and
+ *   folded in chunk order: no float atomics, bit-reproducible.  ws: tok_global_attn_bias_bwd_ws_bytes(...) bytes; with
+ *   dbias == NULL the chunk partials are not needed and tok_global_attn_bwd_ws_bytes(...) bytes are enough.                   */
+int tok_global_attn_bias_fwd(const void* qkv, int ldq, const float* bias, int ldb, int batch, int n, int heads, int head_dim,
+                             void* out, int ldo, float* lse, void* stream);
+int tok_global_attn_bias_bwd_chunks(int batch, int n, int heads);
+size_t tok_global_attn_bias_bwd_ws_bytes(int batch, int n, int heads, int ldb);
+int tok_global_attn_bias_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
+                             const float* bias, int ldb, int batch, int n, int heads, int head_dim, void* dqkv, int ldd,
+                             float* dbias, int dbias_accumulate, void* ws, size_t ws_bytes, void* stream);
+/* Relative position bias of BEiT: bias[h][i][j] = table[index[i][j]][h] (exact gather), table fp32 [table_rows][heads], index
+ * int64 [n][n] with every entry in [0, table_rows) (the caller checks), bias fp32 [heads][n][ldb] (columns >= n not written).
+ * tok_relpos_bias_bwd: dtable[t][h] (= | +=) sum over {(i, j): index[i][j] == t} of dbias[h][i][j], in a fixed order;
+ * 1 <= heads <= TOK_RELPOS_MAX_HEADS.                                                                                         */
+#define TOK_RELPOS_MAX_HEADS 32
+int tok_relpos_bias_fwd(const float* table, const int64_t* index, int heads, int n_tokens, float* bias, int ldb, void* stream);
+int tok_relpos_bias_bwd(const float* dbias, int ldb, const int64_t* index, int heads, int n_tokens, int table_rows,
+                        float* dtable, int accumulate, void* stream);
+/* LayerScale residual ([timm 0.6.13] beit.Block: x + drop_path(gamma * f(x))) on bf16 rows [rows][d], d % 8 == 0:
+ *   out = bf16(x + s * gamma[c] * a), s = row_scale[row / rows_per_sample] (row_scale NULL: 1), gamma fp32 [d].
+ * tok_layer_scale_bwd: da (= | +=, nullable) bf16(s * gamma * dout); dgamma[c] (= | +=, nullable) sum_rows s * dout * a through
+ *   partial fp32 [tok_layer_scale_bwd_rows(rows, d)][d] per-block rows folded in a fixed order.  dx = dout needs no kernel.   */
+int tok_layer_scale_fwd(const void* x, const void* a, const float* gamma, const float* row_scale, int rows_per_sample, void* out,
+                        int64_t rows, int d, void* stream);
+int tok_layer_scale_bwd_rows(int64_t rows, int d);
+int tok_layer_scale_bwd(const void* dout, const void* a, const float* gamma, const float* row_scale, int rows_per_sample,
+                        void* da, int da_accumulate, float* dgamma, int dgamma_accumulate, float* partial, int64_t rows, int d,
+                        void* stream);
 /* Patch embedding as a GEMM: img NHWC bf16 [n][h][w][4] (3 channels zero-padded to 4) -> rows bf16 [n*(h/p)*(w/p)][p*p*4],
  * element (py, px, c) of a row at (py*p + px)*4 + c — the k = p, stride = p convolution is then a 1x1 layer against the
  * [D][p][p][4] weight pack.  h, w multiples of p.                                                                             */

@@ -192,6 +192,16 @@ PROTOTYPES = {
     'tok_global_attn_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     'tok_global_attn_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'tok_global_attn_bwd': (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    'tok_global_attn_bias_fwd': (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
+    'tok_global_attn_bias_bwd_chunks': (c_int, [c_int, c_int, c_int]),
+    'tok_global_attn_bias_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'tok_global_attn_bias_bwd': (c_int, [_P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P,
+                                         c_int, _P, c_size_t, _P]),
+    'tok_relpos_bias_fwd': (c_int, [_P, _P, c_int, c_int, _P, c_int, _P]),
+    'tok_relpos_bias_bwd': (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, _P]),
+    'tok_layer_scale_fwd': (c_int, [_P, _P, _P, _P, c_int, _P, c_int64, c_int, _P]),
+    'tok_layer_scale_bwd_rows': (c_int, [c_int64, c_int]),
+    'tok_layer_scale_bwd': (c_int, [_P, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, c_int64, c_int, _P]),
     'tok_patch_gather': (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     'tok_vit_embed_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     'tok_vit_embed_bwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P]),

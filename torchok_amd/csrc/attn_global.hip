@@ -9,6 +9,8 @@
 // Backward: delta = rowsum(dO o O) (pre-pass); dK / dV per (image, head, 64-key tile), dQ per (image, head, 64-query tile), each
 //           recomputing P from Q, K and the LSE.  Every output element is written by exactly one lane and every sum runs in a fixed
 //           order: no float atomics, bit-reproducible run to run.
+// Bias    : BEiT's relative-position bias ([timm 0.6.13] beit.Attention) is one more template argument of the same kernels:
+//           softmax(q k^T * 64^-0.5 + bias[h]); its gradient is a reduction over the images (gattn_dbias_kernel).
 #include "tok_common.h"
 
 namespace {
@@ -46,8 +48,12 @@ __device__ __forceinline__ float sum16(float v) {
   return v;
 }
 
+// BIAS: logits get + bias[h][query][key] (fp32, row pitch ldb, shared by every image); columns >= N of a bias row and rows of
+// queries >= N are never loaded.  Without it the kernel is the one the un-biased entry point has always launched.
+template <bool BIAS>
 __global__ __launch_bounds__(256) void gattn_fwd_kernel(const bf16* __restrict__ qkv, int ldq, int N, int H,
-                                                        bf16* __restrict__ out, int ldo, float* __restrict__ lse) {
+                                                        bf16* __restrict__ out, int ldo, float* __restrict__ lse,
+                                                        const float* __restrict__ bias, int ldb) {
   __shared__ __attribute__((aligned(16))) bf16 ks[TL * PT];        // K [key][d]
   __shared__ __attribute__((aligned(16))) bf16 vt[HD * PT];        // V^T [d][key]
   __shared__ __attribute__((aligned(16))) bf16 ps[4][16 * PT];     // per wave: P [query][key]
@@ -88,7 +94,14 @@ __global__ __launch_bounds__(256) void gattn_fwd_kernel(const bf16* __restrict__
       float v[4], mx = -INFINITY;
 #pragma unroll
       for (int kj = 0; kj < 4; ++kj) {
-        v[kj] = (k0 + kj * 16 + l15 < N) ? s[kj][r] * sc : -INFINITY;
+        const int key = k0 + kj * 16 + l15;
+        if constexpr (BIAS) {
+          const int q = q0 + 4 * g + r;
+          const float bl = (key < N && q < N) ? bias[((size_t)h * N + q) * ldb + key] * LOG2E : 0.f;
+          v[kj] = (key < N) ? s[kj][r] * sc + bl : -INFINITY;
+        } else {
+          v[kj] = (key < N) ? s[kj][r] * sc : -INFINITY;
+        }
         mx = fmaxf(mx, v[kj]);
       }
       const float mn = fmaxf(m[r], max16(mx));           // finite: key k0 < N is in every tile
@@ -148,9 +161,11 @@ __global__ __launch_bounds__(256) void gattn_delta_kernel(const bf16* __restrict
 }
 
 // dK, dV of 64 keys: a wave owns 16 keys and walks every query tile
+template <bool BIAS>
 __global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__ qkv, int ldq, const bf16* __restrict__ dout,
                                                         int ldo, const float* __restrict__ lse, const float* __restrict__ delta,
-                                                        int N, int H, bf16* __restrict__ dqkv, int ldd) {
+                                                        int N, int H, bf16* __restrict__ dqkv, int ldd,
+                                                        const float* __restrict__ bias, int ldb) {
   __shared__ __attribute__((aligned(16))) bf16 qs[TL * PT];       // Q [query][d]
   __shared__ __attribute__((aligned(16))) bf16 qt[HD * PT];       // Q^T [d][query]
   __shared__ __attribute__((aligned(16))) bf16 dos[TL * PT];      // dO [query][d]
@@ -203,9 +218,20 @@ __global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__
     for (int qj = 0; qj < 4; ++qj) {
       const int ql = qj * 16 + l15;
       const float lq = lsl[ql], dq = dl[ql];
+      float lqb[4] = {lq, lq, lq, lq};
+      if constexpr (BIAS) {
+        // keys k0 + 4g ... + 3 of query row q0 + ql: one aligned 16-byte load (ldb % 4 == 0 keeps it inside the row)
+        const int q = q0 + ql, kb = k0 + 4 * g;
+        if (q < N && kb < N) {
+          const float4 b4 = *reinterpret_cast<const float4*>(bias + ((size_t)h * N + q) * ldb + kb);
+          const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) lqb[r] = kb + r < N ? lq - bv[r] * LOG2E : lq;
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = exp2f(st[qj][r] * sc - lq);
+        const float p = exp2f(st[qj][r] * sc - (BIAS ? lqb[r] : lq));
         ws[wv][(4 * g + r) * PT + ql] = f2bf(p);
         dsv[qj][r] = p * (dpt[qj][r] - dq);
       }
@@ -246,9 +272,11 @@ __global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__
 }
 
 // dQ of 64 queries: a wave owns 16 queries and walks every key tile
+template <bool BIAS>
 __global__ __launch_bounds__(256) void gattn_dq_kernel(const bf16* __restrict__ qkv, int ldq, const bf16* __restrict__ dout,
                                                        int ldo, const float* __restrict__ lse, const float* __restrict__ delta,
-                                                       int N, int H, bf16* __restrict__ dqkv, int ldd) {
+                                                       int N, int H, bf16* __restrict__ dqkv, int ldd,
+                                                       const float* __restrict__ bias, int ldb) {
   __shared__ __attribute__((aligned(16))) bf16 ks[TL * PT];       // K [key][d]
   __shared__ __attribute__((aligned(16))) bf16 kt[HD * PT];       // K^T [d][key]
   __shared__ __attribute__((aligned(16))) bf16 vs[TL * PT];       // V [key][d]
@@ -297,10 +325,16 @@ __global__ __launch_bounds__(256) void gattn_dq_kernel(const bf16* __restrict__ 
     // element (kj, r): query q0 + 4g + r, key k0 + 16 kj + l15
 #pragma unroll
     for (int kj = 0; kj < 4; ++kj) {
-      const bool live = k0 + kj * 16 + l15 < N;
+      const int key = k0 + kj * 16 + l15;
+      const bool live = key < N;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = live ? exp2f(s[kj][r] * sc - lr[r]) : 0.f;
+        float lb = lr[r];
+        if constexpr (BIAS) {
+          const int q = q0 + 4 * g + r;
+          if (live && q < N) lb = lr[r] - bias[((size_t)h * N + q) * ldb + key] * LOG2E;
+        }
+        const float p = live ? exp2f(s[kj][r] * sc - lb) : 0.f;
         ws[wv][(4 * g + r) * PT + kj * 16 + l15] = f2bf(p * (dp[kj][r] - dr[r]));
       }
     }
@@ -321,6 +355,99 @@ __global__ __launch_bounds__(256) void gattn_dq_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int dj = 0; dj < 4; ++dj) row[dj * 16 + l15] = f2bf(dq[dj][r] * SCALE);
   }
+}
+
+// d(bias)[h][i][j] = sum over images of dS_b[i][j] = P_b (dP_b - delta_b): one workgroup per (64-query x 64-key tile, head, chunk
+// of images), a wave owns 16 queries.  The workgroup walks the images of its chunk in image order, recomputes S and dP of its tile
+// (16 MFMA per wave and image) and keeps the fp32 sum in registers; the bias values of the tile are loaded once.  Partials
+// [chunk][h][N][ldb] are folded in chunk order by gattn_dbias_fold_kernel: no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void gattn_dbias_kernel(const bf16* __restrict__ qkv, int ldq, const bf16* __restrict__ dout,
+                                                          int ldo, const float* __restrict__ lse, const float* __restrict__ delta,
+                                                          const float* __restrict__ bias, int ldb, int B, int N, int H,
+                                                          int per_chunk, float* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) bf16 ks[TL * PT];       // K [key][d]
+  __shared__ __attribute__((aligned(16))) bf16 vs[TL * PT];       // V [key][d]
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l15 = lane & 15, g = lane >> 4;
+  const int nt = (N + TL - 1) / TL;
+  const int h = blockIdx.y, C = H * HD;
+  const int q0 = (blockIdx.x / nt) * TL + wv * 16, k0 = (blockIdx.x % nt) * TL;
+  const int b_lo = blockIdx.z * per_chunk, b_hi = min(B, b_lo + per_chunk);
+  float bl[4][4];
+#pragma unroll
+  for (int kj = 0; kj < 4; ++kj)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = q0 + 4 * g + r, key = k0 + kj * 16 + l15;
+      bl[kj][r] = (q < N && key < N) ? bias[((size_t)h * N + q) * ldb + key] * LOG2E : 0.f;
+    }
+  f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const float sc = SCALE * LOG2E;
+  for (int b = b_lo; b < b_hi; ++b) {
+    const bf16* base = qkv + (size_t)b * N * ldq;
+    const float* lrow = lse + ((size_t)b * H + h) * N;
+    const float* drow = delta + ((size_t)b * H + h) * N;
+    __syncthreads();                                    // the previous image's tiles have been consumed by every wave
+    stage_tile(base, ldq, C + h * HD, k0, N, ks, nullptr);
+    stage_tile(base, ldq, 2 * C + h * HD, k0, N, vs, nullptr);
+    bf16x8 qf[2], df[2];
+    {
+      const int qr = q0 + l15;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        qf[t] = qr < N ? ldg16(base + (size_t)qr * ldq + h * HD + 32 * t + 8 * g) : zero8();
+        df[t] = qr < N ? ldg16(dout + ((size_t)b * N + qr) * ldo + h * HD + 32 * t + 8 * g) : zero8();
+      }
+    }
+    float lr[4], dr[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = q0 + 4 * g + r;
+      lr[r] = q < N ? lrow[q] * LOG2E : INFINITY;
+      dr[r] = q < N ? drow[q] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kj = 0; kj < 4; ++kj) {
+      f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f}, dp = s;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t], lds8(ks + (kj * 16 + l15) * PT + 32 * t + 8 * g), s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[t], lds8(vs + (kj * 16 + l15) * PT + 32 * t + 8 * g), dp, 0, 0, 0);
+      }
+      const bool live = k0 + kj * 16 + l15 < N;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = live ? exp2f(s[r] * sc - (lr[r] - bl[kj][r])) : 0.f;
+        acc[kj][r] += p * (dp[r] - dr[r]);
+      }
+    }
+  }
+  float* dst = part + (size_t)blockIdx.z * H * N * ldb;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int q = q0 + 4 * g + r;
+    if (q >= N) continue;
+#pragma unroll
+    for (int kj = 0; kj < 4; ++kj) {
+      const int key = k0 + kj * 16 + l15;
+      if (key < N) dst[((size_t)h * N + q) * ldb + key] = acc[kj][r];
+    }
+  }
+}
+
+// dbias[h][i][j] (=|+=) sum_chunk part[chunk][h][i][j], chunk order; columns >= N of a row are not touched
+__global__ __launch_bounds__(256) void gattn_dbias_fold_kernel(const float* __restrict__ part, int chunks, int H, int N, int ldb,
+                                                               float* __restrict__ dbias, int accumulate) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)H * N * N) return;
+  const int j = (int)(i % N);
+  const int64_t row = i / N;
+  float s = 0.f;
+  for (int c = 0; c < chunks; ++c) s += part[((size_t)c * H * N + row) * ldb + j];
+  float* o = dbias + row * ldb + j;
+  *o = accumulate ? *o + s : s;
 }
 
 // ---- embedding helpers ------------------------------------------------------------------------------------------------------
@@ -439,9 +566,24 @@ extern "C" int tok_global_attn_fwd(const void* qkv, int ldq, int batch, int n, i
                                    float* lse, void* stream) {
   GA_CHECK_GEO("tok_global_attn_fwd");
   TOK_CHECK_ARG(qkv && out && lse, "tok_global_attn_fwd: null pointer");
-  hipLaunchKernelGGL(gattn_fwd_kernel, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)qkv, ldq, n, heads, (bf16*)out, ldo, lse);
+  hipLaunchKernelGGL(gattn_fwd_kernel<false>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)qkv, ldq, n, heads, (bf16*)out, ldo, lse, (const float*)nullptr, 0);
   TOK_CHECK_LAUNCH("tok_global_attn_fwd");
+  return TOK_OK;
+}
+
+#define GA_CHECK_BIAS(who)                                                                                                    \
+  TOK_CHECK_ARG(bias && ldb >= n && ldb % 4 == 0 && ((uintptr_t)bias & 15) == 0,                                            \
+                "%s: bias pointer / row pitch ldb %d (16-byte aligned, >= n, a multiple of 4)", who, ldb)
+
+extern "C" int tok_global_attn_bias_fwd(const void* qkv, int ldq, const float* bias, int ldb, int batch, int n, int heads,
+                                        int head_dim, void* out, int ldo, float* lse, void* stream) {
+  GA_CHECK_GEO("tok_global_attn_bias_fwd");
+  TOK_CHECK_ARG(qkv && out && lse, "tok_global_attn_bias_fwd: null pointer");
+  GA_CHECK_BIAS("tok_global_attn_bias_fwd");
+  hipLaunchKernelGGL(gattn_fwd_kernel<true>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)qkv, ldq, n, heads, (bf16*)out, ldo, lse, bias, ldb);
+  TOK_CHECK_LAUNCH("tok_global_attn_bias_fwd");
   return TOK_OK;
 }
 
@@ -465,12 +607,69 @@ extern "C" int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, co
   hipLaunchKernelGGL(gattn_delta_kernel, dim3(blocks_of((int64_t)batch * n * heads)), dim3(256), 0, st, (const bf16*)out,
                      (const bf16*)dout, ldo, batch, n, heads, delta);
   TOK_CHECK_LAUNCH("tok_global_attn_bwd(delta)");
-  hipLaunchKernelGGL(gattn_dkv_kernel, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
-                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd);
+  hipLaunchKernelGGL(gattn_dkv_kernel<false>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, (const float*)nullptr, 0);
   TOK_CHECK_LAUNCH("tok_global_attn_bwd(dkv)");
-  hipLaunchKernelGGL(gattn_dq_kernel, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
-                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd);
+  hipLaunchKernelGGL(gattn_dq_kernel<false>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, (const float*)nullptr, 0);
   TOK_CHECK_LAUNCH("tok_global_attn_bwd(dq)");
+  return TOK_OK;
+}
+
+// images per d(bias) chunk: enough (tile, head, chunk) workgroups for eight per CU of the 256 where the batch allows it
+// (heads x tiles^2 is 192 at base / 224), at most 64 chunks to fold
+static int dbias_per_chunk(int batch, int n, int heads) {
+  const long long tiles = (long long)tok_cdiv(n, TL) * tok_cdiv(n, TL) * heads;
+  long long chunks = (2048 + tiles - 1) / tiles;
+  if (chunks > 64) chunks = 64;
+  if (chunks > batch) chunks = batch;
+  return tok_cdiv(batch, chunks);
+}
+
+extern "C" int tok_global_attn_bias_bwd_chunks(int batch, int n, int heads) {
+  if (batch <= 0 || n <= 0 || heads <= 0) return 0;
+  return tok_cdiv(batch, dbias_per_chunk(batch, n, heads));
+}
+
+extern "C" size_t tok_global_attn_bias_bwd_ws_bytes(int batch, int n, int heads, int ldb) {
+  if (batch <= 0 || n <= 0 || heads <= 0 || ldb < n) return 0;
+  return tok_global_attn_bwd_ws_bytes(batch, n, heads) +
+         (size_t)tok_global_attn_bias_bwd_chunks(batch, n, heads) * heads * n * ldb * sizeof(float);
+}
+
+extern "C" int tok_global_attn_bias_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
+                                        const float* bias, int ldb, int batch, int n, int heads, int head_dim, void* dqkv,
+                                        int ldd, float* dbias, int dbias_accumulate, void* ws, size_t ws_bytes, void* stream) {
+  GA_CHECK_GEO("tok_global_attn_bias_bwd");
+  TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "tok_global_attn_bias_bwd: null pointer");
+  GA_CHECK_BIAS("tok_global_attn_bias_bwd");
+  TOK_CHECK_ARG(ldd >= 3 * heads * HD && ldd % 8 == 0, "tok_global_attn_bias_bwd: ldd %d", ldd);
+  // without dbias only delta lives in the workspace: a frozen table pays for no chunk partials
+  const size_t ws_need = dbias ? tok_global_attn_bias_bwd_ws_bytes(batch, n, heads, ldb) : tok_global_attn_bwd_ws_bytes(batch, n, heads);
+  if (ws_bytes < ws_need) {
+    tok_set_error("tok_global_attn_bias_bwd: workspace %zu < %zu bytes", ws_bytes, ws_need);
+    return TOK_ERR_WORKSPACE;
+  }
+  hipStream_t st = tok_stream(stream);
+  float* delta = (float*)ws;
+  float* part = (float*)((char*)ws + tok_global_attn_bwd_ws_bytes(batch, n, heads));
+  hipLaunchKernelGGL(gattn_delta_kernel, dim3(blocks_of((int64_t)batch * n * heads)), dim3(256), 0, st, (const bf16*)out,
+                     (const bf16*)dout, ldo, batch, n, heads, delta);
+  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(delta)");
+  hipLaunchKernelGGL(gattn_dkv_kernel<true>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, bias, ldb);
+  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(dkv)");
+  hipLaunchKernelGGL(gattn_dq_kernel<true>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, bias, ldb);
+  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(dq)");
+  if (!dbias) return TOK_OK;
+  const int per = dbias_per_chunk(batch, n, heads), chunks = tok_cdiv(batch, per), nt = tok_cdiv(n, TL);
+  hipLaunchKernelGGL(gattn_dbias_kernel, dim3(nt * nt, heads, chunks), dim3(256), 0, st, (const bf16*)qkv, ldq, (const bf16*)dout,
+                     ldo, lse, (const float*)delta, bias, ldb, batch, n, heads, per, part);
+  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(dbias)");
+  hipLaunchKernelGGL(gattn_dbias_fold_kernel, dim3(blocks_of((int64_t)heads * n * n)), dim3(256), 0, st, (const float*)part,
+                     chunks, heads, n, ldb, dbias, dbias_accumulate ? 1 : 0);
+  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(fold)");
   return TOK_OK;
 }
 

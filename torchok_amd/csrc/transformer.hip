@@ -1099,6 +1099,57 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a, const bf16* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// relative position bias of BEiT ([timm 0.6.13] beit.Attention): bias[h][i][j] = table[index[i][j]][h], table fp32 [T][heads]
+__global__ __launch_bounds__(256) void relpos_bias_fwd_kernel(const float* __restrict__ table, const int64_t* __restrict__ index,
+                                                              int heads, int n, float* __restrict__ bias, int ldb) {
+  const int64_t nn = (int64_t)n * n, total = heads * nn;
+  // grid-stride: blocks_for() caps the grid, and 16 heads x 1025^2 (large / 512) is more than the cap covers in one trip
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int h = (int)(i / nn);
+    const int64_t ij = i - h * nn;
+    bias[((size_t)h * n + ij / n) * ldb + ij % n] = table[index[ij] * heads + h];
+  }
+}
+
+// dtable[t][h] (=|+=) sum_{(i,j): index == t} dbias[h][i][j]: the ordered transpose of cpb_bias_bwd_kernel with one block per table
+// row serving every head, so the index is scanned once per row.  Thread x takes the positions p = x (mod 256) in ascending order
+// and keeps one running sum per head in LDS; a wave then folds the 256 sums of a head in a fixed order.
+__global__ __launch_bounds__(256) void relpos_bias_bwd_kernel(const float* __restrict__ dbias, int ldb,
+                                                              const int64_t* __restrict__ index, int heads, int n,
+                                                              float* __restrict__ dtable, int accumulate) {
+  extern __shared__ float rp_acc[];      // [heads][256]
+  const int t = blockIdx.x, nn = n * n, tid = threadIdx.x;
+  for (int h = 0; h < heads; ++h) rp_acc[h * 256 + tid] = 0.f;
+  // eight index loads per thread in flight, all unconditional, before any is compared (the one-at-a-time form is a chain of
+  // dependent L2 round trips, see cpb_bias_bwd_kernel); only the rare matches read d(bias).  Ascending p per thread as before.
+  for (int p0 = tid; p0 < nn; p0 += 256 * 8) {
+    int64_t idx[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int p = p0 + 256 * u;
+      idx[u] = index[p < nn ? p : nn - 1];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int p = p0 + 256 * u;
+      if (p >= nn || idx[u] != t) continue;
+      const size_t off = (size_t)(p / n) * ldb + p % n;
+      for (int h = 0; h < heads; ++h) rp_acc[h * 256 + tid] += dbias[(size_t)h * n * ldb + off];
+    }
+  }
+  __syncthreads();
+  const int lane = tid & 63, wv = tid >> 6;
+  for (int h = wv; h < heads; h += 4) {
+    const float* a = rp_acc + h * 256;
+    const float v = wave_sum((a[lane] + a[lane + 64]) + (a[lane + 128] + a[lane + 192]));
+    if (lane == 0) {
+      float* o = dtable + (size_t)t * heads + h;
+      *o = accumulate ? *o + v : v;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // continuous position bias: bias[h][i][j] = 16 * sigmoid(table[index[i][j]][h])
 __global__ __launch_bounds__(256) void cpb_bias_fwd_kernel(const bf16* __restrict__ table, int ld,
                                                            const int64_t* __restrict__ index, int heads, int nn,
@@ -1411,6 +1462,25 @@ extern "C" int tok_cpb_bias_bwd(const float* dbias, int transposed, const void* 
   hipLaunchKernelGGL(cpb_bias_bwd_kernel, dim3(table_rows, ld), dim3(64), 0, tok_stream(stream), dbias,
                      (const bf16*)table, ld, index, heads, n_tokens, transposed, (bf16*)dtable);
   TOK_CHECK_LAUNCH("tok_cpb_bias_bwd");
+  return TOK_OK;
+}
+
+extern "C" int tok_relpos_bias_fwd(const float* table, const int64_t* index, int heads, int n_tokens, float* bias, int ldb,
+                                   void* stream) {
+  TOK_CHECK_ARG(table && index && bias && heads > 0 && n_tokens > 0 && ldb >= n_tokens, "tok_relpos_bias_fwd: bad args");
+  hipLaunchKernelGGL(relpos_bias_fwd_kernel, dim3(blocks_for((size_t)heads * n_tokens * n_tokens)), dim3(256), 0,
+                     tok_stream(stream), table, index, heads, n_tokens, bias, ldb);
+  TOK_CHECK_LAUNCH("tok_relpos_bias_fwd");
+  return TOK_OK;
+}
+
+extern "C" int tok_relpos_bias_bwd(const float* dbias, int ldb, const int64_t* index, int heads, int n_tokens, int table_rows,
+                                   float* dtable, int accumulate, void* stream) {
+  TOK_CHECK_ARG(dbias && index && dtable && heads > 0 && heads <= TOK_RELPOS_MAX_HEADS && n_tokens > 0 && table_rows > 0 &&
+                ldb >= n_tokens, "tok_relpos_bias_bwd: bad args (1 ... %d heads)", TOK_RELPOS_MAX_HEADS);
+  hipLaunchKernelGGL(relpos_bias_bwd_kernel, dim3(table_rows), dim3(256), (size_t)heads * 256 * sizeof(float),
+                     tok_stream(stream), dbias, ldb, index, heads, n_tokens, dtable, accumulate ? 1 : 0);
+  TOK_CHECK_LAUNCH("tok_relpos_bias_bwd");
   return TOK_OK;
 }
 

@@ -11,7 +11,10 @@ window_attention     WindowAttention.forward between qkv and proj, with roll / w
                      folded into the kernel's token addressing
 patch_merge          PatchMerging's strided 2x2 gather + cat
 reshape              .view between (B, H, W, C) maps and (B*H*W, C) token rows (zero copy)
-global_attention     ViT Attention.forward between qkv and proj: softmax(q k^T / 8) v over all tokens of an image
+global_attention     ViT Attention.forward between qkv and proj: softmax(q k^T / 8) v over all tokens of an image; with
+                     `bias` BEiT's softmax(q k^T / 8 + relative_position_bias) v
+relpos_bias          BEiT relative_position_bias_table[relative_position_index] -> [heads][N][N] (gathered again in the backward)
+layer_scale_add      BEiT Block's  x + drop_path(gamma * f(x))
 patch_embed          ViT PatchEmbed.proj (k = stride = patch): patch gather + 1x1 GEMM
 vit_embed            VisionTransformer._pos_embed: cls token + pos_embed, one rounding
 rows_select          x[:, first:first + count] of the (B, T, C) token view (cls rows, patch rows)
@@ -697,6 +700,7 @@ def dwconv3x3(region: Region, x: TTensor, conv: nn.Conv2d) -> TTensor:
 # ---- Vision Transformer: global attention, patch embedding, token assembly ---------------------------------------------------
 class _GlobalAttnNode(Node):
     needs_backward = True
+    bias_node = None        # _RelposBiasNode: the attention ran with its bias; d(bias) is handed to it
 
     def backward(self):
         lib, st = _C.lib(), stream_ptr()
@@ -710,22 +714,94 @@ class _GlobalAttnNode(Node):
         tgt, acc = grad_target(qkv)
         if acc:
             raise RuntimeError('global_attention: qkv has a single consumer')
-        ws_bytes = int(lib.tok_global_attn_bwd_ws_bytes(b, n, heads))
-        ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-        _C.check(lib.tok_global_attn_bwd(ptr(qkv.data), qkv.cp, ptr(o.data), ptr(g), o.cp, ptr(self.lse), b, n, heads, 64,
-                                         ptr(tgt), qkv.cp, ptr(ws), ws_bytes, st), 'tok_global_attn_bwd')
+        bn = self.bias_node
+        if bn is None:
+            ws_bytes = int(lib.tok_global_attn_bwd_ws_bytes(b, n, heads))
+            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
+            _C.check(lib.tok_global_attn_bwd(ptr(qkv.data), qkv.cp, ptr(o.data), ptr(g), o.cp, ptr(self.lse), b, n, heads, 64,
+                                             ptr(tgt), qkv.cp, ptr(ws), ws_bytes, st), 'tok_global_attn_bwd')
+        else:
+            bias = bn.gather()             # gathered again: no block keeps its [heads][N][N] bias across the step
+            ldb = bias.shape[-1]
+            dbias = torch.empty_like(bias) if bn.table.requires_grad else None
+            # a frozen table needs delta only, not the chunk partials of d(bias)
+            ws_bytes = int(lib.tok_global_attn_bias_bwd_ws_bytes(b, n, heads, ldb) if dbias is not None
+                           else lib.tok_global_attn_bwd_ws_bytes(b, n, heads))
+            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
+            _C.check(lib.tok_global_attn_bias_bwd(ptr(qkv.data), qkv.cp, ptr(o.data), ptr(g), o.cp, ptr(self.lse), ptr(bias), ldb,
+                                                  b, n, heads, 64, ptr(tgt), qkv.cp, ptr(dbias), 0, ptr(ws), ws_bytes, st),
+                     'tok_global_attn_bias_bwd')
+            bn.dbias = dbias
         c = heads * 64
         if qkv.cp != 3 * c:
             tgt[:, 3 * c:] = 0
         self.out.grad = None
 
     def release(self):
-        self.qkv = self.out = self.lse = None
+        self.qkv = self.out = self.lse = self.bias_node = None
 
 
-def global_attention(region: Region, qkv: TTensor, batch: int, tokens: int, heads: int, head_dim: int = 64) -> TTensor:
+class _RelposBiasNode(Node):
+    """The bias of one BEiT attention unit.  `gather()` produces it (forward, and again in the attention unit's backward);
+    the attention unit's backward leaves d(bias) here and this unit — recorded before it, so run after it — transposes the
+    gather into the table's gradient."""
+    needs_backward = True
+    dbias = None
+
+    def gather(self) -> torch.Tensor:
+        heads, n = self.heads, self.n
+        ldb = (n + 3) // 4 * 4
+        bias = torch.empty((heads, n, ldb), dtype=F32, device=self.table.device)
+        _C.check(_C.lib().tok_relpos_bias_fwd(ptr(self.table.detach()), ptr(self.index), heads, n, ptr(bias), ldb, stream_ptr()),
+                 'tok_relpos_bias_fwd')
+        return bias
+
+    def backward(self):
+        dbias, self.dbias = self.dbias, None
+        table = self.table
+        if dbias is None or not table.requires_grad:
+            return
+        slot, acc = PG.sink(table)
+        _C.check(_C.lib().tok_relpos_bias_bwd(ptr(dbias), dbias.shape[-1], ptr(self.index), self.heads, self.n, table.shape[0],
+                                              ptr(slot), acc, stream_ptr()), 'tok_relpos_bias_bwd')
+        PG.commit(table, slot, acc)
+
+    def release(self):
+        self.table = self.index = self.dbias = None
+
+
+def relpos_bias(region: Region, table: nn.Parameter, index: torch.Tensor, heads: int, n_tokens: int, checked: dict = None):
+    """[timm 0.6.13] beit.Attention._get_rel_pos_bias: table[index.view(-1)].view(N, N, heads).permute(2, 0, 1) as fp32
+    [heads][N][ldb] (ldb = N rounded up to 4; the pad columns are never read).  -> (bias, node); `global_attention` takes the
+    pair.  An index outside the table is refused here, on the host (one sync).  `checked` is a dict the caller owns (the attention
+    module): the range check is skipped while it records this table height and this very index storage and version."""
+    rows = table.shape[0]
+    if (tuple(table.shape) != (rows, heads) or not table.is_contiguous() or table.dtype != F32 or index.dtype != torch.int64
+            or tuple(index.shape) != (n_tokens, n_tokens) or not index.is_contiguous() or index.device != table.device):
+        raise ValueError(f'relpos_bias: table {tuple(table.shape)} / index {tuple(index.shape)} {index.dtype} for {heads} heads, '
+                         f'{n_tokens} tokens (fp32 [T][heads], contiguous int64 [N][N] on one device)')
+    seen = (rows, index.data_ptr(), index._version, index.device)
+    if checked is None or checked.get('relpos_index') != seen:
+        lo, hi = int(index.min()), int(index.max())
+        if lo < 0 or hi >= rows:
+            raise ValueError(f'relpos_bias: relative_position_index holds {lo} ... {hi}, the table has {rows} rows')
+        if checked is not None:
+            checked['relpos_index'] = seen
+    node = _RelposBiasNode()
+    node.table, node.index, node.heads, node.n = table, index, heads, n_tokens
+    bias = node.gather()
+    if not region.grad_mode:
+        return bias, None
+    region.add(node)
+    return bias, node
+
+
+def global_attention(region: Region, qkv: TTensor, batch: int, tokens: int, heads: int, head_dim: int = 64,
+                     bias=None) -> TTensor:
     """[timm 0.6.13] Attention.forward between qkv and proj: qkv rows [B*N][3C] -> softmax(q k^T * 64^-0.5) v rows [B*N][C],
-    over all N tokens of an image.  The node keeps qkv, the output and the row log-sum-exp; its backward writes d(qkv)."""
+    over all N tokens of an image.  The node keeps qkv, the output and the row log-sum-exp; its backward writes d(qkv).
+    bias: the (bias, node) pair of `relpos_bias` — softmax(q k^T * 64^-0.5 + bias[h]) v; the backward gathers the bias again
+    and hands d(bias) to that node."""
     c = heads * head_dim
     if qkv.c != 3 * c:
         raise ValueError(f'global_attention: qkv width {qkv.c} != 3 * {heads} heads * {head_dim}')
@@ -733,15 +809,26 @@ def global_attention(region: Region, qkv: TTensor, batch: int, tokens: int, head
     dev = qkv.data.device
     out_data = torch.empty((batch * tokens, c), dtype=BF16, device=dev)
     lse = torch.empty((batch, heads, tokens), dtype=F32, device=dev)
-    rc = lib.tok_global_attn_fwd(ptr(qkv.data), qkv.cp, batch, tokens, heads, head_dim, ptr(out_data), c, ptr(lse), st)
+    if bias is None:
+        what = 'tok_global_attn_fwd'
+        rc = lib.tok_global_attn_fwd(ptr(qkv.data), qkv.cp, batch, tokens, heads, head_dim, ptr(out_data), c, ptr(lse), st)
+    else:
+        what = 'tok_global_attn_bias_fwd'
+        bias_data, bias_node = bias
+        if tuple(bias_data.shape[:2]) != (heads, tokens):
+            raise ValueError(f'global_attention: bias {tuple(bias_data.shape)} for {heads} heads, {tokens} tokens')
+        rc = lib.tok_global_attn_bias_fwd(ptr(qkv.data), qkv.cp, ptr(bias_data), bias_data.shape[-1], batch, tokens, heads,
+                                          head_dim, ptr(out_data), c, ptr(lse), st)
     if rc != 0 and head_dim != 64:
         raise NotImplementedError(f'global_attention: head_dim {head_dim} (64 only)')
-    _C.check(rc, 'tok_global_attn_fwd')
-    req = region.grad_mode and qkv.requires_grad
+    _C.check(rc, what)
+    req = region.grad_mode and (qkv.requires_grad or (bias is not None and bias[1] is not None and bias[1].table.requires_grad))
     out = TTensor(out_data, c, requires_grad=req)
     if req:
         node = _GlobalAttnNode()
         node.qkv, node.out, node.lse, node.geo = qkv, out, lse, (batch, tokens, heads)
+        if bias is not None:
+            node.bias_node = bias[1]
         out.node = node
         qkv.uses += 1
         region.add(node)
@@ -906,5 +993,62 @@ def rows_select(region: Region, x: TTensor, batch: int, first: int, count: int) 
         node.x, node.out, node.geo = x, out, (batch, t, first, count)
         out.node = node
         x.uses += 1
+        region.add(node)
+    return out
+
+
+# ---- BEiT: LayerScale residual ------------------------------------------------------------------------------------------------
+class _LayerScaleNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        lib, st = _C.lib(), stream_ptr()
+        g = self.out.grad
+        if g is None:
+            return
+        x, a, gamma = self.x, self.a, self.gamma
+        rows, d = _rows(a), a.cp
+        g_need = gamma.requires_grad
+        if a.requires_grad or g_need:
+            tgt, acc = grad_target(a) if a.requires_grad else (None, 0)
+            slot, gacc = PG.sink(gamma) if g_need else (None, 0)
+            part = torch.empty((lib.tok_layer_scale_bwd_rows(rows, d), d), dtype=F32, device=g.device) if g_need else None
+            _C.check(lib.tok_layer_scale_bwd(ptr(g), ptr(a.data), ptr(gamma.detach()), ptr(self.row_scale), self.rps, ptr(tgt), acc,
+                                             ptr(slot), gacc, ptr(part), rows, d, st), 'tok_layer_scale_bwd')
+            if g_need:
+                PG.commit(gamma, slot, gacc)
+        if x.requires_grad:
+            if not (self.out.grad_owned and donate_grad(x, g.view(x.data.shape))):
+                tgt, acc = grad_target(x)
+                _C.check(lib.tok_act_bwd(2, ptr(g), ptr(g), ptr(tgt), acc, g.numel(), st), 'tok_act_bwd')
+        self.out.grad = None
+
+    def release(self):
+        self.x = self.a = self.out = self.row_scale = self.gamma = None
+
+
+def layer_scale_add(region: Region, x: TTensor, a: TTensor, gamma: nn.Parameter, row_scale: Optional[torch.Tensor] = None,
+                    tokens: int = 0) -> TTensor:
+    """out = x + row_scale[sample] * gamma * a — [timm 0.6.13] beit.Block's  x + drop_path(gamma_i * f(norm(x)))  with the
+    stochastic-depth keep/scale vector applied in place (`tokens` rows per sample).  gamma: the fp32 [dim] parameter."""
+    lib, st = _C.lib(), stream_ptr()
+    rows, d = _rows(a), a.cp
+    if x.data.shape != a.data.shape:
+        raise ValueError(f'layer_scale_add: {tuple(x.data.shape)} vs {tuple(a.data.shape)}')
+    if gamma.numel() != d or gamma.dtype != F32 or not gamma.is_contiguous():
+        raise ValueError(f'layer_scale_add: gamma {tuple(gamma.shape)} {gamma.dtype} for rows of {d} (fp32, contiguous)')
+    out_data = torch.empty_like(a.data)
+    _C.check(lib.tok_layer_scale_fwd(ptr(x.data), ptr(a.data), ptr(gamma.detach()), ptr(row_scale), tokens, ptr(out_data), rows, d,
+                                     st), 'tok_layer_scale_fwd')
+    req = region.grad_mode and (x.requires_grad or a.requires_grad or gamma.requires_grad)
+    out = TTensor(out_data, a.c, requires_grad=req)
+    if req:
+        node = _LayerScaleNode()
+        node.x, node.a, node.out, node.gamma, node.row_scale, node.rps = x, a, out, gamma, row_scale, tokens
+        out.node = node
+        if x.requires_grad:
+            x.uses += 1
+        if a.requires_grad:
+            a.uses += 1
         region.add(node)
     return out
