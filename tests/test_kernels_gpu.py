@@ -89,7 +89,7 @@ CONV_CASES = [
     (5, 13, 15, 40, 136, 3, 1, 1),     # C = 40: second chunk a quarter full; K = 136: second channel tile ragged
     (2, 56, 56, 64, 64, 3, 1, 1),      # 64-channel form of the window kernel (4 x 1 waves): ResNet stage 1
     (1, 40, 72, 48, 48, 3, 1, 1),      # HRNet-W48's high-resolution branch: 48 of 64 channels, C = 32 + 16
-    (8, 128, 128, 48, 48, 3, 1, 1),    # ... at a size the register-resident form serves (conv_winr_kernel: 8 x 32 tiles, >= 512 of them)
+    (8, 128, 128, 48, 48, 3, 1, 1),    # ... over 131 072 pixels: the 48-wide window kernels on many tiles per image, weight gradient split 256 ways
     (4, 64, 512, 48, 48, 3, 1, 1),     # ... sixteen x-tiles per row group, images of 8 row groups
 ]
 
@@ -1907,7 +1907,7 @@ def test_gemm256_tile_kernel_is_bit_identical_to_the_default_kernels():
 
 
 def test_wgrad_256_tile_kernel_matches_the_128_tile_plan():
-    """conv_wgrad_ring8_kernel<256, 256> (eight waves; serves pointwise layers over >= 200 k pixels by default, every eligible layer
+    """conv_wgrad_ring_kernel<256, 256, 4> (eight waves; serves pointwise layers over >= 200 k pixels by default, every eligible layer
     with TOK_WGRAD_256=2) against the 128 x 128 ring plan: dW, accumulated dW and the bias column sums agree to fp32 summation
     order (different split-M partition), and with the fp32 product where the host can form it.  Subprocess arms: the knob is
     read once per process (tools/ubench/wgrad256_check.py)."""

@@ -1,4 +1,4 @@
-"""conv_wgrad_ring8_kernel<256, 256> against the 128 x 128 ring plan on the layers it serves: dW (+ bias column sums), per-call time.
+"""conv_wgrad_ring_kernel<256, 256, 4> against the 128 x 128 ring plan on the layers it serves: dW (+ bias column sums), per-call time.
    python tools/ubench/wgrad256_check.py        (runs itself twice: TOK_WGRAD_256=1 / 0)"""
 import os
 import subprocess

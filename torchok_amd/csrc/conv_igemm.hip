@@ -713,12 +713,6 @@ int plan_grid(int bn_tile, int gridM, int gridN, int per_cu = 0) {
 template <int BM, int BN, int IN_DIV, bool C4, int PW>
 int launch_pw(ConvArgs& a, hipStream_t st) {
   constexpr int smem = 2 * (BM + BN) * BK * 2 + 2 * 4 * BN * 4 + (PW == 4 ? 2 * BM * BN * 2 : 0);
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<BM, BN, IN_DIV, C4, PW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
   const int grid = a.force_grid > 0 ? a.force_grid
                                     : plan_grid(BN, a.gridM, a.gridN, PW == 4 ? 2 : 0);   // (PW 4: two shortcut tiles in LDS -> 2 per CU)
   a.stat_rows = grid / a.gridN;
@@ -731,7 +725,7 @@ int launch_pw(ConvArgs& a, hipStream_t st) {
     a.timing = tbuf;
   }
 #endif
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, IN_DIV, C4, PW>), dim3(grid), dim3(256), smem, st, a);
+  tok_launch_lds<&conv_igemm_kernel<BM, BN, IN_DIV, C4, PW>>(smem, dim3(grid), dim3(256), smem, st, a);
 #ifdef TOK_TIMING
   {
     unsigned long long h[8];

@@ -326,13 +326,7 @@ int pick_wbn(int K, long long ptiles) {
 
 template <int TW, int BN>
 void launch_variant(const ConvArgs& a, const S2Geo& g, int grid, hipStream_t st) {
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s2d_kernel<TW, BN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              s2_smem(BN));
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
-  hipLaunchKernelGGL((conv_s2d_kernel<TW, BN>), dim3(grid), dim3(256), s2_smem(BN), st, a, g);
+  tok_launch_lds<&conv_s2d_kernel<TW, BN>>(s2_smem(BN), dim3(grid), dim3(256), s2_smem(BN), st, a, g);
 }
 
 }  // namespace

@@ -322,29 +322,38 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {         
 //   iteration st:  wait vmcnt(L) -> stage st has landed (this wave's share); lgkmcnt(0) -> this wave's reads of stage st-1 retired
 //                  s_barrier     -> every wave's share of stage st landed, nobody reads stage st-1 any more
 //                  issue stage st+2 into the buffer of stage st-1;  fragment reads + MFMAs of stage st
-// Tiles 64/128/256 x 64/128/256 (2 x 2 waves): a 64-channel layer takes a 64 x 256 (or 256 x 64) tile so that every barrier
-// still covers 16 MFMAs per wave.
-template <int TN, int TK>
-__global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
-  constexpr int MS = 32, NST = 3;
+// WK = waves along k; the waves are 2 (n) x WK (k), 128 * WK threads.
+// WK = 2: tiles 64/128/256 x 64/128/256; a 64-channel layer takes a 64 x 256 (or 256 x 64) tile so that every barrier still
+// covers 16 MFMAs per wave.
+// WK = 4: the 256 x 256 tile (pointwise layers with wide outputs AND deep filters).  What bounds the 128 x 128 tile on the
+// transformer and late-ResNet layers is the L2 -> LDS staging path: it stages (128 + 128) x 2 bytes per reduction row for
+// 128 x 128 MACs, and every (n, k) tile of a layer stages ALL M rows of its two operand slices again — SwinV2-T stage-3 fc2
+// (384 x 1536 weights, 50 176 tokens): 36 tiles x 25.7 MB = 925 MB through a path that sustains ~10 TB/s chip-wide = the 93 us
+// the launch takes (2.0 TB/s of HBM, MFMA util 0.23: "neither bound", profiles/r03_*).  A 256 x 256 tile stages half the bytes
+// per MAC.  A wave owns 128 x 64 of the tile = 32 accumulator blocks, 24 transpose reads per 32 MFMAs.  One workgroup per CU
+// (96 KB of LDS, ~200 registers); the split-M partial tiles are 256 KB each, so the plan aims at one workgroup per CU (256
+// slabs) — twice the partial-sum bytes of the 128 x 128 plan, against half the staged bytes.
+template <int TN, int TK, int WK>
+__global__ __launch_bounds__(128 * WK, WK == 4 ? 1 : 0) void conv_wgrad_ring_kernel(WgradArgs a) {   // (0: no occupancy request)
+  constexpr int MS = 32, NST = 3, NTHR = 128 * WK;
   constexpr int CN = TN / 8, CK = TK / 8;
-  constexpr int RPY = 256 / CN, RPX = 256 / CK;
+  constexpr int RPY = NTHR / CN, RPX = NTHR / CK;
   constexpr int YP = MS / RPY, XP = MS / RPX;
-  static_assert(YP >= 1 && XP >= 1, "tile too narrow for 256 threads");
+  static_assert(YP >= 1 && XP >= 1 && MS % RPY == 0 && MS % RPX == 0, "tile too narrow for the thread count");
   constexpr int LOADS = YP + XP;                 // DMA instructions per thread and stage
   constexpr int YS = TN * 2, XS = TK * 2;
   constexpr int YBYTES = MS * YS, XBYTES = MS * XS, STAGE = YBYTES + XBYTES;
   // swizzle masks: row bits that do not change from one staging pass to the next (a thread keeps ONE logical chunk)
   constexpr int SWY = (CN / 2 - 1) < (RPY - 1) ? (CN / 2 - 1) : (RPY - 1);
   constexpr int SWX = (CK / 2 - 1) < (RPX - 1) ? (CK / 2 - 1) : (RPX - 1);
-  constexpr int NT = TN / 32, KTL = TK / 32;
+  constexpr int NT = TN / 32, KTL = TK / (16 * WK);   // 16-wide blocks per wave: TN / 2 rows of n, TK / WK columns of k
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = tid >> 6;
-  const int wn2 = wv & 1, wk2 = wv >> 1;
+  const int wn2 = wv & 1, wk = wv >> 1;
 
   const int ntile = a.tilesN * a.tilesK;
   const int id = tok_xcd_remap(blockIdx.x, ntile * a.splitM);
@@ -365,13 +374,22 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
   const int yn = tn * TN + ylog * 8;
   const bool yn_ok = yn < a.K;
 
-  const int k0 = tk * TK + xlog * 8;
-  const int tap = k0 / a.C;
-  const int kc0 = k0 - tap * a.C;
-  const int kr = tap / a.S;
-  const bool k_ok = kr < a.R;
+  // this thread's k-chunk never changes.  Pointwise layers only: the k column IS the input channel — the eight-wave form says
+  // so, the four-wave form keeps the general (tap, channel) decode of conv_wgrad_kernel
+  int kc0;
+  bool k_ok;
+  if constexpr (WK == 2) {
+    const int k0 = tk * TK + xlog * 8;
+    const int tap = k0 / a.C;
+    kc0 = k0 - tap * a.C;
+    const int kr = tap / a.S;
+    k_ok = kr < a.R;
+  } else {
+    kc0 = tk * TK + xlog * 8;
+    k_ok = kc0 < a.C;
+  }
 
-  // row cursor: output pixel of this thread's X rows (pointwise layers only: input pixel == output pixel)
+  // row cursor: output pixel of this thread's X rows (input pixel == output pixel)
   int xm[XP];
 #pragma unroll
   for (int i = 0; i < XP; ++i) xm[i] = mstart + xrow + i * RPX;
@@ -405,7 +423,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
   const int rrow = 4 * g + (li >> 2);
   const int yswz = ((rrow & SWY) << 1) << 4, xswz = ((rrow & SWX) << 1) << 4;
   auto ycolb = [&](int i) { return ((wn2 * (TN / 2) + i * 16 + (li & 3) * 4) * 2) ^ yswz; };
-  auto xcolb = [&](int j) { return ((wk2 * (TK / 2) + j * 16 + (li & 3) * 4) * 2) ^ xswz; };
+  auto xcolb = [&](int j) { return ((wk * (TK / WK) + j * 16 + (li & 3) * 4) * 2) ^ xswz; };
 
   f32x4 acc[NT][KTL];
 #pragma unroll
@@ -415,7 +433,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
 
   // bias gradient = dy^T 1: the waves that own the first k-tile multiply their dy fragments with an all-ones operand as well
   // (NT extra MFMAs per stage; every column of the result tile holds the column sums) — no separate pass over dy
-  const bool do_cs = a.cs != nullptr && tk == 0 && wk2 == 0;     // wave-uniform
+  const bool do_cs = a.cs != nullptr && tk == 0 && wk == 0;     // wave-uniform
   f32x4 csacc[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i) csacc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -437,28 +455,61 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
     const uint32_t Yb = lds_base + cur * STAGE;
     const uint32_t Xb = Yb + YBYTES;
     u32x2 ya[NT][2], xb[KTL][2];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      ya[i][0] = tr_read_asm(Yb + rrow * YS + ycolb(i));
-      ya[i][1] = tr_read_asm(Yb + (rrow + 16) * YS + ycolb(i));
-    }
-#pragma unroll
-    for (int j = 0; j < KTL; ++j) {
-      xb[j][0] = tr_read_asm(Xb + rrow * XS + xcolb(j));
-      xb[j][1] = tr_read_asm(Xb + (rrow + 16) * XS + xcolb(j));
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);     // keeps the MFMAs below the wait (they only depend on registers)
     bf16x8 af[NT], bfr[KTL];
+    if constexpr (WK == 2) {
 #pragma unroll
-    for (int i = 0; i < NT; ++i) af[i] = __builtin_bit_cast(bf16x8, (u32x4){ya[i][0][0], ya[i][0][1], ya[i][1][0], ya[i][1][1]});
+      for (int i = 0; i < NT; ++i) {
+        ya[i][0] = tr_read_asm(Yb + rrow * YS + ycolb(i));
+        ya[i][1] = tr_read_asm(Yb + (rrow + 16) * YS + ycolb(i));
+      }
 #pragma unroll
-    for (int j = 0; j < KTL; ++j) bfr[j] = __builtin_bit_cast(bf16x8, (u32x4){xb[j][0][0], xb[j][0][1], xb[j][1][0], xb[j][1][1]});
+      for (int j = 0; j < KTL; ++j) {
+        xb[j][0] = tr_read_asm(Xb + rrow * XS + xcolb(j));
+        xb[j][1] = tr_read_asm(Xb + (rrow + 16) * XS + xcolb(j));
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);     // keeps the MFMAs below the wait (they only depend on registers)
 #pragma unroll
-    for (int i = 0; i < NT; ++i)
+      for (int i = 0; i < NT; ++i) af[i] = __builtin_bit_cast(bf16x8, (u32x4){ya[i][0][0], ya[i][0][1], ya[i][1][0], ya[i][1][1]});
 #pragma unroll
-      for (int j = 0; j < KTL; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < KTL; ++j) bfr[j] = __builtin_bit_cast(bf16x8, (u32x4){xb[j][0][0], xb[j][0][1], xb[j][1][0], xb[j][1][1]});
+#pragma unroll
+      for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < KTL; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    } else {
+      // (24 transpose reads: the 4-bit lgkmcnt counter cannot count them all; the first 8 — every x fragment — are waited for
+      //  together with the first half of the dy fragments, then the rest)
+#pragma unroll
+      for (int j = 0; j < KTL; ++j) {
+        xb[j][0] = tr_read_asm(Xb + rrow * XS + xcolb(j));
+        xb[j][1] = tr_read_asm(Xb + (rrow + 16) * XS + xcolb(j));
+      }
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        ya[i][0] = tr_read_asm(Yb + rrow * YS + ycolb(i));
+        ya[i][1] = tr_read_asm(Yb + (rrow + 16) * YS + ycolb(i));
+      }
+      asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < KTL; ++j) bfr[j] = __builtin_bit_cast(bf16x8, (u32x4){xb[j][0][0], xb[j][0][1], xb[j][1][0], xb[j][1][1]});
+#pragma unroll
+      for (int i = 0; i < NT / 2; ++i) {
+        af[i] = __builtin_bit_cast(bf16x8, (u32x4){ya[i][0][0], ya[i][0][1], ya[i][1][0], ya[i][1][1]});
+#pragma unroll
+        for (int j = 0; j < KTL; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = NT / 2; i < NT; ++i) {
+        af[i] = __builtin_bit_cast(bf16x8, (u32x4){ya[i][0][0], ya[i][0][1], ya[i][1][0], ya[i][1][1]});
+#pragma unroll
+        for (int j = 0; j < KTL; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      }
+    }
     if (do_cs) {
 #pragma unroll
       for (int i = 0; i < NT; ++i) csacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], ones, csacc[i], 0, 0, 0);
@@ -484,179 +535,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_ring_kernel(WgradArgs a) {
   for (int i = 0; i < NT; ++i) {
 #pragma unroll
     for (int j = 0; j < KTL; ++j) {
-      const int kcol = tk * TK + wk2 * (TK / 2) + j * 16 + li;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = tn * TN + wn2 * (TN / 2) + i * 16 + g * 4 + r;
-        if (n < a.K && kcol < a.Ktot) out[(size_t)n * a.Ktot + kcol] = acc[i][j][r];
-      }
-    }
-  }
-}
-
-
-// ---- 256 x 256 tiles, eight waves (pointwise layers with wide outputs AND deep filters) ------------------------------------------
-// What bounds conv_wgrad_ring_kernel<128, 128> on the transformer and late-ResNet layers is the L2 -> LDS staging path: a
-// 128 x 128 tile stages (128 + 128) x 2 bytes per reduction row for 128 x 128 MACs, and every (n, k) tile of a layer stages ALL
-// M rows of its two operand slices again — SwinV2-T stage-3 fc2 (384 x 1536 weights, 50 176 tokens): 36 tiles x 25.7 MB =
-// 925 MB through a path that sustains ~10 TB/s chip-wide = the 93 us the launch takes (2.0 TB/s of HBM, MFMA util 0.23:
-// "neither bound", profiles/r03_*).  A 256 x 256 tile stages half the bytes per MAC.  Same ring (three 32-row stages, counted
-// vmcnt + raw barrier, transpose reads from row-major tiles) on 512 threads: waves 2 (n) x 4 (k), a wave owns 128 x 64 of the
-// tile = 32 accumulator blocks, 24 transpose reads per 32 MFMAs.  One workgroup per CU (96 KB of LDS, ~200 registers); the
-// split-M partial tiles are 256 KB each, so the plan aims at one workgroup per CU (256 slabs) — twice the partial-sum bytes of
-// the 128 x 128 plan, against half the staged bytes.
-template <int TN, int TK>
-__global__ __launch_bounds__(512, 1) void conv_wgrad_ring8_kernel(WgradArgs a) {
-  constexpr int MS = 32, NST = 3, NTHR = 512;
-  constexpr int CN = TN / 8, CK = TK / 8;
-  constexpr int RPY = NTHR / CN, RPX = NTHR / CK;
-  constexpr int YP = MS / RPY, XP = MS / RPX;
-  static_assert(YP >= 1 && XP >= 1 && MS % RPY == 0 && MS % RPX == 0, "tile too narrow for 512 threads");
-  constexpr int LOADS = YP + XP;
-  constexpr int YS = TN * 2, XS = TK * 2;
-  constexpr int YBYTES = MS * YS, XBYTES = MS * XS, STAGE = YBYTES + XBYTES;
-  constexpr int SWY = (CN / 2 - 1) < (RPY - 1) ? (CN / 2 - 1) : (RPY - 1);
-  constexpr int SWX = (CK / 2 - 1) < (RPX - 1) ? (CK / 2 - 1) : (RPX - 1);
-  constexpr int NT = TN / 32, KTL = TK / 64;       // 16-wide blocks per wave: TN / 2 rows of n, TK / 4 columns of k
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = tid >> 6;
-  const int wn2 = wv & 1, wk4 = wv >> 1;
-
-  const int ntile = a.tilesN * a.tilesK;
-  const int id = tok_xcd_remap(blockIdx.x, ntile * a.splitM);
-  const int split = id / ntile;
-  const int t = id - split * ntile;
-  const int tn = t / a.tilesK;
-  const int tk = t - tn * a.tilesK;
-  const int mstart = split * a.mchunk;
-  const int mend = min(a.M, mstart + a.mchunk);
-  const int steps = (mend - mstart + MS - 1) / MS;
-
-  const int ycol = tid % CN, yrow = tid / CN;
-  const int xcol = tid % CK, xrow = tid / CK;
-  const int ylog = ycol ^ ((yrow & SWY) << 1);
-  const int xlog = xcol ^ ((xrow & SWX) << 1);
-  const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int yn = tn * TN + ylog * 8;
-  const bool yn_ok = yn < a.K;
-  const int kc0 = tk * TK + xlog * 8;              // pointwise: the k column IS the input channel
-  const bool k_ok = kc0 < a.C;
-  int xm[XP];
-#pragma unroll
-  for (int i = 0; i < XP; ++i) xm[i] = mstart + xrow + i * RPX;
-  int ym = mstart + yrow;
-
-  const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dy_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.x_bytes, 0x00020000);
-  typedef __attribute__((address_space(3))) void lds_void;
-  auto issue = [&](int dbuf) {
-    char* Ydst = smem + dbuf * STAGE + wave_u * 1024;
-    char* Xdst = smem + dbuf * STAGE + YBYTES + wave_u * 1024;
-#pragma unroll
-    for (int i = 0; i < YP; ++i) {
-      const int m = ym + i * RPY;
-      uint32_t off = (yn_ok && m < mend) ? (uint32_t)(m * a.K + yn) * 2u : 0xFFFFFFF0u;
-      asm volatile("" : "+v"(off));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ysrd, (lds_void*)(Ydst + i * RPY * YS), 16, off, 0, 0, 0);
-    }
-    ym += MS;
-#pragma unroll
-    for (int i = 0; i < XP; ++i) {
-      uint32_t off = (k_ok && xm[i] < mend) ? (uint32_t)(xm[i] * a.C + kc0) * 2u : 0xFFFFFFF0u;
-      asm volatile("" : "+v"(off));
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrd, (lds_void*)(Xdst + i * RPX * XS), 16, off, 0, 0, 0);
-      xm[i] += MS;
-    }
-  };
-
-  const int g = lane >> 4, li = lane & 15;
-  const int rrow = 4 * g + (li >> 2);
-  const int yswz = ((rrow & SWY) << 1) << 4, xswz = ((rrow & SWX) << 1) << 4;
-  auto ycolb = [&](int i) { return ((wn2 * (TN / 2) + i * 16 + (li & 3) * 4) * 2) ^ yswz; };
-  auto xcolb = [&](int j) { return ((wk4 * (TK / 4) + j * 16 + (li & 3) * 4) * 2) ^ xswz; };
-
-  f32x4 acc[NT][KTL];
-#pragma unroll
-  for (int i = 0; i < NT; ++i)
-#pragma unroll
-    for (int j = 0; j < KTL; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const bool do_cs = a.cs != nullptr && tk == 0 && wk4 == 0;     // wave-uniform: bias gradient = dy^T 1 (see the ring kernel)
-  f32x4 csacc[NT];
-#pragma unroll
-  for (int i = 0; i < NT; ++i) csacc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const bf16 one_b = (bf16)1.0f;
-  const bf16x8 ones = {one_b, one_b, one_b, one_b, one_b, one_b, one_b, one_b};
-
-  typedef __attribute__((address_space(3))) char lds_char;
-  const uint32_t lds_base = (uint32_t)(size_t)(lds_char*)smem;
-  issue(0);
-  issue(1);
-  int cur = 0, nxt = 2;
-  for (int st = 0; st < steps; ++st) {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LOADS) : "memory");
-    __builtin_amdgcn_s_barrier();
-    issue(nxt);
-    const uint32_t Yb = lds_base + cur * STAGE;
-    const uint32_t Xb = Yb + YBYTES;
-    u32x2 ya[NT][2], xb[KTL][2];
-#pragma unroll
-    for (int j = 0; j < KTL; ++j) {
-      xb[j][0] = tr_read_asm(Xb + rrow * XS + xcolb(j));
-      xb[j][1] = tr_read_asm(Xb + (rrow + 16) * XS + xcolb(j));
-    }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      ya[i][0] = tr_read_asm(Yb + rrow * YS + ycolb(i));
-      ya[i][1] = tr_read_asm(Yb + (rrow + 16) * YS + ycolb(i));
-    }
-    // (24 transpose reads: the 4-bit lgkmcnt counter cannot count them all; the first 8 — every x fragment — are waited for
-    //  together with the first half of the dy fragments, then the rest)
-    bf16x8 af[NT], bfr[KTL];
-    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < KTL; ++j) bfr[j] = __builtin_bit_cast(bf16x8, (u32x4){xb[j][0][0], xb[j][0][1], xb[j][1][0], xb[j][1][1]});
-#pragma unroll
-    for (int i = 0; i < NT / 2; ++i) {
-      af[i] = __builtin_bit_cast(bf16x8, (u32x4){ya[i][0][0], ya[i][0][1], ya[i][1][0], ya[i][1][1]});
-#pragma unroll
-      for (int j = 0; j < KTL; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = NT / 2; i < NT; ++i) {
-      af[i] = __builtin_bit_cast(bf16x8, (u32x4){ya[i][0][0], ya[i][0][1], ya[i][1][0], ya[i][1][1]});
-#pragma unroll
-      for (int j = 0; j < KTL; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    if (do_cs) {
-#pragma unroll
-      for (int i = 0; i < NT; ++i) csacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], ones, csacc[i], 0, 0, 0);
-    }
-    cur = cur == NST - 1 ? 0 : cur + 1;
-    nxt = nxt == NST - 1 ? 0 : nxt + 1;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  if (do_cs && li == 0) {
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = tn * TN + wn2 * (TN / 2) + i * 16 + g * 4 + r;
-        if (n < a.cs_cols) a.cs[(size_t)split * a.cs_stride + n] = csacc[i][r];
-      }
-  }
-  float* out = a.ws + (size_t)split * a.ws_stride;
-#pragma unroll
-  for (int i = 0; i < NT; ++i) {
-#pragma unroll
-    for (int j = 0; j < KTL; ++j) {
-      const int kcol = tk * TK + wk4 * (TK / 4) + j * 16 + li;
+      const int kcol = tk * TK + wk * (TK / WK) + j * 16 + li;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int n = tn * TN + wn2 * (TN / 2) + i * 16 + g * 4 + r;
@@ -1205,155 +1084,145 @@ __global__ __launch_bounds__(256) void wgrad_reduce_flat_kernel(const float* __r
   }
 }
 
-struct Plan {
-  int TN, TK, tilesN, tilesK, splitM, mchunk, MS;
-  bool ring;
-  bool taps;     // tap-stationary 3x3 kernel: tilesK counts 64-wide INPUT-CHANNEL tiles
+// which kernel family serves a layer (make_plan decides, wgrad_impl dispatches on it)
+enum Route {
+  kStem,      // 7x7 / stride 2 on the 4-channel image: stem_wgrad_kernel (stem.hip)
+  kWindow,    // 3x3, stride 1, padding 1: conv_wgrad_winp_kernel; tilesK counts 64- or 48-wide INPUT-CHANNEL tiles
+  kTaps,      // other 3x3: conv_wgrad_taps_kernel; tilesK counts 64-wide INPUT-CHANNEL tiles
+  kRing,      // pointwise: conv_wgrad_ring_kernel (the only family that also gives the bias gradient)
+  kTwoBuf     // everything else: conv_wgrad_kernel
 };
 
-static int taps_target() {    // TOK_WGRAD_TAPS_WGS=<n>: workgroups the split aims at (default 256; 512 is faster in isolation, 256 on the step)
-  static const int v = [] { const char* e = getenv("TOK_WGRAD_TAPS_WGS"); return (int)(e ? atoi(e) : 256); }();
-  return v;
-}
+struct Plan {
+  Route route;
+  int TN, TK, tilesN, tilesK, splitM, mchunk, MS;
+};
 
-static int ring_target() {    // TOK_WGRAD_WGS=<n>: workgroups the split aims at (default: what is resident at once)
-  static const int v = [] { const char* e = getenv("TOK_WGRAD_WGS"); return (int)(e ? atoi(e) : 0); }();
-  return v;
+// Cuts M reduction rows into splits of whole MS-row stages so that `tiles` output tiles give about `target` workgroups: at least
+// 8 stages per workgroup, at most `cap` splits.  Sets splitM and mchunk (rows per split).
+static void split_m(Plan& p, long long M, int target, int tiles, int MS, int cap) {
+  long long split = (target + tiles - 1) / tiles;
+  const long long max_split = (M + 8 * MS - 1) / (8 * MS);
+  if (split > max_split) split = max_split;
+  if (split > cap) split = cap;
+  if (split < 1) split = 1;
+  long long chunk = (M + split - 1) / split;
+  chunk = (chunk + MS - 1) / MS * MS;
+  p.mchunk = (int)chunk;
+  p.splitM = (int)((M + chunk - 1) / chunk);
 }
 
 Plan make_plan(const tok_conv_desc* d) {
   Plan p;
   const int Ktot = d->r * d->s_pad * d->c;
   const long long M = (long long)d->n * d->p * d->q;
-  // the ring pays on the streaming (pointwise) layers; 3x3 / strided layers are LDS-read bound and keep the 64-row
-  // two-buffer kernel (measured per layer, tools/bench_conv.py: ring 3x3 0.9-2x slower)
-  p.taps = false;
-  // (64-wide channel tiles; widths that are multiples of 48 but not of 64 — HRNet's 48 / 96 — take the 48-wide form of the
-  //  window kernel on stride-1 layers and stay on the two-buffer kernel otherwise)
-  const bool same3 = d->r == 3 && d->s == 3 && d->s_pad == 3 && d->stride == 1 && d->pad == 1 &&
+  const bool is3x3 = d->r == 3 && d->s == 3 && d->s_pad == 3;
+  const bool pointwise = d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0;
+  // the window kernel parks its idle DMA lanes at 2^31 + 2^30: tensors below 1 GiB only
+  const bool same3 = is3x3 && d->stride == 1 && d->pad == 1 &&
                      (unsigned long long)d->n * d->h * d->w * d->c * 2 < 0x40000000ull &&
                      (unsigned long long)d->n * d->p * d->q * d->k * 2 < 0x40000000ull;
+  // (64-wide channel tiles; widths that are multiples of 48 but not of 64 — HRNet's 48 / 96 — take the 48-wide form of the
+  //  window kernel on stride-1 layers and stay on the two-buffer kernel otherwise)
   const bool w64 = d->c % 64 == 0 && d->k % 64 == 0;
-  const bool w48 = !w64 && d->c % 48 == 0 && d->k % 48 == 0 && same3;   // window kernel only
-  if (d->c != 4 && (w64 || w48) && d->r == 3 && d->s == 3 && d->s_pad == 3) {
-    p.taps = true; p.ring = false;
+  const bool w48 = !w64 && d->c % 48 == 0 && d->k % 48 == 0 && same3;
+  if (d->c != 4 && (w64 || w48) && is3x3) {
+    // TOK_WGRAD_TAPS_WGS=<n>: workgroups the split aims at (default 256; 512 is faster in isolation, 256 on the step)
+    static const int target = tok_env_int("TOK_WGRAD_TAPS_WGS", 256);
+    // (window kernel, probe of round 6: asking for 160 KB of LDS — no LDS-using workgroup of another kernel beside it — costs
+    //  HRNet-W48 +1.2 ms and ResNet-50 +0.13 ms per step: the co-residency of the main stream's kernels is worth more than an
+    //  undisturbed CU; profiles/r06_wgrad_winp_ab.txt)
+    p.route = same3 && d->p == d->h && d->q == d->w ? kWindow : kTaps;
     p.TN = w64 ? 64 : 48; p.TK = p.TN; p.MS = 32;
     p.tilesN = tok_cdiv(d->k, p.TN);
     p.tilesK = tok_cdiv(d->c, p.TN);
-    const int tiles = p.tilesN * p.tilesK;
-    long long split = (taps_target() + tiles - 1) / tiles;
-    const long long max_split = (M + 8 * 32 - 1) / (8 * 32);        // at least 8 stages per workgroup
-    if (split > max_split) split = max_split;
-    if (split > 512) split = 512;
-    if (split < 1) split = 1;
-    long long chunk = (M + split - 1) / split;
-    chunk = ((chunk + 31) / 32) * 32;
-    p.mchunk = (int)chunk;
-    p.splitM = (int)((M + chunk - 1) / chunk);
+    split_m(p, M, target, p.tilesN * p.tilesK, 32, 512);
     return p;
   }
-  p.ring = d->c != 4 && d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0;
-  if (p.ring) {
+  // the ring pays on the streaming (pointwise) layers; 3x3 / strided layers are LDS-read bound and keep the 64-row
+  // two-buffer kernel (measured per layer, tools/bench_conv.py: ring 3x3 0.9-2x slower)
+  if (d->c != 4 && pointwise) {
     // ring kernel: 32 reduction rows per stage, three stages.  Narrow layers take a 64 x 256 / 256 x 64 tile.
-    p.MS = 32;
+    p.route = kRing; p.MS = 32;
     if (d->k <= 64) { p.TN = 64; p.TK = Ktot >= 256 ? 256 : (Ktot >= 128 ? 128 : 64); }
     else if (Ktot <= 64) { p.TK = 64; p.TN = d->k >= 256 ? 256 : 128; }
     else { p.TN = 128; p.TK = 128; }
-    // wide outputs AND deep filters over very many pixels: 256 x 256 tiles on eight waves (conv_wgrad_ring8_kernel: half the staged
-    // bytes per MAC) where the ragged edge tiles waste at most a third of the work.  Measured per call (tools/ubench/
-    // wgrad256_check.py, same dW to fp32 summation order): HRNet-W48's 720 x 720 neck convolution over 786 432 pixels 1829 ->
-    // 1479 us; on the 12 544 ... 50 176-pixel layers of ResNet-50 / SwinV2-T the 128 x 128 plan wins (99 vs 152 us at
-    // 384 x 1536: twice the partial-slab bytes, one workgroup per CU, a barrier per 32 MFMAs) — hence the pixel threshold.
+    // wide outputs AND deep filters over very many pixels: 256 x 256 tiles on eight waves (half the staged bytes per MAC) where
+    // the ragged edge tiles waste at most a third of the work.  Measured per call (tools/ubench/wgrad256_check.py, same dW to
+    // fp32 summation order): HRNet-W48's 720 x 720 neck convolution over 786 432 pixels 1829 -> 1479 us; on the 12 544 ...
+    // 50 176-pixel layers of ResNet-50 / SwinV2-T the 128 x 128 plan wins (99 vs 152 us at 384 x 1536: twice the partial-slab
+    // bytes, one workgroup per CU, a barrier per 32 MFMAs) — hence the pixel threshold.
     // TOK_WGRAD_256=0 keeps the 128 x 128 plan everywhere, =2 lowers the threshold to 8192 pixels (A/B, tests).
-    static const int big = [] { const char* e = getenv("TOK_WGRAD_256"); return (int)(e ? atoi(e) : 1); }();
-    if (big && d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->k >= 256 && Ktot >= 256 && M >= (big >= 2 ? 8192 : 200000) &&
+    static const int big = tok_env_int("TOK_WGRAD_256", 1);
+    if (big && d->k >= 256 && Ktot >= 256 && M >= (big >= 2 ? 8192 : 200000) &&
         (long long)tok_cdiv(d->k, 256) * tok_cdiv(Ktot, 256) * 65536 * 2 <= (long long)d->k * Ktot * 3) {
       p.TN = 256; p.TK = 256;
     }
     p.tilesN = tok_cdiv(d->k, p.TN);
     p.tilesK = tok_cdiv(Ktot, p.TK);
-    const int tiles = p.tilesN * p.tilesK;
     const int stage = 32 * (p.TN + p.TK) * 2;
     const int per_cu = (160 * 1024) / (3 * stage);                 // LDS-resident workgroups per CU
     // (split target: what is resident at once was 768 workgroups on the 128 x 128 tile; 512 measured better on the step — the
     //  partial-sum slabs are a third smaller and the side stream leaves more of every CU to the main chain:
     //  ResNet-50 19.93 -> 19.38 ms/step together with the tap kernels' 256, tools/ubench/sweep_r02.sh)
-    static const int long_target = [] { const char* e = getenv("TOK_WGRAD_WGS_LONG"); return (int)(e ? atoi(e) : 0); }();   // TOK_WGRAD_WGS_LONG=<n>: split target of the long-M layers (>= 100 k rows: the main-stream launches)
+    // TOK_WGRAD_WGS=<n>: workgroups the split aims at; TOK_WGRAD_WGS_LONG=<n>: the same for the long-M layers alone (>= 100 k
+    // rows: the main-stream launches)
+    static const int ring_target = tok_env_int("TOK_WGRAD_WGS", 0), long_target = tok_env_int("TOK_WGRAD_WGS_LONG", 0);
     const int target = (long_target > 0 && M >= 100000) ? long_target
-                       : ring_target() > 0 ? ring_target() : 256 * (per_cu > 2 ? 2 : per_cu);
-    long long split = (target + tiles - 1) / tiles;
-    const long long max_split = (M + 8 * 32 - 1) / (8 * 32);        // at least 8 stages per workgroup
-    if (split > max_split) split = max_split;
-    if (split > 512) split = 512;
-    if (split < 1) split = 1;
-    long long chunk = (M + split - 1) / split;
-    chunk = ((chunk + 31) / 32) * 32;
-    p.mchunk = (int)chunk;
-    p.splitM = (int)((M + chunk - 1) / chunk);
+                       : ring_target > 0 ? ring_target : 256 * (per_cu > 2 ? 2 : per_cu);
+    split_m(p, M, target, p.tilesN * p.tilesK, 32, 512);
     return p;
   }
+  // the stem kernel writes one slab per workgroup: it takes the two-buffer kernel's split
+  p.route = stem_wgrad_serves(d) ? kStem : kTwoBuf;
   p.TN = d->k >= 128 ? 128 : 64;
   p.TK = Ktot >= 128 ? 128 : 64;
   // (a 128 x 256 tile for deep filters was measured: no gain — the loop is LDS-write bound, not barrier bound)
   p.tilesN = tok_cdiv(d->k, p.TN);
   p.tilesK = tok_cdiv(Ktot, p.TK);
   const int tiles = p.tilesN * p.tilesK;
-  static const int tb_target = [] { const char* e = getenv("TOK_WGRAD_2BUF_WGS"); return (int)(e ? atoi(e) : 1024); }();     // TOK_WGRAD_2BUF_WGS=<n>: workgroups the split of the two-buffer kernel aims at
-  long long split = (tb_target + tiles - 1) / tiles;  // aim at ~4 workgroups per CU
   // reduction rows per barrier: 64 on the long-M layers (twice the MFMAs per barrier), 32 where M is
   // short and occupancy (4 workgroups per CU instead of 2) matters more
   p.MS = (M >= 100000 && p.TN == 128 && p.TK == 128) ? 64 : 32;
-  const long long max_split = (M + 8 * p.MS - 1) / (8 * p.MS);   // at least 8 steps per workgroup
-  if (split > max_split) split = max_split;
-  // (512 only for the stem — 2 tiles over 3.2 M pixels at B = 256: 512 workgroups left every CU with 2 and the launch
-  //  latency-bound; every other layer keeps its partition, and with it its summation order)
-  const long long cap = (d->c == 4 && tiles <= 2) ? 512 : 256;
-  if (split > cap) split = cap;
-  if (split < 1) split = 1;
-  long long chunk = (M + split - 1) / split;
-  chunk = ((chunk + p.MS - 1) / p.MS) * p.MS;
-  p.mchunk = (int)chunk;
-  p.splitM = (int)((M + chunk - 1) / chunk);
+  // TOK_WGRAD_2BUF_WGS=<n>: workgroups the split aims at (default: ~4 per CU).  Cap 256; 512 only for the stem — 2 tiles over
+  // 3.2 M pixels at B = 256: 512 workgroups left every CU with 2 and the launch latency-bound; every other layer keeps its
+  // partition, and with it its summation order
+  static const int target = tok_env_int("TOK_WGRAD_2BUF_WGS", 1024);
+  split_m(p, M, target, tiles, p.MS, (d->c == 4 && tiles <= 2) ? 512 : 256);
   return p;
 }
 
-template <int TN, int TK>
+template <int TN, int TK, int WK>
 void launch_ring(const WgradArgs& a, hipStream_t st) {
   constexpr int smem = 3 * 32 * (TN + TK) * 2;
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ring_kernel<TN, TK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
-  hipLaunchKernelGGL((conv_wgrad_ring_kernel<TN, TK>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(256), smem, st, a);
-}
-
-template <int TN, int TK, bool C4, int MS, bool PWK>
-void launch_wgrad_pw(const WgradArgs& a, hipStream_t st) {
-  constexpr int smem = 2 * MS * ((TN + 16) * 2 + (TK + 16) * 2);   // (the unpadded DMA layout needs less)
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TN, TK, C4, MS, PWK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
-  hipLaunchKernelGGL((conv_wgrad_kernel<TN, TK, C4, MS, PWK>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(256),
-                     smem, st, a);
+  tok_launch_lds<&conv_wgrad_ring_kernel<TN, TK, WK>>(smem, dim3(a.tilesN * a.tilesK * a.splitM), dim3(128 * WK), smem, st, a);
 }
 
 template <int TN, int TK, bool C4, int MS>
-void launch_wgrad_ms(const WgradArgs& a, hipStream_t st) {
-  if constexpr (!C4) {
-    if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) { launch_wgrad_pw<TN, TK, C4, MS, true>(a, st); return; }
+void launch_2buf_ms(const WgradArgs& a, hipStream_t st) {
+  constexpr int smem = 2 * MS * ((TN + 16) * 2 + (TK + 16) * 2);   // (the unpadded DMA layout needs less)
+  const dim3 grid(a.tilesN * a.tilesK * a.splitM);
+  if constexpr (!C4) {   // 1x1, stride 1, no padding: the form without a row cursor
+    if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) {
+      tok_launch_lds<&conv_wgrad_kernel<TN, TK, C4, MS, true>>(smem, grid, dim3(256), smem, st, a);
+      return;
+    }
   }
-  launch_wgrad_pw<TN, TK, C4, MS, false>(a, st);
+  tok_launch_lds<&conv_wgrad_kernel<TN, TK, C4, MS, false>>(smem, grid, dim3(256), smem, st, a);
 }
 
 template <int TN, int TK, bool C4>
-void launch_wgrad(const WgradArgs& a, hipStream_t st, int ms) {
-  if (ms == 64) launch_wgrad_ms<TN, TK, C4, 64>(a, st);
-  else launch_wgrad_ms<TN, TK, C4, 32>(a, st);
+void launch_2buf(const WgradArgs& a, hipStream_t st, int ms) {
+  if (ms == 64) launch_2buf_ms<TN, TK, C4, 64>(a, st);
+  else launch_2buf_ms<TN, TK, C4, 32>(a, st);
+}
+
+template <bool C4>
+void launch_2buf_tile(const Plan& p, const WgradArgs& a, hipStream_t st) {
+  if (p.TN == 128 && p.TK == 128) launch_2buf<128, 128, C4>(a, st, p.MS);
+  else if (p.TN == 128) launch_2buf<128, 64, C4>(a, st, p.MS);
+  else if (p.TK == 128) launch_2buf<64, 128, C4>(a, st, p.MS);
+  else launch_2buf<64, 64, C4>(a, st, p.MS);
 }
 
 }  // namespace
@@ -1366,7 +1235,7 @@ extern "C" size_t tok_conv_wgrad_ws_bytes(const tok_conv_desc* d) {
 
 extern "C" int tok_conv_wgrad_bias_ok(const tok_conv_desc* d) {
   if (d == nullptr || d->c == 4) return 0;
-  return make_plan(d).ring ? 1 : 0;
+  return make_plan(d).route == kRing ? 1 : 0;
 }
 
 extern "C" size_t tok_conv_wgrad_bias_ws_bytes(const tok_conv_desc* d) {
@@ -1436,64 +1305,34 @@ int wgrad_impl(const tok_conv_desc* d, const void* x, const void* dy, float* dw,
     a.x_bytes = (uint32_t)xb; a.dy_bytes = (uint32_t)yb;
   }
   hipStream_t st = tok_stream(stream);
-  const bool c4 = d->c == 4;
-  if (c4 && dbias == nullptr && stem_wgrad_serves(d)) {
-    // the 7x7 / stride 2 stem: transpose reads straight from a shared input window (stem.hip); one slab per workgroup
-    stem_wgrad_launch(d, x, dy, a.ws, p.splitM, st);
-  } else
-  if (p.taps) {
-    constexpr int smem = 3 * 10 * 32 * 128;
-    static const bool attr_set = [&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_taps_kernel<0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-      return true;
-    }();   // once per process (thread-safe function-local static)
-    (void)attr_set;
-    // stride 1 / "same" padding: the shared-window kernel (its idle DMA lanes sit at 2^31 + 2^30: tensors below 1 GiB — make_plan
-    // sends 48-wide layers elsewhere above that, 64-wide ones take the per-tap kernel below)
-    const bool same = a.stride == 1 && a.pad == 1 && a.P == a.H && a.Q == a.W && a.x_bytes < 0x40000000u && a.dy_bytes < 0x40000000u;
-    if (same) {
-      // (probe, round 6: asking for 160 KB of LDS — no LDS-using workgroup of another kernel beside this one — costs HRNet-W48 +1.2 ms and
-      //  ResNet-50 +0.13 ms per step: the co-residency of the main stream's kernels is worth more than an undisturbed CU;
-      //  profiles/r06_wgrad_winp_ab.txt)
-      constexpr int smem_p = 3 * (32 * 128 + 128 * 128);
-      static const bool attr_p = [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_winp_kernel<4, 3, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_p);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_winp_kernel<3, 3, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, smem_p);
-        return true;
-      }();   // once per process (thread-safe function-local static)
-      (void)attr_p;
-      const dim3 gw(a.tilesN * a.tilesK * a.splitM);
-      if (p.TN == 48) hipLaunchKernelGGL((conv_wgrad_winp_kernel<3, 3, 7>), gw, dim3(256), smem_p, st, a);
-      else hipLaunchKernelGGL((conv_wgrad_winp_kernel<4, 3, 9>), gw, dim3(256), smem_p, st, a);
-    } else {
-      hipLaunchKernelGGL((conv_wgrad_taps_kernel<0>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(256), smem, st, a);
+  const dim3 grid(a.tilesN * a.tilesK * a.splitM);
+  switch (p.route) {
+    case kStem:      // transpose reads straight from a shared input window; one slab per workgroup (never with dbias: not a ring layer)
+      stem_wgrad_launch(d, x, dy, a.ws, p.splitM, st);
+      break;
+    case kWindow: {
+      constexpr int smem = 3 * (32 * 128 + 128 * 128);
+      if (p.TN == 48) tok_launch_lds<&conv_wgrad_winp_kernel<3, 3, 7>>(smem, grid, dim3(256), smem, st, a);
+      else tok_launch_lds<&conv_wgrad_winp_kernel<4, 3, 9>>(smem, grid, dim3(256), smem, st, a);
+      break;
     }
-  } else if (p.ring) {
-    if (p.TN == 256 && p.TK == 256) {
-      constexpr int smem8 = 3 * 32 * (256 + 256) * 2;
-      static const bool attr8 = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_ring8_kernel<256, 256>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, smem8);
-        return true;
-      }();
-      (void)attr8;
-      hipLaunchKernelGGL((conv_wgrad_ring8_kernel<256, 256>), dim3(a.tilesN * a.tilesK * a.splitM), dim3(512), smem8, st, a);
+    case kTaps: {
+      constexpr int smem = 3 * 10 * 32 * 128;
+      tok_launch_lds<&conv_wgrad_taps_kernel<0>>(smem, grid, dim3(256), smem, st, a);
+      break;
     }
-    else if (p.TN == 64 && p.TK == 64) launch_ring<64, 64>(a, st);
-    else if (p.TN == 64 && p.TK == 128) launch_ring<64, 128>(a, st);
-    else if (p.TN == 64 && p.TK == 256) launch_ring<64, 256>(a, st);
-    else if (p.TN == 128 && p.TK == 64) launch_ring<128, 64>(a, st);
-    else if (p.TN == 256 && p.TK == 64) launch_ring<256, 64>(a, st);
-    else launch_ring<128, 128>(a, st);
-  } else if (p.TN == 128 && p.TK == 128) {
-    if (c4) launch_wgrad<128, 128, true>(a, st, p.MS); else launch_wgrad<128, 128, false>(a, st, p.MS);
-  } else if (p.TN == 128) {
-    if (c4) launch_wgrad<128, 64, true>(a, st, p.MS); else launch_wgrad<128, 64, false>(a, st, p.MS);
-  } else if (p.TK == 128) {
-    if (c4) launch_wgrad<64, 128, true>(a, st, p.MS); else launch_wgrad<64, 128, false>(a, st, p.MS);
-  } else {
-    if (c4) launch_wgrad<64, 64, true>(a, st, p.MS); else launch_wgrad<64, 64, false>(a, st, p.MS);
+    case kRing:
+      if (p.TN == 256 && p.TK == 256) launch_ring<256, 256, 4>(a, st);
+      else if (p.TN == 64 && p.TK == 64) launch_ring<64, 64, 2>(a, st);
+      else if (p.TN == 64 && p.TK == 128) launch_ring<64, 128, 2>(a, st);
+      else if (p.TN == 64 && p.TK == 256) launch_ring<64, 256, 2>(a, st);
+      else if (p.TN == 128 && p.TK == 64) launch_ring<128, 64, 2>(a, st);
+      else if (p.TN == 256 && p.TK == 64) launch_ring<256, 64, 2>(a, st);
+      else launch_ring<128, 128, 2>(a, st);
+      break;
+    case kTwoBuf:
+      if (d->c == 4) launch_2buf_tile<true>(p, a, st); else launch_2buf_tile<false>(p, a, st);
+      break;
   }
   TOK_CHECK_LAUNCH("tok_conv_wgrad");
   if (dbias != nullptr && !cs_inline) {

@@ -338,13 +338,7 @@ int pick_wbn(int K, long long ptiles) {
 
 template <int TW, int BN>
 void launch_variant(const ConvArgs& a, const WinGeo& g, int grid, hipStream_t st) {
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_win_kernel<TW, BN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              win_smem(BN));
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
-  hipLaunchKernelGGL((conv_win_kernel<TW, BN>), dim3(grid), dim3(256), win_smem(BN), st, a, g);
+  tok_launch_lds<&conv_win_kernel<TW, BN>>(win_smem(BN), dim3(grid), dim3(256), win_smem(BN), st, a, g);
 }
 
 }  // namespace

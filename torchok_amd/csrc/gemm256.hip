@@ -319,22 +319,14 @@ int gemm256_rows(const ConvArgs& a) { return (tok_cdiv(a.M, GT) + 7) / 8 * 8; }
 
 int gemm256_launch(ConvArgs& a, hipStream_t st) {
   constexpr int smem = 2 * STAGE_B + 2 * 4 * GT * 4;
-  static const bool attr_set = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return true;
-  }();
-  (void)attr_set;
   a.gridM = tok_cdiv(a.M, GT);
   a.gridN = tok_cdiv(a.K, GT);
   a.stat_rows = gemm256_rows(a);
   const int tiles = a.gridM * a.gridN;
   const int grid = tiles < 256 ? tiles : 256;          // one workgroup per CU, walking tiles
-  if (a.mask_store) hipLaunchKernelGGL(gemm256_kernel<3>, dim3(grid), dim3(512), smem, st, a);
-  else if (a.stats == nullptr) hipLaunchKernelGGL(gemm256_kernel<0>, dim3(grid), dim3(512), smem, st, a);
-  else if (a.bn_y == nullptr) hipLaunchKernelGGL(gemm256_kernel<1>, dim3(grid), dim3(512), smem, st, a);
-  else hipLaunchKernelGGL(gemm256_kernel<2>, dim3(grid), dim3(512), smem, st, a);
+  if (a.mask_store) tok_launch_lds<&gemm256_kernel<3>>(smem, dim3(grid), dim3(512), smem, st, a);
+  else if (a.stats == nullptr) tok_launch_lds<&gemm256_kernel<0>>(smem, dim3(grid), dim3(512), smem, st, a);
+  else if (a.bn_y == nullptr) tok_launch_lds<&gemm256_kernel<1>>(smem, dim3(grid), dim3(512), smem, st, a);
+  else tok_launch_lds<&gemm256_kernel<2>>(smem, dim3(grid), dim3(512), smem, st, a);
   return 0;
 }

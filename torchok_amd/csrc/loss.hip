@@ -725,17 +725,9 @@ extern "C" int tok_upsample_ce_bwd(const void* low, int n, int hs, int ws, int c
     const int tiles_y = tok_cdiv(hs, UT), tiles_x = tok_cdiv(ws, UT);
     const int tgrid = n * tiles_y * tiles_x;
     const int smem = UWIN * UWIN * ld * 2;
-#define UPCE_TILED_LAUNCH(NV)                                                                                                          \
-    {                                                                                                                               \
-      static const bool attr_set = [] {                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upce_bwd_tiled_kernel<NV>),                                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, UWIN * UWIN * NV * 16);                               \
-        return true;                                                                                                                \
-      }();                                                                                                                          \
-      (void)attr_set;                                                                                                               \
-      hipLaunchKernelGGL(upce_bwd_tiled_kernel<NV>, dim3(tgrid), dim3(256), smem, st, (const bf16*)low, target, a, ignore_index,    \
-                         lse, loss, gscale, (bf16*)dlow, accumulate, tiles_y, tiles_x);                                             \
-    }
+#define UPCE_TILED_LAUNCH(NV)                                                                                                       \
+    tok_launch_lds<&upce_bwd_tiled_kernel<NV>>(UWIN * UWIN * NV * 16, dim3(tgrid), dim3(256), smem, st, (const bf16*)low, target, a, \
+                                               ignore_index, lse, loss, gscale, (bf16*)dlow, accumulate, tiles_y, tiles_x);
     switch (ld >> 3) {
       case 1: UPCE_TILED_LAUNCH(1) break;
       case 2: UPCE_TILED_LAUNCH(2) break;

@@ -457,18 +457,12 @@ template <int C, int HC, int NT, int WAVES, bool PF, int MODE, bool SAVE, int RD
 void launch_v(const MlpArgs& a, hipStream_t st) {
   constexpr int STAGE = (HC / 32) * (2 * (C / 32) + C / 16) * 1024;
   const int smem = 3 * STAGE + (MODE == 0 ? (a.H + C) * 4 : 0);
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_kernel<C, HC, NT, WAVES, PF, MODE, SAVE, RD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
   MlpArgs b = a;
   constexpr int TILE = WAVES * NT * 16;
   b.ntiles = (a.T + TILE - 1) / TILE;
   const int cap = 256 * mlp_min_blocks<C, NT, WAVES>();
   const int grid = b.ntiles < cap ? b.ntiles : cap;
-  hipLaunchKernelGGL((mlp_kernel<C, HC, NT, WAVES, PF, MODE, SAVE, RD>), dim3(grid), dim3(WAVES * 64), smem, st, b);
+  tok_launch_lds<&mlp_kernel<C, HC, NT, WAVES, PF, MODE, SAVE, RD>>(smem, dim3(grid), dim3(WAVES * 64), smem, st, b);
 }
 
 template <int C, int HC, int NT, int WAVES, bool PF, int MODE, int RD = 3>

@@ -433,12 +433,6 @@ template <int BN, bool BNEP>
 int launch_ring(const PwArgs& a, hipStream_t st) {
   constexpr int STAGE = BM * BK * 2 + BN * BK * 2 + (BN == 64 ? 1024 : 4096);
   constexpr int smem = 3 * STAGE;
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_gemm_ring_kernel<BN, BNEP>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
   const int KT1 = tok_cdiv(a.C, BK);
   const int KT = KT1 + (a.x2 != nullptr ? tok_cdiv(a.C2, BK) : 0);
   const int SPT = KT + (a.e1 ? 1 : 0) + (a.e2 ? 1 : 0);
@@ -456,8 +450,8 @@ int launch_ring(const PwArgs& a, hipStream_t st) {
     fd_w = make_pwdiv((uint32_t)a.sub_W);
   }
   const int grid = pw_ring_grid(BN, a.gridM, a.gridN);
-  hipLaunchKernelGGL((pw_gemm_ring_kernel<BN, BNEP>), dim3(grid), dim3(256), smem, st, a, (uint32_t)xb, (uint32_t)wb, (uint32_t)yb,
-                     (uint32_t)mb, KT, SPT, (uint32_t)e1b, fd_hw, fd_w, (uint32_t)x2b, (uint32_t)w2b, KT1);
+  tok_launch_lds<&pw_gemm_ring_kernel<BN, BNEP>>(smem, dim3(grid), dim3(256), smem, st, a, (uint32_t)xb, (uint32_t)wb, (uint32_t)yb,
+                                                 (uint32_t)mb, KT, SPT, (uint32_t)e1b, fd_hw, fd_w, (uint32_t)x2b, (uint32_t)w2b, KT1);
   return 0;
 }
 

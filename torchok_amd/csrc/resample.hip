@@ -846,13 +846,7 @@ extern "C" int tok_bilinear_bwd_multi(const void* ddst, int n, int hd, int wd, i
   }
   if (present == 0) return TOK_OK;
   if (fast) {
-    static const bool attr_set = [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bilinear_adj3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ADJ_SMEM);
-      return true;
-    }();
-    (void)attr_set;
-    hipLaunchKernelGGL(bilinear_adj3_kernel, dim3(n * (hd / ADJ_T) * (wd / ADJ_T)), dim3(256), ADJ_SMEM, tok_stream(stream), a);
+    tok_launch_lds<&bilinear_adj3_kernel>(ADJ_SMEM, dim3(n * (hd / ADJ_T) * (wd / ADJ_T)), dim3(256), ADJ_SMEM, tok_stream(stream), a);
     TOK_CHECK_LAUNCH("tok_bilinear_bwd_multi");
     return TOK_OK;
   }

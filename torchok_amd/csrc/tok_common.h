@@ -43,7 +43,8 @@ static inline hipStream_t tok_stream(void* s) { return reinterpret_cast<hipStrea
 // TOK_DBG_SKIP=<bitmask>: ablation probe for step-time budgeting (tools/ubench/runs/*): the named launches are NOT issued, results are
 // garbage, only the step time means something (an upper bound on what removing / folding that launch class can buy).
 //   1 BatchNorm finalizes (forward + backward)   2 wgrad_reduce_flat   4 fused-unit helpers (Gram finalize, prepare rows, Wb) + colsum_f32
-//   8 BatchNorm apply passes (bn_act_fwd, bn_bwd_apply)   16 every weight-gradient launch   32 optimizer + repack
+//   8 BatchNorm apply passes (bn_act_fwd, bn_bwd_apply)   16 every weight-gradient launch
+//   32 BatchNorm apply passes of units without activation (bn.hip)
 #include <stdlib.h>
 // A process that runs with it set says so once on stderr: the launches it names return TOK_OK without running.
 inline int tok_dbg_skip(int bit) {   // (inline, not static: ONE instance and one warning per process)
@@ -58,6 +59,21 @@ inline int tok_dbg_skip(int bit) {   // (inline, not static: ONE instance and on
   return v & bit;
 }
 static inline int tok_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// integer knob from the environment; callers keep it in a function-local static, so it is read once per process
+static inline int tok_env_int(const char* name, int dflt) { const char* e = getenv(name); return (int)(e ? atoi(e) : dflt); }
+
+// Launch of a kernel that may need more than 64 KB of dynamic LDS.  Above 64 KB a kernel has to opt in through
+// hipFuncAttributeMaxDynamicSharedMemorySize: every instantiation does so at its first launch, once per process (thread-safe
+// function-local static).  `max_bytes` is the limit asked for, `bytes` what this launch uses (the same number at most sites).
+template <auto Kernel, typename... Args>
+void tok_launch_lds(int max_bytes, dim3 grid, dim3 block, size_t bytes, hipStream_t st, const Args&... args) {
+  static const bool armed = [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
+    return true;
+  }();
+  (void)armed;
+  hipLaunchKernelGGL(Kernel, grid, block, bytes, st, args...);
+}
 
 // ---- device helpers -----------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
@@ -91,30 +107,6 @@ __device__ __forceinline__ float tok_gelu_tail(float a) {   // Phi(-a), 0 <= a <
   q = fmaf(q, a, TOK_GELU_C0);
   return __builtin_amdgcn_exp2f(q);
 }
-#ifdef TOK_GELU_AS726   // A/B: the Abramowitz-Stegun 7.1.26 form (rcp + exp per element)
-__device__ __forceinline__ float tok_erf_core(float z, float& gauss) {
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.0f));
-  float p = fmaf(t, 1.061405429f, -1.453152027f);
-  p = fmaf(t, p, 1.421413741f);
-  p = fmaf(t, p, -0.284496736f);
-  p = fmaf(t, p, 0.254829592f);
-  p *= t;
-  gauss = __builtin_amdgcn_exp2f(az * az * -1.4426950408889634f);
-  return fmaf(-p, gauss, 1.0f);
-}
-__device__ __forceinline__ float gelu_f(float x) {
-  float g;
-  const float e = copysignf(tok_erf_core(x * 0.70710678118654752f, g), x);
-  const float hx = 0.5f * x;
-  return fmaf(hx, e, hx);
-}
-__device__ __forceinline__ float gelu_d(float x) {
-  float g;
-  const float e = copysignf(tok_erf_core(x * 0.70710678118654752f, g), x);
-  return fmaf(x * 0.3989422804014327f, g, fmaf(0.5f, e, 0.5f));
-}
-#else
 __device__ __forceinline__ float gelu_f(float x) {
   const float a = __builtin_amdgcn_fmed3f(fabsf(x), 0.f, TOK_GELU_AMAX);
   const float m = __builtin_amdgcn_fmed3f(x, 0.f, __builtin_inff());
@@ -127,7 +119,6 @@ __device__ __forceinline__ float gelu_d(float x) {           // Phi(x) + x phi(x
   const float pdf = __builtin_amdgcn_exp2f(fmaf(x * x, -0.72134752044448170f, -1.3257480647361593f));
   return fmaf(x, pdf, cdf);
 }
-#endif
 // two elements per instruction where the ISA has a packed form
 __device__ __forceinline__ f32x2 tok_gelu_tail2(f32x2 a) {
   f32x2 q = __builtin_elementwise_fma(a, (f32x2)(TOK_GELU_C5), (f32x2)(TOK_GELU_C4));

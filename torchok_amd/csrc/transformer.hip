@@ -1383,14 +1383,8 @@ extern "C" int tok_window_attn_fwd(const void* qkv, int batch, int h, int w, int
   }
   const size_t smem = (size_t)a.N * HD * 3 * sizeof(float);
   TOK_CHECK_ARG(smem <= 160 * 1024, "tok_window_attn_fwd: window %d too large", ws);
-  static const bool attr = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr;
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3(batch * a.nW * heads), dim3(64), smem, tok_stream(stream), a,
-                     (const bf16*)qkv, logit_scale, bias, mask, (bf16*)out, lse);
+  tok_launch_lds<&attn_fwd_kernel>(160 * 1024, dim3(batch * a.nW * heads), dim3(64), smem, tok_stream(stream), a,
+                                   (const bf16*)qkv, logit_scale, bias, mask, (bf16*)out, lse);
   TOK_CHECK_LAUNCH("tok_window_attn_fwd");
   return TOK_OK;
 }
@@ -1418,29 +1412,17 @@ extern "C" int tok_window_attn_bwd(const void* qkv, const void* dout, int batch,
   if (a.N <= 64) {
     const int bpw = attn_bpw(a);
     const int waves = tok_cdiv(batch, bpw) * a.nW * heads;
-    static const bool attr_m = [&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      return true;
-    }();   // once per process (thread-safe function-local static)
-    (void)attr_m;
-    hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(8 * tok_cdiv(waves, 8)), dim3(256), MFMA_BWD_LDS, tok_stream(stream), a,
-                       (const bf16*)qkv, (const bf16*)dout, logit_scale, bias, mask, lse, (bf16*)dqkv, ds_scratch, dscale_part, bpw,
-                       waves);
+    tok_launch_lds<&attn_bwd_mfma_kernel>(160 * 1024, dim3(8 * tok_cdiv(waves, 8)), dim3(256), MFMA_BWD_LDS, tok_stream(stream), a,
+                                          (const bf16*)qkv, (const bf16*)dout, logit_scale, bias, mask, lse, (bf16*)dqkv, ds_scratch,
+                                          dscale_part, bpw, waves);
     TOK_CHECK_LAUNCH("tok_window_attn_bwd(mfma)");
     return TOK_OK;
   }
   const size_t smem = ((size_t)a.N * HD * 4 + (size_t)a.N * 4) * sizeof(float);
   TOK_CHECK_ARG(smem <= 160 * 1024, "tok_window_attn_bwd: window %d too large", ws);
-  static const bool attr = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr;
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3(batch * a.nW * heads), dim3(64), smem, tok_stream(stream), a,
-                     (const bf16*)qkv, (const bf16*)dout, logit_scale, bias, mask, lse, (bf16*)dqkv, ds_scratch,
-                     dscale_part);
+  tok_launch_lds<&attn_bwd_kernel>(160 * 1024, dim3(batch * a.nW * heads), dim3(64), smem, tok_stream(stream), a,
+                                   (const bf16*)qkv, (const bf16*)dout, logit_scale, bias, mask, lse, (bf16*)dqkv, ds_scratch,
+                                   dscale_part);
   TOK_CHECK_LAUNCH("tok_window_attn_bwd");
   return TOK_OK;
 }

@@ -485,16 +485,11 @@ extern "C" int tok_bn3_bwd_prepare(const float* G, const float* w, const float* 
   if (tok_dbg_skip(4)) return TOK_OK;
   hipStream_t st = tok_stream(stream);
   const size_t smem = (size_t)PR_CH * p * sizeof(float);
-  static const bool attr_set = [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bn3_prepare_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              PR_CH * 2048 * 4);
-    return true;
-  }();   // once per process (thread-safe function-local static)
-  (void)attr_set;
   float* At = ws;                                   // [k][p + 1]
   float* parts = ws + (size_t)k * (p + 1);          // split-reduction partials of the (p + 1) x p product
-  hipLaunchKernelGGL(bn3_prepare_rows_kernel, dim3(tok_cdiv(k, PR_CH)), dim3(1024), smem, st, G, w, wz, zsum, partial, rows, count,
-                     p, k, gamma, mean, rstd, dgamma, dbeta, param_accumulate, coef, dw, dw_accumulate, (bf16*)wa, At);
+  tok_launch_lds<&bn3_prepare_rows_kernel>(PR_CH * 2048 * 4, dim3(tok_cdiv(k, PR_CH)), dim3(1024), smem, st, G, w, wz, zsum, partial,
+                                           rows, count, p, k, gamma, mean, rstd, dgamma, dbeta, param_accumulate, coef, dw, dw_accumulate,
+                                           (bf16*)wa, At);
   TOK_CHECK_LAUNCH("tok_bn3_bwd_prepare(rows)");
   // [wb ; cvec] = At^T W_bf16   ((p + 1) x p, reduction over k)
   if (p == 64 || p == 128 || p == 256) {
