@@ -6,10 +6,11 @@ Guards.  Every operand sits in a helpers.GuardedSpan: a guard of at least one fu
 AND behind (halos reach backwards).  Inputs carry NaN there, so a value the kernel does not own that reaches a result - even
 multiplied by a zero weight - fails the bound; outputs carry sentinel bits, asserted unchanged after every call.
 
-Routes.  The routing predicates of the launchers are restated below (at the thresholds tests/conftest.py sets:
-TOK_CONV_WIN_MIN_TILES = TOK_CONV_S2D_MIN_TILES = 1, everything else default).  Every case names the kernel it is meant for; the
-test asserts that the restatement gives that name and that the library's row queries equal the restated ones, so a routing change
-breaks a test instead of silently moving its coverage.  ROUTES_FWD / ROUTES_DGRAD list what must be covered.
+Routes.  The library's route is restated in tests/conv_route_ref.py (at the thresholds tests/conftest.py sets:
+TOK_CONV_WIN_MIN_TILES = TOK_CONV_S2D_MIN_TILES = 1, everything else default; tests/test_conv_route.py compares it with the
+library's queries without a GPU).  Every case names the kernel it is meant for; the test asserts that the restatement gives that
+name and that the library's row queries equal the restated ones, so a routing change breaks a test instead of silently moving
+its coverage.  ROUTES_FWD / ROUTES_DGRAD list what must be covered.
 
 Bounds (derived, not fitted).  bf16 results of an fp32 accumulator: |err| <= 2^-8 |ref| + d 2^-24 mag, `mag` the same operation on
 absolute values, d the fp32 additions on the longest path into one output: the whole reduction length (MFMA's internal order is
@@ -24,12 +25,11 @@ Host cost, measured on 16 CPU threads: the fp64 references of all forward cases 
 (pointwise layers are a matmul); with the element-wise comparisons both contract modules together run in 17 s, the slowest
 case (the 103 488-row ring data gradient with its seven epilogues) in 3 s."""
 import ctypes
-from collections import namedtuple
-
 import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_route_ref import ACT_ROUTES, ROUTES_DGRAD, ROUTES_FWD, pick_bn, pw_serves, route_dgrad, route_fwd
 from helpers import (A_BF, BF, ERR_INVALID, F32, U8, U32, assert_bounded, cdiv, conv_desc as mk, gin, gout, halo_guard, last_error,
                      pack_bits, unpack_bits)
 from torchok_amd import _C
@@ -37,215 +37,6 @@ from torchok_amd.engine.core import stream_ptr
 
 pytestmark = pytest.mark.gpu
 GELU_PHI = 3e-7             # csrc/tok_common.h: |error in Phi| of the GELU polynomial
-
-
-# ---- the routing of csrc/conv_igemm.hip, conv_win.hip, conv_s2d.hip, gemm256.hip, stem.hip and pw_gemm.hip, restated ------------
-WIN_MIN_TILES = S2D_MIN_TILES = 1         # tests/conftest.py
-PW_MIN_ROWS, SHORT_K = 100000, 400        # pw_min_rows(), short_k()
-G256_MIN_TILES, G256_MIN_K = 128, 384     # gemm256_geometry, default rule
-
-Geo = namedtuple('Geo', 'B H W C K R S P Q stride pad M Ktot x_bytes')     # ConvArgs as the launchers fill it
-
-
-def geo_fwd(d):
-    return Geo(d.n, d.h, d.w, d.c, d.k, d.r, d.s_pad, d.p, d.q, d.stride, d.pad, d.n * d.p * d.q, d.r * d.s_pad * d.c,
-               d.n * d.h * d.w * d.c * 2)
-
-
-def geo_dgrad(d):
-    """dgrad_fill: the gathered tensor is dY (p x q x k), the output dX (h x w x c), stride 1, padding r - 1 - pad"""
-    return Geo(d.n, d.p, d.q, d.k, d.c, d.r, d.s, d.h, d.w, 1, d.r - 1 - d.pad, d.n * d.h * d.w, d.r * d.s * d.k,
-               d.n * d.p * d.q * d.k * 2)
-
-
-def pick_bn(n_out, ktot, token_rows=False):
-    if n_out <= 64:
-        return 64
-    if token_rows:
-        return 128
-    return 64 if ktot <= SHORT_K else 128
-
-
-def pw_serves(bn, rows, c_red, n_out):
-    return bn == 64 and rows >= PW_MIN_ROWS and c_red % 8 == 0 and n_out % 64 == 0
-
-
-def _grid(cap, grid_m, grid_n):
-    """plan_grid / pw_ring_grid / conv_win_grid / conv_s2d_grid: `cap` workgroups, never more than the tiles need, in units of
-    8 * gridN"""
-    unit, need = 8 * grid_n, grid_m * grid_n
-    g = cap if need >= cap else cdiv(need, unit) * unit
-    return max(g // unit * unit, unit)
-
-
-def plan_grid(bn, gm, gn, per_cu=0):
-    return _grid(256 * (per_cu or (3 if bn == 64 else 2)), gm, gn)
-
-
-def ring_grid(bn, gm, gn):
-    return _grid(256 * (2 if bn == 64 else 1), gm, gn)
-
-
-def pick_tw(w):
-    return 16 if w <= 16 else (32 if w <= 32 else 64)
-
-
-def pick_wbn(k, ptiles):
-    if k == 48:
-        return 48
-    if k <= 64:
-        return 64
-    if k % 96 == 0 and k % 128 != 0:
-        return 96
-    if k % 96 == 0 and ptiles * (k // 128) <= 256 and ptiles * (k // 96) <= 512:
-        return 96
-    return 128
-
-
-def win_tiles(g):
-    tw = pick_tw(g.W)
-    gm = cdiv((g.M // (g.H * g.W)) * g.H, 256 // tw) * cdiv(g.W, tw)
-    bn = pick_wbn(g.K, gm)
-    return gm, cdiv(g.K, bn), tw, bn
-
-
-def _win_common(g):
-    if g.C % 8 or g.K % 8 or g.K < 32 or g.C < 32 or 64 < g.K < 96 or g.W < 12 or g.x_bytes >= 0x7FFFFFF0:
-        return False
-    return True
-
-
-def win_serves(g, fused=False):
-    if not (g.R == 3 and g.S == 3 and g.stride == 1 and g.pad == 1 and g.H == g.P and g.W == g.Q) or fused:
-        return False
-    gm, gn, _, _ = win_tiles(g)
-    return _win_common(g) and gm * gn >= WIN_MIN_TILES
-
-
-def s2d_tiles(g):
-    tw = pick_tw(g.W)
-    gm = 4 * cdiv((g.M // (g.P * g.Q)) * g.H, 256 // tw) * cdiv(g.W, tw)
-    bn = pick_wbn(g.K, gm)
-    return gm, cdiv(g.K, bn), tw, bn
-
-
-def s2d_serves(g, stride, pad, fused=False):
-    if not (g.R == 3 and g.S == 3 and stride == 2 and pad == 1) or fused:
-        return False
-    if g.P % 2 or g.Q % 2 or g.P != 2 * g.H or g.Q != 2 * g.W:
-        return False
-    gm, gn, _, _ = s2d_tiles(g)
-    return _win_common(g) and gm * gn >= S2D_MIN_TILES
-
-
-def g256_geometry(g):
-    if not (g.R == 1 and g.S == 1 and g.stride == 1 and g.pad == 0 and g.C != 4):
-        return False
-    if g.Ktot % 8 or g.K % 8 or g.Ktot <= 64 or g.K < 192 or g.M < 4096:
-        return False
-    nt = cdiv(g.K, 256)
-    if nt * 256 * 3 > g.K * 4 or cdiv(g.M, 256) * nt < G256_MIN_TILES:
-        return False
-    return g.Ktot >= G256_MIN_K
-
-
-def g256_rows(g):
-    return cdiv(cdiv(g.M, 256), 8) * 8
-
-
-def stem_win_serves(g, bias, fused):
-    if not (g.C == 4 and g.R == 7 and g.S == 8 and g.stride == 2 and g.pad == 3) or g.K % 8 or g.K > 64 or g.W % 2:
-        return False
-    return not bias and not fused and g.B * cdiv(g.P, 16) * cdiv(g.Q, 16) >= 16
-
-
-def _pointwise(g):
-    return g.R == 1 and g.S == 1 and g.stride == 1 and g.pad == 0 and g.C != 4
-
-
-def fwd_route(d, bias=False, act=False, bnep=False):
-    """conv_fwd_impl + launch<>: the kernel a forward entry runs"""
-    g, c4 = geo_fwd(d), d.c == 4
-    bn = pick_bn(d.k, g.Ktot, d.h == 1 and d.w == 1)
-    if c4 and not bnep and stem_win_serves(g, bias, act):
-        return 'stem_win'
-    if not c4 and not bnep and win_serves(g, act):
-        _, _, tw, wbn = win_tiles(g)
-        return f'conv_win<{tw},{wbn}>'
-    owns = not c4 and g256_geometry(g) and not pw_serves(bn, g.M, g.Ktot, g.K)
-    if owns and not (act or bnep):
-        return 'gemm256'
-    bt = 64 if (bnep or bn == 64) else 128
-    if _pointwise(g):
-        if pw_serves(bt, g.M, g.C, g.K):
-            return 'igemm<128,64,pw3>@ring_grid' if act else ('ring<64,bnep>' if bnep else 'ring<64>')
-        return f'igemm<128,{bt},pw{3 if act else 4 if bnep else 1}>' + ('@g256_layer' if owns else '')
-    assert not (act or bnep), 'fused epilogues: pointwise layers only'
-    return f'igemm<128,{bt},{"c4" if c4 else "gather"}>'
-
-
-def fwd_stat_rows(d):
-    """tok_conv_fwd_stat_rows -> (rows, pixels one tile holds, pixel tiles)"""
-    g = geo_fwd(d)
-    bn = pick_bn(d.k, g.Ktot, d.h == 1 and d.w == 1)
-    gm, gn = cdiv(g.M, 128), cdiv(d.k, bn)
-    if d.c != 4:
-        if win_serves(g):
-            wm, wn, _, _ = win_tiles(g)
-            return _grid(512, wm, wn) // wn, 256, wm
-        if g256_geometry(g) and not pw_serves(bn, g.M, g.Ktot, g.K):
-            return g256_rows(g), 256, g256_rows(g)
-        if _pointwise(g) and pw_serves(bn, g.M, d.c, d.k):
-            return ring_grid(bn, gm, gn) // gn, 128, gm
-    return plan_grid(bn, gm, gn) // gn, 128, gm
-
-
-def dgrad_plan(d):
-    g = geo_dgrad(d)
-    bn = pick_bn(d.c, g.Ktot, d.h == 1 and d.w == 1)
-    if d.stride == 1:
-        gm = cdiv(g.M, 128)
-    else:
-        gm = 4 * max(cdiv(d.n * ((d.h - ph + 1) // 2) * ((d.w - pw + 1) // 2), 128) for ph in (0, 1) for pw in (0, 1))
-    return g, bn, gm, cdiv(d.c, bn)
-
-
-def dgrad_route(d, act=False, sub=False):
-    g, bn, gm, gn = dgrad_plan(d)
-    fused = act or sub
-    if d.stride == 1 and win_serves(g, fused):
-        _, _, tw, wbn = win_tiles(g)
-        return f'conv_win<{tw},{wbn}>'
-    if d.stride == 2 and s2d_serves(g, d.stride, d.pad, fused):
-        _, _, tw, wbn = s2d_tiles(g)
-        return f'conv_s2d<{tw},{wbn}>'
-    owns = d.stride == 1 and g256_geometry(g) and not pw_serves(bn, g.M, g.Ktot, g.K)
-    if owns and not fused:
-        return 'gemm256'
-    if d.stride == 1 and _pointwise(g):
-        if pw_serves(bn, g.M, g.C, g.K):
-            return 'igemm<128,64,pw3>@ring_grid' if act else 'ring<64>'
-        if sub:
-            return 'refused'
-        return f'igemm<128,{bn},pw{3 if act else 1}>' + ('@g256_layer' if owns else '')
-    if fused:
-        return 'refused'
-    return f'igemm<128,{bn},gather_s{d.stride}>'
-
-
-def dgrad_stat_rows(d):
-    g, bn, gm, gn = dgrad_plan(d)
-    if d.stride == 1 and win_serves(g):
-        wm, wn, _, _ = win_tiles(g)
-        return _grid(512, wm, wn) // wn, 256, wm
-    if d.stride == 2 and s2d_serves(g, d.stride, d.pad):
-        wm, wn, _, _ = s2d_tiles(g)
-        return _grid(512, wm, wn) // wn, 256, wm
-    if d.stride == 1 and g256_geometry(g) and not pw_serves(bn, g.M, g.Ktot, g.K):
-        return g256_rows(g), 256, g256_rows(g)
-    if d.stride == 1 and _pointwise(g) and pw_serves(bn, g.M, d.k, d.c):
-        return ring_grid(bn, gm, gn) // gn, 128, gm
-    return plan_grid(bn, gm, gn) // gn, 128, gm
 
 
 def row_map(route, rows, n, h, w):
@@ -413,10 +204,6 @@ FWD_CASES = [
     ('win16_48', (3, 9, 16, 48, 48, 3, 1, 1), 'fwd', 'conv_win<16,48>'),
     ('win64_48_large', (8, 128, 128, 48, 48, 3, 1, 1), 'fwd', 'conv_win<64,48>'),                # 2048 tiles: the persistent grid walks
 ]
-ROUTES_FWD = ({f'igemm<128,{bn},{m}>' for bn in (64, 128) for m in ('gather', 'pw1', 'pw3')} |
-              {'igemm<128,64,pw4>', 'igemm<128,64,c4>', 'stem_win', 'ring<64>', 'ring<64,bnep>', 'igemm<128,64,pw3>@ring_grid',
-               'gemm256', 'igemm<128,64,pw4>@g256_layer', 'igemm<128,128,pw3>@g256_layer'} |
-              {f'conv_win<{tw},{bn}>' for tw in (16, 32, 64) for bn in (48, 64, 96, 128)})
 
 
 def _entry_flags(entry):
@@ -436,8 +223,8 @@ def test_conv_fwd_contract(case):
     k, m = d.k, L.m_out
     on_stem_window = route == 'stem_win'
     flags = _entry_flags(entry)
-    assert fwd_route(d, bias=not on_stem_window, **flags) == route
-    rows, tile_px, tiles = fwd_stat_rows(d)
+    restated, rows, tile_px, tiles = route_fwd(d, bias=not on_stem_window, **flags)
+    assert restated == route
     assert lib.tok_conv_fwd_stat_rows(ctypes.byref(d)) == rows
 
     ktot = d.r * d.s_pad * d.c
@@ -574,10 +361,6 @@ DGRAD_CASES = [
     ('g256', (8, 32, 32, 1024, 1024, 1, 1, 0), 'gemm256', ('gelu',)),
     ('g256_ragged', (4, 65, 65, 384, 512, 1, 1, 0), 'gemm256', ()),
 ]
-ROUTES_DGRAD = ({f'igemm<128,{bn},{m}>' for bn in (64, 128) for m in ('gather_s1', 'gather_s2', 'pw1')} | {'ring<64>', 'gemm256'} |
-                {f'{kern}<{tw},{bn}>' for kern in ('conv_win', 'conv_s2d') for tw in (16, 32, 64) for bn in (48, 64, 96, 128)})
-ACT_ROUTES = {'pw1_64': 'igemm<128,64,pw3>', 'pw1_128': 'igemm<128,128,pw3>', 'ring_256to64': 'igemm<128,64,pw3>@ring_grid',
-              'g256': 'igemm<128,128,pw3>@g256_layer'}
 
 
 def test_every_dgrad_route_has_a_case():
@@ -592,8 +375,8 @@ def test_conv_dgrad_contract(case):
     L = Layer(geo, seed=7 * sum(geo) + len(name))
     d, tag = L.d, f'conv_contract/dgrad/{name}'
     c, m = d.c, L.m_in
-    assert dgrad_route(d) == route
-    rows, tile_px, tiles = dgrad_stat_rows(d)
+    restated, rows, tile_px, tiles = route_dgrad(d)
+    assert restated == route
     assert lib.tok_conv_dgrad_stat_rows(ctypes.byref(d)) == rows
     chain = stat_chain(rows, tile_px, tiles)
     pad_from = cdiv(m, 256) if route == 'gemm256' else None
@@ -681,7 +464,7 @@ def test_conv_dgrad_contract(case):
         # dx = bf16(bf16(GEMM) * act'(act_x)): against the fp64 derivative times the plain call's stored result.  ReLU's factor
         # is exact; GELU's Phi + x phi carries the polynomial's error in Phi, one v_exp_f32 and three fp32 roundings (<= 8 ulp of 1)
         kind = int(kind_name == 'gelu')
-        assert dgrad_route(d, act=True) == ACT_ROUTES[name]
+        assert route_dgrad(d, act=True).name == ACT_ROUTES[name]
         ax = L.randn(m, c).to(BF)
         ag, a_dx, a_dx2 = gin(ax, 128 * c), dx_buf(), dx_buf()
         ins.append((ag, 'act_x'))
@@ -704,7 +487,7 @@ def test_conv_dgrad_contract(case):
             assert_bounded(av, v0.double() * fac, v0.double().abs(), A_BF, eps, f'dx ({kind_name})', tag)
 
     if 'subacc' in extra:
-        assert lib.tok_conv_dgrad_subacc_ok(D) == 1 and dgrad_route(d, sub=True) == 'ring<64>'
+        assert lib.tok_conv_dgrad_subacc_ok(D) == 1 and route_dgrad(d, sub=True).name == 'ring<64>'
         h2, w2 = cdiv(d.h, 2), cdiv(d.w, 2)
         dsub = L.randn(d.n, h2, w2, c).to(BF)
         sg, u_dx, u_part = gin(dsub, 128 * c), dx_buf(), part_buf()
@@ -738,7 +521,7 @@ def test_conv_dgrad_contract(case):
         assert lib.tok_conv_dgrad2_ok(D, ctypes.byref(d2)) == 1
         assert pick_bn(d2.c, d2.k) == 64 and pw_serves(64, m, d.k, c) and pw_serves(64, m, d2.k, c)
         rows2 = lib.tok_conv_dgrad_stat_rows(ctypes.byref(d2))
-        assert rows2 == dgrad_stat_rows(d2)[0]
+        assert rows2 == route_dgrad(d2).rows
         g2, w2g = gin(L2.dy, 128 * d2.k), gin(L2.wd, 128 * d2.k)
         ins += [(g2, 'dy2'), (w2g, 'w2_dgrad')]
         t_dx, t_part = dx_buf(old), gout(2 * rows2 * c, F32, 128 * c)

@@ -40,7 +40,7 @@ struct ConvArgs {
   // dgrad completing the gradient of such a unit's output: the epilogue stores dz = relu_mask ? dx : 0 (what the unit's
   // backward and its shortcut both want) and reduces sum(dz) into the statistics rows; bn_y is not needed
   int mask_store;
-  int force_grid;          // > 0: persistent grid size decided by the caller (statistics rows sized for the ring kernel)
+  int grid;                // workgroups of this launch (host side: the route's, as gridM / gridN / stat_rows below)
   // pointwise dgrad on the ring whose result also takes the gradient of the stride-2 pixel subsample of the same tensor
   // (tok_conv_dgrad_subacc): dx[b][h][w] = acc + (h, w even ? sub[b][h/2][w/2] : 0)
   const bf16* sub;
@@ -50,7 +50,7 @@ struct ConvArgs {
   int P, Q;      // output spatial
   int stride, pad;
   int M, PQ, Ktot, KT;
-  int gridM, gridN;
+  int gridM, gridN;        // tiles of the kernel that runs
   int accumulate, uniform_taps;
   uint32_t x_bytes, w_bytes;   // extents of x / w for the buffer descriptors (< 4 GiB)
   uint32_t s_bytes;            // BNEP: extent of the shortcut tensor
@@ -63,26 +63,31 @@ struct ConvArgs {
 };
 
 
+// The launchers below take grid, gridM, gridN and stat_rows from `a` as the route of conv_igemm.hip (route_fwd / route_dgrad) filled
+// them; the *_serves / *_tiles / *_grid functions are what that route is made of.
 // conv_win.hip: 3x3 / stride 1 / padding 1 layers on a shared input window
 bool conv_win_serves(const ConvArgs& a);
 int conv_win_grid(int gridM, int gridN);
 void conv_win_tiles(const ConvArgs& a, int* gridM, int* gridN);
-int conv_win_launch(ConvArgs& a, hipStream_t st);            // fills a.gridM / a.gridN / a.stat_rows itself
+int conv_win_launch(ConvArgs& a, hipStream_t st);
 // conv_s2d.hip: data gradient of 3x3 / stride 2 / padding 1 layers on a shared dY window (`a` as dgrad_fill leaves it)
 bool conv_s2d_serves(const ConvArgs& a, int stride, int pad);
 int conv_s2d_grid(int gridM, int gridN);
 void conv_s2d_tiles(const ConvArgs& a, int* gridM, int* gridN);
-int conv_s2d_launch(ConvArgs& a, hipStream_t st);            // fills a.gridM / a.gridN / a.stat_rows itself
+int conv_s2d_launch(ConvArgs& a, hipStream_t st);
 
 // gemm256.hip: pointwise layers with a deep reduction and a mid-sized pixel count on 256 x 256 tiles (8 waves)
 bool gemm256_geometry(const ConvArgs& a);                    // does the kernel own this layer (pure function of the geometry)
 bool gemm256_modes(const ConvArgs& a);                       // ... and carry this epilogue mode
 bool gemm256_serves(const ConvArgs& a);                      // both
 int gemm256_rows(const ConvArgs& a);                         // statistics rows = pixel tiles, rounded up to a multiple of 8 (pad rows are zero)
-int gemm256_launch(ConvArgs& a, hipStream_t st);             // fills a.gridM / a.gridN / a.stat_rows itself
+void gemm256_tiles(const ConvArgs& a, int* gridM, int* gridN);
+int gemm256_grid(int gridM, int gridN);
+int gemm256_launch(ConvArgs& a, hipStream_t st);
 
 // stem.hip: the 7x7 / stride 2 stem convolution of a 4-channel-padded image on a shared input window
 bool stem_win_serves(const ConvArgs& a);
-int stem_win_launch(ConvArgs& a, int stat_rows, hipStream_t st);   // stat_rows: rows of a.stats as sized by tok_conv_fwd_stat_rows
+int stem_win_grid(const ConvArgs& a);
+int stem_win_launch(ConvArgs& a, hipStream_t st);            // a.stat_rows >= a.grid: the kernel zero-fills the surplus rows
 bool stem_wgrad_serves(const tok_conv_desc* d);
 int stem_wgrad_launch(const tok_conv_desc* d, const void* x, const void* dy, float* ws, int slabs, hipStream_t st);

@@ -713,10 +713,7 @@ int plan_grid(int bn_tile, int gridM, int gridN, int per_cu = 0) {
 template <int BM, int BN, int IN_DIV, bool C4, int PW>
 int launch_pw(ConvArgs& a, hipStream_t st) {
   constexpr int smem = 2 * (BM + BN) * BK * 2 + 2 * 4 * BN * 4 + (PW == 4 ? 2 * BM * BN * 2 : 0);
-  const int grid = a.force_grid > 0 ? a.force_grid
-                                    : plan_grid(BN, a.gridM, a.gridN, PW == 4 ? 2 : 0);   // (PW 4: two shortcut tiles in LDS -> 2 per CU)
-  a.stat_rows = grid / a.gridN;
-
+  const int grid = a.grid;
 #ifdef TOK_TIMING
   {
     static unsigned long long* tbuf = nullptr;
@@ -739,8 +736,7 @@ int launch_pw(ConvArgs& a, hipStream_t st) {
   return 0;
 }
 
-// pointwise layers whose reduction and output widths fit the ring kernel's access pattern (decided from the geometry alone,
-// so that tok_conv_*_stat_rows can size the statistics rows before any launch)
+// pointwise layers whose reduction and output widths fit the ring kernel's access pattern
 // (the ring pays on the long-M streaming layers; short-M / deep-K ones are MFMA/LDS-bound and keep the two-buffer kernel's
 //  3 workgroups per CU — measured per layer with tools/bench_conv.py)
 static long long pw_min_rows() {
@@ -751,54 +747,6 @@ static long long pw_min_rows() {
 static bool pw_serves(int bn_tile, long long rows, int c_red, int n_out) {
   // (the 128-wide tile would run 1 workgroup per CU on the ring: SwinV2-T 26.0 -> 30.3 ms/step; 64-wide tiles only)
   return bn_tile == 64 && rows >= pw_min_rows() && c_red % 8 == 0 && n_out % 64 == 0;
-}
-
-// 256 x 256 tiles (gemm256.hip) — decided on the GEOMETRY alone, and behind the pointwise ring, so that the statistics-row
-// queries (which know the descriptor, not the epilogue mode) and every launch agree on who owns a layer
-static bool g256_owns(const ConvArgs& a, int bn_tile) {
-  return gemm256_geometry(a) && !pw_serves(bn_tile, a.M, a.Ktot, a.K);
-}
-
-template <int BM, int BN, int IN_DIV, bool C4>
-int launch(ConvArgs& a, hipStream_t st) {
-  if constexpr (IN_DIV == 1 && !C4) {
-    if (a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) {
-      if (pw_serves(BN, a.M, a.C, a.K)) {
-        // pointwise layers run on the three-stage DMA ring (pw_gemm.hip); modes it does not carry (fused activation) stay
-        // here, on the ring's grid so that the statistics rows agree
-        if (a.y2 == nullptr && a.act_x == nullptr) {
-          PwArgs p = {};
-          p.x = a.x; p.w = a.w; p.y = a.y; p.bias = a.bias; p.stats = a.stats;
-          p.stat_rows = pw_ring_grid(BN, a.gridM, a.gridN) / a.gridN;
-          p.e1 = a.accumulate ? a.y : a.ep_short;
-          p.e2 = a.bn_y; p.mask_in = a.bn_mask; p.mask_out = a.ep_mask;
-          p.ep_scale = a.ep_scale; p.ep_shift = a.ep_shift; p.ep_relu = a.ep_relu;
-          p.accumulate = a.accumulate; p.mask_store = a.mask_store;
-          if (a.sub != nullptr) { p.e1 = a.sub; p.accumulate = 1; p.e1_sub = 1; p.sub_H = a.P; p.sub_W = a.Q; }
-          p.M = a.M; p.C = a.C; p.N = a.K; p.gridM = a.gridM; p.gridN = a.gridN;
-          const int rc = pw_ring_launch(p, BN, st);
-          if (rc == 0) return 0;
-          if (rc < 0) { tok_set_error("pointwise ring kernel: inconsistent arguments"); return TOK_ERR_INVALID; }
-        }
-        a.force_grid = pw_ring_grid(BN, a.gridM, a.gridN);
-      }
-      if (a.sub != nullptr) {
-        tok_set_error("tok_conv_dgrad_subacc: layer not served by the pointwise ring kernel (ask tok_conv_dgrad_subacc_ok)");
-        return TOK_ERR_INVALID;
-      }
-      // (PWM 2 = streaming / non-temporal output stores: +5..25 % on the write-heavy layers in
-      //  isolation, but the consumer BatchNorm pass then misses the 256 MB Infinity Cache and the
-      //  whole step loses 2 % — measured, so it stays off)
-      if (a.y2 != nullptr || a.act_x != nullptr) return launch_pw<BM, BN, 1, false, 3>(a, st);
-      if (a.ep_scale != nullptr) return launch_pw<BM, BN, 1, false, 4>(a, st);
-      return launch_pw<BM, BN, 1, false, 1>(a, st);
-    }
-  }
-  if (a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.sub != nullptr) {
-    tok_set_error("fused activation / BatchNorm epilogue / subsample accumulate: 1x1 / stride 1 / no padding layers only");
-    return TOK_ERR_INVALID;
-  }
-  return launch_pw<BM, BN, IN_DIV, C4, 0>(a, st);
 }
 
 // Channel-tile width.  Short-K layers are HBM-streaming problems: the 128x64 tile (4 waves, 3
@@ -819,6 +767,145 @@ int pick_bn(int n_out, int ktot, bool token_rows = false) {
   return 128;
 }
 
+// ---- the route: which kernel runs a forward / data-gradient launch, on which grid, and how many statistics rows it writes ----
+// ONE pure host function per direction (route_fwd, route_dgrad) of the descriptor, the mode and the knobs.  The row queries of the
+// C ABI return a field of it and the launches switch on it, so the rows a caller allocates and the rows a kernel writes cannot
+// differ.  The GEOMETRY alone decides the row count (the queries know the descriptor, not the epilogue): it names the layer's
+// owner among the window kernels, the pointwise ring (pw_gemm.hip), the 256 x 256 tiles (gemm256.hip, behind the ring) and this
+// file's kernel.  The MODE decides the kernel: one the owner does not carry runs this file's kernel on the owner's grid wherever
+// it writes statistics rows.  tests/conv_route_ref.py restates all of it.
+enum ConvKernel { K_STEM_WIN, K_WIN, K_S2D, K_GEMM256, K_RING, K_IGEMM };
+struct ConvMode { bool act, bnep, sub, stats; };   // fused activation, BatchNorm epilogue, subsample accumulate, statistics written
+struct ConvRoute {
+  ConvKernel kernel;
+  int pw;                        // K_IGEMM: the PW mode of conv_igemm_kernel (0 gather, 1 pointwise, 3 + activation, 4 + BatchNorm epilogue)
+  int bn_tile, gridM, gridN;     // of the kernel that runs
+  int grid;                      // workgroups launched
+  int stat_rows;                 // rows of the partial-statistics buffer
+};
+
+ConvMode mode_of(const ConvArgs& a) { return {a.y2 || a.act_x, a.ep_scale != nullptr, a.sub != nullptr, a.stats != nullptr}; }
+
+ConvRoute route_window(ConvKernel kernel, const ConvArgs& a) {   // conv_win.hip / conv_s2d.hip: one row per workgroup of a channel tile
+  ConvRoute r = {};
+  r.kernel = kernel;
+  if (kernel == K_WIN) { conv_win_tiles(a, &r.gridM, &r.gridN); r.grid = conv_win_grid(r.gridM, r.gridN); }
+  else { conv_s2d_tiles(a, &r.gridM, &r.gridN); r.grid = conv_s2d_grid(r.gridM, r.gridN); }
+  r.stat_rows = r.grid / r.gridN;
+  return r;
+}
+
+// a layer the window kernels do not take (`a` with its 128-row gridM filled): pointwise ring, 256 x 256 tiles or this file's kernel
+ConvRoute route_gemm(const ConvArgs& a, bool pointwise, int bn_pick, ConvMode m) {
+  ConvRoute r = {};
+  const int gn = tok_cdiv(a.K, bn_pick);
+  const bool ring_owns = pointwise && pw_serves(bn_pick, a.M, a.C, a.K);
+  const bool g256_owns = pointwise && !ring_owns && gemm256_geometry(a);
+  r.stat_rows = g256_owns ? gemm256_rows(a) : (ring_owns ? pw_ring_grid(bn_pick, a.gridM, gn) : plan_grid(bn_pick, a.gridM, gn)) / gn;
+  if (g256_owns && gemm256_modes(a)) {
+    // deep-K pointwise layers with a mid-sized pixel count: 256 x 256 tiles, eight waves
+    r.kernel = K_GEMM256;
+    gemm256_tiles(a, &r.gridM, &r.gridN);
+    r.grid = gemm256_grid(r.gridM, r.gridN);
+    return r;
+  }
+  r.bn_tile = m.bnep ? 64 : bn_pick;   // (BatchNorm epilogue: 64-wide tiles; it writes no statistics)
+  r.gridM = a.gridM; r.gridN = tok_cdiv(a.K, r.bn_tile);
+  const bool ring_layer = pointwise && pw_serves(r.bn_tile, a.M, a.C, a.K);
+  r.kernel = ring_layer && !m.act ? K_RING : K_IGEMM;   // (the ring carries no fused activation)
+  // (PW 2 = streaming / non-temporal output stores: +5..25 % on the write-heavy layers in isolation, but the consumer BatchNorm
+  //  pass then misses the 256 MB Infinity Cache and the whole step loses 2 % — measured, so it stays off)
+  r.pw = !pointwise ? 0 : m.act ? 3 : m.bnep ? 4 : 1;
+  r.grid = ring_layer ? pw_ring_grid(r.bn_tile, r.gridM, r.gridN)
+           : g256_owns && m.stats ? r.stat_rows * r.gridN   // (gemm256's rows are a multiple of 8: a grid of 8 * gridN units)
+                                  : plan_grid(r.bn_tile, r.gridM, r.gridN, r.pw == 4 ? 2 : 0);   // (PW 4: two shortcut tiles in LDS -> 2 per CU)
+  return r;
+}
+
+// `a` as fwd_fill leaves it, with the operands of a launch or without (the queries)
+ConvRoute route_fwd(const tok_conv_desc* d, const ConvArgs& a, ConvMode m) {
+  const bool c4 = d->c == 4;
+  // 3x3 / stride 1 / padding 1: shared input window in LDS (conv_win.hip)
+  if (!c4 && !m.bnep && conv_win_serves(a)) return route_window(K_WIN, a);
+  const bool pointwise = !c4 && a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0;
+  ConvRoute r = route_gemm(a, pointwise, pick_bn(d->k, a.Ktot, d->h == 1 && d->w == 1), m);
+  if (c4 && !m.bnep && stem_win_serves(a)) {
+    // the 7x7 / stride 2 stem on a shared input window (stem.hip): it fills the rows sized above and zero-fills the ones its
+    // grid does not own, so the grid is clamped to them
+    r.kernel = K_STEM_WIN;
+    r.grid = stem_win_grid(a);
+    if (m.stats && r.grid > r.stat_rows) r.grid = r.stat_rows;
+  }
+  return r;
+}
+
+// `a` as dgrad_fill leaves it
+ConvRoute route_dgrad(const tok_conv_desc* d, const ConvArgs& a, ConvMode m) {
+  if (d->stride == 1 && conv_win_serves(a)) return route_window(K_WIN, a);
+  if (d->stride == 2 && conv_s2d_serves(a, d->stride, d->pad)) return route_window(K_S2D, a);
+  const bool pointwise = d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0;
+  return route_gemm(a, pointwise, pick_bn(d->c, a.Ktot, d->h == 1 && d->w == 1), m);
+}
+
+int launch_ring(const ConvArgs& a, const ConvRoute& r, hipStream_t st) {
+  PwArgs p = {};
+  p.x = a.x; p.w = a.w; p.y = a.y; p.bias = a.bias; p.stats = a.stats;
+  p.stat_rows = r.stat_rows;
+  p.e1 = a.accumulate ? a.y : a.ep_short;
+  p.e2 = a.bn_y; p.mask_in = a.bn_mask; p.mask_out = a.ep_mask;
+  p.ep_scale = a.ep_scale; p.ep_shift = a.ep_shift; p.ep_relu = a.ep_relu;
+  p.accumulate = a.accumulate; p.mask_store = a.mask_store;
+  if (a.sub != nullptr) { p.e1 = a.sub; p.accumulate = 1; p.e1_sub = 1; p.sub_H = a.P; p.sub_W = a.Q; }
+  p.M = a.M; p.C = a.C; p.N = a.K; p.gridM = r.gridM; p.gridN = r.gridN;
+  return pw_ring_launch(p, r.bn_tile, r.grid, st);
+}
+
+// this file's kernel: in_div 2 = stride-2 data gradient, c4 = 4-channel stem input (both in gather mode only)
+template <int BN>
+int launch_igemm(ConvArgs& a, int pw, int in_div, bool c4, hipStream_t st) {
+  if (pw == 1) return launch_pw<128, BN, 1, false, 1>(a, st);
+  if (pw == 3) return launch_pw<128, BN, 1, false, 3>(a, st);
+  if (pw == 4) return launch_pw<128, BN, 1, false, 4>(a, st);
+  if (c4) return launch_pw<128, BN, 1, true, 0>(a, st);
+  return in_div == 2 ? launch_pw<128, BN, 2, false, 0>(a, st) : launch_pw<128, BN, 1, false, 0>(a, st);
+}
+
+// Hands the route's tiling to the kernel arguments and launches its kernel.  Where statistics are written the grid must be the
+// one the rows were sized for — one row per workgroup of a channel tile; gemm256 writes one row per pixel tile and zero-fills up
+// to stat_rows, the stem window kernel zero-fills the rows behind its grid — or the kernel would write past the caller's buffer
+// or leave rows unwritten: such a launch is refused, not issued.
+int run_route(ConvArgs& a, const ConvRoute& r, int in_div, bool c4, hipStream_t st) {
+  a.gridM = r.gridM; a.gridN = r.gridN; a.grid = r.grid; a.stat_rows = r.stat_rows;
+  if (a.stats != nullptr) {
+    const bool rows_agree = r.kernel == K_GEMM256 ? r.gridM <= r.stat_rows
+                            : r.kernel == K_STEM_WIN ? r.grid <= r.stat_rows : r.grid == r.stat_rows * r.gridN;
+    TOK_CHECK_ARG(rows_agree, "conv route: %d workgroups over %d channel tiles do not write %d statistics rows", r.grid, r.gridN, r.stat_rows);
+  }
+  switch (r.kernel) {
+    case K_STEM_WIN: return stem_win_launch(a, st);
+    case K_WIN: return conv_win_launch(a, st);
+    case K_S2D: return conv_s2d_launch(a, st);
+    case K_GEMM256: return gemm256_launch(a, st);
+    case K_RING: {
+      const int rc = launch_ring(a, r, st);
+      if (rc == 0) return 0;
+      if (rc < 0) { tok_set_error("pointwise ring kernel: inconsistent arguments"); return TOK_ERR_INVALID; }
+    }
+      [[fallthrough]];   // (the ring declined: this file's kernel, on the ring's grid so that the statistics rows agree)
+    case K_IGEMM:
+      if (r.pw == 0 && (a.y2 != nullptr || a.act_x != nullptr || a.ep_scale != nullptr || a.sub != nullptr)) {
+        tok_set_error("fused activation / BatchNorm epilogue / subsample accumulate: 1x1 / stride 1 / no padding layers only");
+        return TOK_ERR_INVALID;
+      }
+      if (a.sub != nullptr) {
+        tok_set_error("tok_conv_dgrad_subacc: layer not served by the pointwise ring kernel (ask tok_conv_dgrad_subacc_ok)");
+        return TOK_ERR_INVALID;
+      }
+      return r.bn_tile == 64 ? launch_igemm<64>(a, r.pw, in_div, c4, st) : launch_igemm<128>(a, r.pw, in_div, c4, st);
+  }
+  return TOK_ERR_INVALID;
+}
+
 int check_desc(const tok_conv_desc* d, const char* who) {
   TOK_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
   TOK_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->c > 0 && d->k > 0, "%s: bad dims", who);
@@ -835,62 +922,8 @@ int check_desc(const tok_conv_desc* d, const char* who) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" int tok_conv_fwd_stat_rows(const tok_conv_desc* d) {
-  if (check_desc(d, "tok_conv_fwd_stat_rows")) return TOK_ERR_INVALID;
-  const int gridM = tok_cdiv((long long)d->n * d->p * d->q, 128);
-  const int bn_tile = pick_bn(d->k, d->r * d->s_pad * d->c, d->h == 1 && d->w == 1);
-  const int gridN = tok_cdiv(d->k, bn_tile);
-  if (d->c != 4) {
-    ConvArgs g = {};
-    g.C = d->c; g.K = d->k; g.Ktot = d->r * d->s_pad * d->c; g.M = d->n * d->p * d->q;
-    g.H = d->h; g.W = d->w; g.P = d->p; g.Q = d->q; g.R = d->r; g.S = d->s_pad; g.stride = d->stride; g.pad = d->pad;
-    const unsigned long long xb = (unsigned long long)d->n * d->h * d->w * d->c * 2;
-    g.x_bytes = xb < 0xFFFFFFF0ull ? (uint32_t)xb : 0xFFFFFFF0u;
-    if (conv_win_serves(g)) {
-      int gm, gn;
-      conv_win_tiles(g, &gm, &gn);
-      return conv_win_grid(gm, gn) / gn;
-    }
-    if (g256_owns(g, bn_tile)) return gemm256_rows(g);
-  }
-  if (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->c != 4 && pw_serves(bn_tile, (long long)d->n * d->p * d->q, d->c, d->k))
-    return pw_ring_grid(bn_tile, gridM, gridN) / gridN;
-  return plan_grid(bn_tile, gridM, gridN) / gridN;
-}
-
-extern "C" int tok_conv_dgrad_stat_rows(const tok_conv_desc* d);
-
-namespace {
-struct BnEpilogue { const float* scale; const float* shift; const void* shortcut; uint8_t* mask; int relu; };
-int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
-                  void* stream, void* y_act = nullptr, int act = 0, const BnEpilogue* ep = nullptr);
-}  // namespace
-
-extern "C" int tok_conv_fwd(const tok_conv_desc* d, const void* x, const void* w,
-                            const float* bias, void* y, float* stats, void* stream) {
-  return conv_fwd_impl(d, x, w, bias, y, stats, stream);
-}
-
-namespace {
-int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
-                  void* stream, void* y_act, int act, const BnEpilogue* ep) {
-  if (int e = check_desc(d, "tok_conv_fwd")) return e;
-  TOK_CHECK_ARG(x && w && y, "tok_conv_fwd: null pointer");
-  // (refused here, by name: launch<>() below knows the mode, not the entry point)
-  TOK_CHECK_ARG(y_act == nullptr || (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->c != 4),
-                "tok_conv_fwd_act: 1x1 / stride 1 / no padding layers only");
-  ConvArgs a = {};
-  a.x = (const bf16*)x; a.w = (const bf16*)w; a.y = (bf16*)y; a.bias = bias; a.stats = stats;
-  a.y2 = (bf16*)y_act; a.act = act;
-  if (ep != nullptr) {
-    a.ep_scale = ep->scale; a.ep_shift = ep->shift; a.ep_short = (const bf16*)ep->shortcut; a.ep_mask = ep->mask;
-    a.ep_relu = ep->relu;
-    const unsigned long long sb = (unsigned long long)d->n * d->p * d->q * d->k * 2;
-    TOK_CHECK_ARG(sb < 0xFFFFFFF0ull, "tok_conv_fwd_bn_apply: tensors of 4 GiB or more are not supported");
-    a.s_bytes = (uint32_t)sb;
-  }
+// geometry of a forward launch.  false where x or w reach 4 GiB: the extents are then clamped, so that the row query still answers
+bool fwd_fill(const tok_conv_desc* d, ConvArgs& a) {
   a.H = d->h; a.W = d->w; a.C = d->c; a.K = d->k; a.R = d->r; a.S = d->s_pad;
   a.P = d->p; a.Q = d->q; a.stride = d->stride; a.pad = d->pad;
   a.M = d->n * d->p * d->q; a.PQ = d->p * d->q;
@@ -898,54 +931,36 @@ int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const fl
   a.gridM = tok_cdiv(a.M, 128);
   a.fd_pq = make_fastdiv(a.PQ); a.fd_q = make_fastdiv(a.Q);
   const unsigned long long xb = (unsigned long long)d->n * d->h * d->w * d->c * 2, wb = (unsigned long long)d->k * a.Ktot * 2;
-  TOK_CHECK_ARG(xb < 0xFFFFFFF0ull && wb < 0xFFFFFFF0ull, "tok_conv_fwd: tensors of 4 GiB or more are not supported");
-  a.x_bytes = (uint32_t)xb; a.w_bytes = (uint32_t)wb;
-  hipStream_t st = tok_stream(stream);
-  const bool c4 = d->c == 4;
-  int rc;
-  const int bn_pick = pick_bn(d->k, a.Ktot, d->h == 1 && d->w == 1);
-  if (c4 && ep == nullptr && stem_win_serves(a)) {
-    // the 7x7 / stride 2 stem on a shared input window (stem.hip); statistics rows as tok_conv_fwd_stat_rows sized them
-    rc = stem_win_launch(a, tok_conv_fwd_stat_rows(d), st);
-    if (rc) return rc;
-    TOK_CHECK_LAUNCH("tok_conv_fwd");
-    return TOK_OK;
+  a.x_bytes = xb < 0xFFFFFFF0ull ? (uint32_t)xb : 0xFFFFFFF0u;
+  a.w_bytes = wb < 0xFFFFFFF0ull ? (uint32_t)wb : 0xFFFFFFF0u;
+  return xb < 0xFFFFFFF0ull && wb < 0xFFFFFFF0ull;
+}
+
+struct BnEpilogue { const float* scale; const float* shift; const void* shortcut; uint8_t* mask; int relu; };
+
+int conv_fwd_impl(const tok_conv_desc* d, const void* x, const void* w, const float* bias, void* y, float* stats,
+                  void* stream, void* y_act = nullptr, int act = 0, const BnEpilogue* ep = nullptr) {
+  if (int e = check_desc(d, "tok_conv_fwd")) return e;
+  TOK_CHECK_ARG(x && w && y, "tok_conv_fwd: null pointer");
+  // (refused here, by name: the route knows the mode, not the entry point)
+  TOK_CHECK_ARG(y_act == nullptr || (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->c != 4),
+                "tok_conv_fwd_act: 1x1 / stride 1 / no padding layers only");
+  ConvArgs a = {};
+  a.x = (const bf16*)x; a.w = (const bf16*)w; a.y = (bf16*)y; a.bias = bias; a.stats = stats;
+  a.y2 = (bf16*)y_act; a.act = act;
+  if (ep != nullptr) {
+    a.ep_scale = ep->scale; a.ep_shift = ep->shift; a.ep_short = (const bf16*)ep->shortcut; a.ep_mask = ep->mask; a.ep_relu = ep->relu;
+    const unsigned long long sb = (unsigned long long)d->n * d->p * d->q * d->k * 2;
+    TOK_CHECK_ARG(sb < 0xFFFFFFF0ull, "tok_conv_fwd_bn_apply: tensors of 4 GiB or more are not supported");
+    a.s_bytes = (uint32_t)sb;
   }
-  if (!c4 && ep == nullptr && conv_win_serves(a)) {
-    // 3x3 / stride 1 / padding 1: shared input window in LDS (conv_win.hip)
-    rc = conv_win_launch(a, st);
-    if (rc) return rc;
-    TOK_CHECK_LAUNCH("tok_conv_fwd");
-    return TOK_OK;
-  }
-  const bool g256 = !c4 && g256_owns(a, bn_pick);
-  if (g256 && gemm256_modes(a)) {
-    // deep-K pointwise layers with a mid-sized pixel count: 256 x 256 tiles, eight waves (gemm256.hip)
-    rc = gemm256_launch(a, st);
-    if (rc) return rc;
-    TOK_CHECK_LAUNCH("tok_conv_fwd");
-    return TOK_OK;
-  }
-  // (a mode gemm256 does not carry that still writes statistics rows: this file's kernel on gemm256's row count — a multiple of 8)
-  if (g256 && a.stats != nullptr) a.force_grid = gemm256_rows(a) * tok_cdiv(d->k, ep != nullptr ? 64 : bn_pick);
-  if (ep != nullptr || bn_pick == 64) {   // (BN epilogue: 64-wide tiles)
-    a.gridN = tok_cdiv(d->k, 64);
-    rc = c4 ? launch<128, 64, 1, true>(a, st) : launch<128, 64, 1, false>(a, st);
-  } else {
-    a.gridN = tok_cdiv(d->k, 128);
-    rc = c4 ? launch<128, 128, 1, true>(a, st) : launch<128, 128, 1, false>(a, st);
-  }
-  if (rc) return rc;
+  TOK_CHECK_ARG(fwd_fill(d, a), "tok_conv_fwd: tensors of 4 GiB or more are not supported");
+  if (int rc = run_route(a, route_fwd(d, a, mode_of(a)), 1, d->c == 4, tok_stream(stream))) return rc;
   TOK_CHECK_LAUNCH("tok_conv_fwd");
   return TOK_OK;
 }
-}  // namespace
 
-namespace {
-
-struct DgradPlan { int bn_tile, gridM, gridN; };
-
-int dgrad_fill(const tok_conv_desc* d, ConvArgs& a, DgradPlan& pl) {
+int dgrad_fill(const tok_conv_desc* d, ConvArgs& a) {
   TOK_CHECK_ARG(d->c % 8 == 0, "tok_conv_dgrad: c4 (stem) input needs no data gradient");
   TOK_CHECK_ARG(d->stride == 1 || d->stride == 2, "tok_conv_dgrad: stride %d unsupported", d->stride);
   TOK_CHECK_ARG(d->r - 1 - d->pad >= 0, "tok_conv_dgrad: pad > r-1 unsupported");
@@ -977,59 +992,49 @@ int dgrad_fill(const tok_conv_desc* d, ConvArgs& a, DgradPlan& pl) {
     }
     a.gridM = 4 * tmax;   // classes interleaved (m-tile & 3) so heavy and light tiles mix on every XCD
   }
-  pl.bn_tile = pick_bn(d->c, a.Ktot, d->h == 1 && d->w == 1);
-  a.gridN = tok_cdiv(d->c, pl.bn_tile);
-  pl.gridM = a.gridM; pl.gridN = a.gridN;
   return 0;
 }
 
-int dgrad_impl(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, int accumulate,
-               const void* bn_y, const uint8_t* bn_mask, float* partial, void* stream, const char* who,
-               const void* act_x = nullptr, int act = 0, const float* bias = nullptr,
-               int mask_store = 0, const void* sub = nullptr) {
+// what rides a data gradient beside the GEMM; every entry point fills the fields it owns and leaves the rest zero
+struct DgradEpilogue {
+  int accumulate;                                                   // dx += ...
+  const void* bn_y; const uint8_t* bn_mask; float* partial;         // BatchNorm-backward sums of the completed gradient
+  const void* act_x; int act;                                       // dx = dy * act'(act_x)
+  const float* bias;
+  int mask_store;                                                   // store relu_mask * dx, sum it into partial
+  const void* sub;                                                  // + the gradient of the stride-2 pixel subsample of dx's tensor
+};
+
+int dgrad_impl(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, const DgradEpilogue& ep, void* stream,
+               const char* who) {
   if (int e = check_desc(d, who)) return e;
   TOK_CHECK_ARG(dy && w_dgrad && dx, "%s: null pointer", who);
-  // (refused here, by name: launch<>() below knows the mode, not the entry point)
-  TOK_CHECK_ARG((act_x == nullptr && sub == nullptr) || (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0),
+  // (refused here, by name: the route knows the mode, not the entry point)
+  TOK_CHECK_ARG((ep.act_x == nullptr && ep.sub == nullptr) || (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0),
                 "%s: 1x1 / stride 1 / no padding layers only", who);
   ConvArgs a = {};
-  DgradPlan pl;
-  if (int e = dgrad_fill(d, a, pl)) return e;
-  a.x = (const bf16*)dy; a.w = (const bf16*)w_dgrad; a.y = (bf16*)dx; a.bias = bias;
-  a.stats = partial; a.bn_y = (const bf16*)bn_y; a.bn_mask = bn_mask; a.mask_store = mask_store;
-  a.accumulate = accumulate;
-  a.sub = (const bf16*)sub;
-  a.act_x = (const bf16*)act_x; a.act = act;
-  hipStream_t st = tok_stream(stream);
-  int rc;
-  if (d->stride == 1 && conv_win_serves(a)) {
-    rc = conv_win_launch(a, st);
-    if (rc) return rc;
-    TOK_CHECK_LAUNCH(who);
-    return TOK_OK;
-  }
-  if (d->stride == 2 && conv_s2d_serves(a, d->stride, d->pad)) {
-    rc = conv_s2d_launch(a, st);
-    if (rc) return rc;
-    TOK_CHECK_LAUNCH(who);
-    return TOK_OK;
-  }
-  const bool g256 = d->stride == 1 && g256_owns(a, pl.bn_tile);
-  if (g256 && gemm256_modes(a)) {
-    rc = gemm256_launch(a, st);
-    if (rc) return rc;
-    TOK_CHECK_LAUNCH(who);
-    return TOK_OK;
-  }
-  if (g256 && a.stats != nullptr) a.force_grid = gemm256_rows(a) * pl.gridN;   // (see conv_fwd_impl)
-  if (pl.bn_tile == 64) rc = d->stride == 1 ? launch<128, 64, 1, false>(a, st) : launch<128, 64, 2, false>(a, st);
-  else rc = d->stride == 1 ? launch<128, 128, 1, false>(a, st) : launch<128, 128, 2, false>(a, st);
-  if (rc) return rc;
+  if (int e = dgrad_fill(d, a)) return e;
+  a.x = (const bf16*)dy; a.w = (const bf16*)w_dgrad; a.y = (bf16*)dx; a.bias = ep.bias;
+  a.stats = ep.partial; a.bn_y = (const bf16*)ep.bn_y; a.bn_mask = ep.bn_mask; a.mask_store = ep.mask_store;
+  a.accumulate = ep.accumulate; a.sub = (const bf16*)ep.sub; a.act_x = (const bf16*)ep.act_x; a.act = ep.act;
+  if (int rc = run_route(a, route_dgrad(d, a, mode_of(a)), d->stride, false, tok_stream(stream))) return rc;
   TOK_CHECK_LAUNCH(who);
   return TOK_OK;
 }
 
 }  // namespace
+
+extern "C" int tok_conv_fwd_stat_rows(const tok_conv_desc* d) {
+  if (check_desc(d, "tok_conv_fwd_stat_rows")) return TOK_ERR_INVALID;
+  ConvArgs a = {};
+  fwd_fill(d, a);
+  return route_fwd(d, a, ConvMode{}).stat_rows;
+}
+
+extern "C" int tok_conv_fwd(const tok_conv_desc* d, const void* x, const void* w,
+                            const float* bias, void* y, float* stats, void* stream) {
+  return conv_fwd_impl(d, x, w, bias, y, stats, stream);
+}
 
 extern "C" int tok_conv_fwd_act(const tok_conv_desc* d, const void* x, const void* w, const float* bias, void* y,
                                 void* y_act, int kind, void* stream) {
@@ -1040,40 +1045,29 @@ extern "C" int tok_conv_fwd_act(const tok_conv_desc* d, const void* x, const voi
 extern "C" int tok_conv_dgrad_act(const tok_conv_desc* d, const void* dy, const void* w_dgrad, const void* act_x, int kind,
                                   void* dx, void* stream) {
   TOK_CHECK_ARG(act_x != nullptr && (kind == 0 || kind == 1), "tok_conv_dgrad_act: act_x and kind 0 (ReLU) / 1 (GELU)");
-  return dgrad_impl(d, dy, w_dgrad, dx, 0, nullptr, nullptr, nullptr, stream, "tok_conv_dgrad_act", act_x, kind);
+  DgradEpilogue ep = {}; ep.act_x = act_x; ep.act = kind;
+  return dgrad_impl(d, dy, w_dgrad, dx, ep, stream, "tok_conv_dgrad_act");
 }
 
 extern "C" int tok_conv_dgrad(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                               int accumulate, void* stream) {
-  return dgrad_impl(d, dy, w_dgrad, dx, accumulate, nullptr, nullptr, nullptr, stream, "tok_conv_dgrad");
+  DgradEpilogue ep = {}; ep.accumulate = accumulate;
+  return dgrad_impl(d, dy, w_dgrad, dx, ep, stream, "tok_conv_dgrad");
 }
 
 extern "C" int tok_conv_dgrad_stat_rows(const tok_conv_desc* d) {
   if (check_desc(d, "tok_conv_dgrad_stat_rows")) return TOK_ERR_INVALID;
   ConvArgs a = {};
-  DgradPlan pl;
-  if (dgrad_fill(d, a, pl)) return TOK_ERR_INVALID;
-  if (d->stride == 1 && conv_win_serves(a)) {
-    int gm, gn;
-    conv_win_tiles(a, &gm, &gn);
-    return conv_win_grid(gm, gn) / gn;
-  }
-  if (d->stride == 2 && conv_s2d_serves(a, d->stride, d->pad)) {
-    int gm, gn;
-    conv_s2d_tiles(a, &gm, &gn);
-    return conv_s2d_grid(gm, gn) / gn;
-  }
-  if (d->stride == 1 && g256_owns(a, pl.bn_tile)) return gemm256_rows(a);
-  if (d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && pw_serves(pl.bn_tile, (long long)d->n * d->h * d->w, d->k, d->c))
-    return pw_ring_grid(pl.bn_tile, pl.gridM, pl.gridN) / pl.gridN;
-  return plan_grid(pl.bn_tile, pl.gridM, pl.gridN) / pl.gridN;
+  if (dgrad_fill(d, a)) return TOK_ERR_INVALID;
+  return route_dgrad(d, a, ConvMode{}).stat_rows;
 }
 
 extern "C" int tok_conv_dgrad_bnstats(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                                       int accumulate, const void* bn_y, const uint8_t* bn_mask,
                                       float* partial, void* stream) {
   TOK_CHECK_ARG(bn_y && partial, "tok_conv_dgrad_bnstats: bn_y / partial must not be null");
-  return dgrad_impl(d, dy, w_dgrad, dx, accumulate, bn_y, bn_mask, partial, stream, "tok_conv_dgrad_bnstats");
+  DgradEpilogue ep = {}; ep.accumulate = accumulate; ep.bn_y = bn_y; ep.bn_mask = bn_mask; ep.partial = partial;
+  return dgrad_impl(d, dy, w_dgrad, dx, ep, stream, "tok_conv_dgrad_bnstats");
 }
 
 
@@ -1092,15 +1086,15 @@ extern "C" int tok_conv_fwd_bn_apply(const tok_conv_desc* d, const void* x, cons
 extern "C" int tok_conv_dgrad_maskstore(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                                         int accumulate, const uint8_t* mask, float* partial, void* stream) {
   TOK_CHECK_ARG(mask && partial, "tok_conv_dgrad_maskstore: mask / partial must not be null");
-  return dgrad_impl(d, dy, w_dgrad, dx, accumulate, nullptr, mask, partial, stream, "tok_conv_dgrad_maskstore", nullptr,
-                    0, nullptr, 1);
+  DgradEpilogue ep = {}; ep.accumulate = accumulate; ep.bn_mask = mask; ep.partial = partial; ep.mask_store = 1;
+  return dgrad_impl(d, dy, w_dgrad, dx, ep, stream, "tok_conv_dgrad_maskstore");
 }
 
 extern "C" int tok_conv_dgrad_bias(const tok_conv_desc* d, const void* dy, const void* w_dgrad, const float* bias, void* dx,
                                    int accumulate, const void* bn_y, const uint8_t* bn_mask, float* partial, void* stream) {
   TOK_CHECK_ARG((bn_y == nullptr) == (partial == nullptr), "tok_conv_dgrad_bias: bn_y and partial go together");
-  return dgrad_impl(d, dy, w_dgrad, dx, accumulate, bn_y, bn_mask, partial, stream, "tok_conv_dgrad_bias", nullptr, 0,
-                    bias);
+  DgradEpilogue ep = {}; ep.accumulate = accumulate; ep.bn_y = bn_y; ep.bn_mask = bn_mask; ep.partial = partial; ep.bias = bias;
+  return dgrad_impl(d, dy, w_dgrad, dx, ep, stream, "tok_conv_dgrad_bias");
 }
 
 // ---- pointwise dgrad + the gradient of the stride-2 pixel subsample of the same tensor ----------------------------------------
@@ -1112,9 +1106,8 @@ extern "C" int tok_conv_dgrad_subacc_ok(const tok_conv_desc* d) {
   if (check_desc(d, "tok_conv_dgrad_subacc_ok")) return 0;
   if (!(d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->c % 8 == 0)) return 0;
   ConvArgs a = {};
-  DgradPlan pl;
-  if (dgrad_fill(d, a, pl)) return 0;
-  return pw_serves(pl.bn_tile, (long long)d->n * d->h * d->w, d->k, d->c) ? 1 : 0;
+  if (dgrad_fill(d, a)) return 0;
+  return route_dgrad(d, a, ConvMode{false, false, /*sub*/ true, false}).kernel == K_RING ? 1 : 0;
 }
 
 extern "C" int tok_conv_dgrad_subacc(const tok_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, const void* dsub,
@@ -1122,8 +1115,8 @@ extern "C" int tok_conv_dgrad_subacc(const tok_conv_desc* d, const void* dy, con
   TOK_CHECK_ARG(dsub != nullptr, "tok_conv_dgrad_subacc: dsub must not be null");
   TOK_CHECK_ARG(!mask_store || (mask && partial && !bn_y), "tok_conv_dgrad_subacc: mask_store needs mask + partial, no bn_y");
   TOK_CHECK_ARG(mask_store || ((bn_y == nullptr) == (partial == nullptr)), "tok_conv_dgrad_subacc: bn_y and partial go together");
-  return dgrad_impl(d, dy, w_dgrad, dx, 0, bn_y, mask, partial, stream, "tok_conv_dgrad_subacc", nullptr, 0, nullptr,
-                    mask_store, dsub);
+  DgradEpilogue ep = {}; ep.bn_y = bn_y; ep.bn_mask = mask; ep.partial = partial; ep.mask_store = mask_store; ep.sub = dsub;
+  return dgrad_impl(d, dy, w_dgrad, dx, ep, stream, "tok_conv_dgrad_subacc");
 }
 
 // ---- sum of two pointwise data gradients in one launch --------------------------------------------------------------------------
@@ -1133,38 +1126,42 @@ extern "C" int tok_conv_dgrad_subacc(const tok_conv_desc* d, const void* dy, con
 // tok_conv_dgrad_bias.  Served where tok_conv_dgrad2_ok(d1, d2) (64-wide tiles on the ring).
 
 namespace {
-bool dgrad2_geometry(const tok_conv_desc* d1, const tok_conv_desc* d2) {
+// The launch runs on the route of the SECOND layer's pointwise geometry (rows x d2->k -> c): it must sit on the 64-wide ring, and
+// its statistics-row count is the one the caller sizes `partial` with.  The first layer only adds K stages of a reduction the
+// ring can read.  (The tile width is picked as for a pixel map.)
+bool dgrad2_route(const tok_conv_desc* d1, const tok_conv_desc* d2, ConvRoute* r) {
   if (d1 == nullptr || d2 == nullptr) return false;
   for (const tok_conv_desc* d : {d1, d2})
     if (!(d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0 && d->k % 8 == 0 && d->c % 64 == 0)) return false;
   if (d1->n != d2->n || d1->h != d2->h || d1->w != d2->w || d1->c != d2->c) return false;
   const long long rows = (long long)d1->n * d1->h * d1->w;
-  // the second layer alone must sit on the 64-wide ring too: its statistics-row count is the one the caller sizes `partial` with
-  if (pick_bn(d2->c, d2->k) != 64) return false;
-  return pw_serves(64, rows, d1->k, d1->c) && pw_serves(64, rows, d2->k, d2->c);
+  ConvArgs g = {};
+  g.M = (int)rows; g.C = g.Ktot = d2->k; g.K = d2->c; g.R = g.S = g.stride = 1;
+  g.gridM = tok_cdiv(rows, 128);
+  *r = route_gemm(g, true, pick_bn(d2->c, d2->k), ConvMode{});
+  return r->kernel == K_RING && r->bn_tile == 64;
 }
 }  // namespace
 
-extern "C" int tok_conv_dgrad2_ok(const tok_conv_desc* d1, const tok_conv_desc* d2) { return dgrad2_geometry(d1, d2) ? 1 : 0; }
+extern "C" int tok_conv_dgrad2_ok(const tok_conv_desc* d1, const tok_conv_desc* d2) { ConvRoute r; return dgrad2_route(d1, d2, &r) ? 1 : 0; }
 
 extern "C" int tok_conv_dgrad2(const tok_conv_desc* d1, const void* dy1, const void* w1_dgrad, const tok_conv_desc* d2,
                                const void* dy2, const void* w2_dgrad, const float* bias, void* dx, int accumulate,
                                const void* bn_y, const uint8_t* bn_mask, float* partial, void* stream) {
-  TOK_CHECK_ARG(dgrad2_geometry(d1, d2), "tok_conv_dgrad2: layers not served (ask tok_conv_dgrad2_ok)");
+  ConvRoute r;
+  TOK_CHECK_ARG(dgrad2_route(d1, d2, &r), "tok_conv_dgrad2: layers not served (ask tok_conv_dgrad2_ok)");
   TOK_CHECK_ARG(dy1 && w1_dgrad && dy2 && w2_dgrad && dx, "tok_conv_dgrad2: null pointer");
   TOK_CHECK_ARG((bn_y == nullptr) == (partial == nullptr), "tok_conv_dgrad2: bn_y and partial go together");
-  const long long rows = (long long)d1->n * d1->h * d1->w;
   PwArgs p = {};
   p.x = (const bf16*)dy1; p.w = (const bf16*)w1_dgrad; p.C = d1->k;
   p.x2 = (const bf16*)dy2; p.w2 = (const bf16*)w2_dgrad; p.C2 = d2->k;
   p.y = (bf16*)dx; p.bias = bias; p.stats = partial;
-  p.M = (int)rows; p.N = d1->c;
-  p.gridM = tok_cdiv(rows, 128); p.gridN = tok_cdiv(d1->c, 64);
-  p.stat_rows = pw_ring_grid(64, p.gridM, p.gridN) / p.gridN;
+  p.M = d1->n * d1->h * d1->w; p.N = d1->c;
+  p.gridM = r.gridM; p.gridN = r.gridN; p.stat_rows = r.stat_rows;
   p.e1 = accumulate ? (const bf16*)dx : nullptr;
   p.accumulate = accumulate;
   p.e2 = (const bf16*)bn_y; p.mask_in = bn_mask;
-  const int rc = pw_ring_launch(p, 64, tok_stream(stream));
+  const int rc = pw_ring_launch(p, 64, r.grid, tok_stream(stream));
   if (rc != 0) { tok_set_error("tok_conv_dgrad2: ring kernel refused the launch (%d)", rc); return TOK_ERR_INVALID; }
   TOK_CHECK_LAUNCH("tok_conv_dgrad2");
   return TOK_OK;

@@ -383,10 +383,8 @@ int conv_win_launch(ConvArgs& a, hipStream_t st) {
   g.XT = (a.W + tw - 1) / tw;
   g.fd_xt = make_fastdiv(g.XT);
   g.fd_h = make_fastdiv(a.H);
-  conv_win_tiles(a, &a.gridM, &a.gridN);
   const int bn = pick_wbn(a.K, a.gridM);
-  const int grid = conv_win_grid(a.gridM, a.gridN);
-  a.stat_rows = grid / a.gridN;
+  const int grid = a.grid;
   if (bn == 128) {
     if (tw == 16) launch_variant<16, 128>(a, g, grid, st);
     else if (tw == 32) launch_variant<32, 128>(a, g, grid, st);

@@ -317,13 +317,12 @@ bool gemm256_geometry(const ConvArgs& a) {
 // (a multiple of 8: conv_igemm.hip's kernels, which take over for the modes this one does not carry, run grids of 8 * gridN)
 int gemm256_rows(const ConvArgs& a) { return (tok_cdiv(a.M, GT) + 7) / 8 * 8; }
 
+void gemm256_tiles(const ConvArgs& a, int* gridM, int* gridN) { *gridM = tok_cdiv(a.M, GT); *gridN = tok_cdiv(a.K, GT); }
+int gemm256_grid(int gridM, int gridN) { return gridM * gridN < 256 ? gridM * gridN : 256; }   // one workgroup per CU, walking tiles
+
 int gemm256_launch(ConvArgs& a, hipStream_t st) {
   constexpr int smem = 2 * STAGE_B + 2 * 4 * GT * 4;
-  a.gridM = tok_cdiv(a.M, GT);
-  a.gridN = tok_cdiv(a.K, GT);
-  a.stat_rows = gemm256_rows(a);
-  const int tiles = a.gridM * a.gridN;
-  const int grid = tiles < 256 ? tiles : 256;          // one workgroup per CU, walking tiles
+  const int grid = a.grid;
   if (a.mask_store) tok_launch_lds<&gemm256_kernel<3>>(smem, dim3(grid), dim3(512), smem, st, a);
   else if (a.stats == nullptr) tok_launch_lds<&gemm256_kernel<0>>(smem, dim3(grid), dim3(512), smem, st, a);
   else if (a.bn_y == nullptr) tok_launch_lds<&gemm256_kernel<1>>(smem, dim3(grid), dim3(512), smem, st, a);

@@ -33,5 +33,6 @@ struct PwArgs {
 };
 
 // 0 = launched; > 0: this configuration is not served by the ring kernel (caller falls back); < 0: error
-int pw_ring_launch(const PwArgs& a, int bn_tile, hipStream_t st);
-int pw_ring_grid(int bn_tile, int gridM, int gridN);   // persistent grid size (for the statistics-row count)
+// `grid`: the workgroups the caller's route decided (pw_ring_grid of the layer that owns the statistics rows)
+int pw_ring_launch(const PwArgs& a, int bn_tile, int grid, hipStream_t st);
+int pw_ring_grid(int bn_tile, int gridM, int gridN);   // persistent grid size

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void pw_gemm_ring_kernel(PwA
 }
 
 template <int BN, bool BNEP>
-int launch_ring(const PwArgs& a, hipStream_t st) {
+int launch_ring(const PwArgs& a, int grid, hipStream_t st) {
   constexpr int STAGE = BM * BK * 2 + BN * BK * 2 + (BN == 64 ? 1024 : 4096);
   constexpr int smem = 3 * STAGE;
   const int KT1 = tok_cdiv(a.C, BK);
@@ -449,7 +449,6 @@ int launch_ring(const PwArgs& a, hipStream_t st) {
     fd_hw = make_pwdiv((uint32_t)hw);
     fd_w = make_pwdiv((uint32_t)a.sub_W);
   }
-  const int grid = pw_ring_grid(BN, a.gridM, a.gridN);
   tok_launch_lds<&pw_gemm_ring_kernel<BN, BNEP>>(smem, dim3(grid), dim3(256), smem, st, a, (uint32_t)xb, (uint32_t)wb, (uint32_t)yb,
                                                  (uint32_t)mb, KT, SPT, (uint32_t)e1b, fd_hw, fd_w, (uint32_t)x2b, (uint32_t)w2b, KT1);
   return 0;
@@ -467,7 +466,8 @@ int pw_ring_grid(int bn_tile, int gridM, int gridN) {
   return G;
 }
 
-int pw_ring_launch(const PwArgs& a, int bn_tile, hipStream_t st) {
+int pw_ring_launch(const PwArgs& a, int bn_tile, int grid, hipStream_t st) {
+  if (a.stats != nullptr && grid != a.stat_rows * a.gridN) return -1;   // one statistics row per workgroup of a channel tile
   if (a.C % 8 != 0 || a.N % 8 != 0) return 1;
   if (a.mask_in != nullptr && a.N % 64 != 0) return 1;       // mask rows are fetched as aligned 4 / 16-byte pieces
   if (a.accumulate && a.e1 == nullptr) return 1;
@@ -475,7 +475,7 @@ int pw_ring_launch(const PwArgs& a, int bn_tile, hipStream_t st) {
   if (a.e1_sub && (!a.accumulate || a.ep_scale != nullptr || a.sub_H <= 0 || a.sub_W <= 0 ||
                    a.M % (a.sub_H * a.sub_W) != 0)) return -1;
   const bool bnep = a.ep_scale != nullptr;
-  if (bn_tile == 64) return bnep ? launch_ring<64, true>(a, st) : launch_ring<64, false>(a, st);
+  if (bn_tile == 64) return bnep ? launch_ring<64, true>(a, grid, st) : launch_ring<64, false>(a, grid, st);
   if (bnep) return 1;
-  return launch_ring<128, false>(a, st);
+  return launch_ring<128, false>(a, grid, st);
 }

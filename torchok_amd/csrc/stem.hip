@@ -360,19 +360,21 @@ bool stem_win_serves(const ConvArgs& a) {
   return (long long)(a.M / (a.P * a.Q)) * tok_cdiv(a.P, ST_T) * tok_cdiv(a.Q, ST_T) >= 16;      // (tiny inputs: not worth a second kernel)
 }
 
-int stem_win_launch(ConvArgs& a, int stat_rows, hipStream_t st) {
+int stem_win_grid(const ConvArgs& a) {             // two workgroups per CU, never more than the tiles
+  const int tiles = (a.M / (a.P * a.Q)) * tok_cdiv(a.P, ST_T) * tok_cdiv(a.Q, ST_T);
+  return tiles < 512 ? tiles : 512;
+}
+
+int stem_win_launch(ConvArgs& a, hipStream_t st) {
   StemGeo g;
   g.TX = tok_cdiv(a.Q, ST_T);
   g.TY = tok_cdiv(a.P, ST_T);
   g.fd_tpi = make_fastdiv((uint32_t)(g.TX * g.TY));
   g.fd_tx = make_fastdiv((uint32_t)g.TX);
   g.tiles = (a.M / (a.P * a.Q)) * g.TX * g.TY;
-  g.rows = stat_rows;
-  int grid = 512;                                  // two workgroups per CU
-  if (grid > g.tiles) grid = g.tiles;
-  if (a.stats != nullptr && grid > stat_rows) grid = stat_rows;
+  g.rows = a.stat_rows;
   constexpr int smem = 2 * ST_BUF;
-  hipLaunchKernelGGL(stem_win_kernel, dim3(grid), dim3(256), smem, st, a, g);
+  hipLaunchKernelGGL(stem_win_kernel, dim3(a.grid), dim3(256), smem, st, a, g);
   return 0;
 }
 

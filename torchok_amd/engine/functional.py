@@ -398,52 +398,60 @@ class _ConvBnActNode(Node):
                 d, x.data, dy, k, c, weight=conv.weight, bias=conv.bias if bias_in_wgrad else None)[1:])
         if x_need:
             prod = x.node
-            fuse = (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.wants_fused_bwd_stats()
-                    and prod.fused_partial is None)
-            # (a fused unit WITHOUT activation has no ReLU bits: its d(out) is dz itself and takes the plain path)
-            mask_fuse = (isinstance(prod, _Unit3Node) and prod.relu and prod.mask is not None and is_last_contribution(x)
-                         and prod.masked_partial is None)
+            rider = _dgrad_rider(x)
             sub = x.grad_sub if getattr(self, 'sub_capable', False) else None
             tgt, acc = grad_target(x, sub_ok=sub is not None)
+            partial = _rider_partial(lib, rider, prod, d, x.cp, g.device)
+            bn_y = ptr(prod.y) if rider == BN_SUMS else None
+            bn_mask = ptr(prod.mask) if (rider == MASKED_DZ or (rider == BN_SUMS and prod.relu)) else None
             if sub is not None:
                 # d(x) = this data gradient + the parked gradient of x[:, ::2, ::2] (a strided projection shortcut): one
-                # launch, d(x) written once; the epilogue variants of the plain call sites below
+                # launch, d(x) written once, with the rider's epilogue
                 x.grad_sub = None
                 assert acc == 0
-                rows = lib.tok_conv_dgrad_stat_rows(d)
-                if mask_fuse:
-                    partial = torch.empty((2, rows, x.cp), dtype=F32, device=g.device)
-                    _C.check(lib.tok_conv_dgrad_subacc(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), ptr(sub), None, ptr(prod.mask),
-                                                       ptr(partial), 1, st), 'tok_conv_dgrad_subacc')
-                    prod.masked_partial = (partial, rows)
-                elif fuse:
-                    partial = torch.empty((2, rows, x.cp), dtype=F32, device=g.device)
-                    _C.check(lib.tok_conv_dgrad_subacc(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), ptr(sub), ptr(prod.y),
-                                                       ptr(prod.mask) if prod.relu else None, ptr(partial), 0, st),
-                             'tok_conv_dgrad_subacc')
-                    prod.fused_partial = (partial, rows)
-                else:
-                    _C.check(lib.tok_conv_dgrad_subacc(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), ptr(sub), None, None, None, 0,
-                                                       st), 'tok_conv_dgrad_subacc')
-            elif mask_fuse:
-                # this dgrad completes the gradient of a fused unit-3 output: its epilogue stores dz = relu_mask * d(out)
-                # (what that unit's backward and its shortcut both consume) and reduces sum(dz)
-                rows = lib.tok_conv_dgrad_stat_rows(d)
-                partial = torch.empty((2, rows, x.cp), dtype=F32, device=g.device)
-                _C.check(lib.tok_conv_dgrad_maskstore(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, ptr(prod.mask),
-                                                      ptr(partial), st), 'tok_conv_dgrad_maskstore')
-                prod.masked_partial = (partial, rows)
-            elif fuse:
-                # this dgrad completes d(x): its epilogue also reduces the BatchNorm-backward sums of the
-                # unit that produced x (saves that unit a full pass over d(x) and y)
-                rows = lib.tok_conv_dgrad_stat_rows(d)
-                partial = torch.empty((2, rows, x.cp), dtype=F32, device=g.device)
-                _C.check(lib.tok_conv_dgrad_bnstats(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, ptr(prod.y),
-                                                    ptr(prod.mask) if prod.relu else None, ptr(partial), st),
+                _C.check(lib.tok_conv_dgrad_subacc(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), ptr(sub), bn_y, bn_mask, ptr(partial),
+                                                   int(rider == MASKED_DZ), st), 'tok_conv_dgrad_subacc')
+            elif rider == MASKED_DZ:
+                _C.check(lib.tok_conv_dgrad_maskstore(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, bn_mask, ptr(partial), st),
+                         'tok_conv_dgrad_maskstore')
+            elif rider == BN_SUMS:
+                _C.check(lib.tok_conv_dgrad_bnstats(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, bn_y, bn_mask, ptr(partial), st),
                          'tok_conv_dgrad_bnstats')
-                prod.fused_partial = (partial, rows)
             else:
                 _C.check(lib.tok_conv_dgrad(d, ptr(dy), ptr(self.pk.dgrad), ptr(tgt), acc, st), 'tok_conv_dgrad')
+
+
+# ---- who rides a data gradient ------------------------------------------------------------------------------------------
+# The launch that completes d(x) can finish work of the unit that produced x in its epilogue:
+BN_SUMS = 'bn_sums'          # the BatchNorm-backward sums sum(dz), sum(dz * y) of a _ConvBnActNode (saves it a pass over d(x) and y)
+MASKED_DZ = 'masked_dz'      # dz = relu_mask * d(out) and sum(dz) of a fused _Unit3Node (what its backward and its shortcut consume)
+
+
+def _dgrad_rider(x: TTensor):
+    """What rides the next data gradient into `x`: BN_SUMS, MASKED_DZ or None.  Only the last contribution completes d(x), and
+    only once per producer."""
+    prod = x.node
+    if (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.wants_fused_bwd_stats()
+            and prod.fused_partial is None):
+        return BN_SUMS
+    # (a fused unit WITHOUT activation has no ReLU bits: its d(out) is dz itself and takes the plain path)
+    if (isinstance(prod, _Unit3Node) and prod.relu and prod.mask is not None and is_last_contribution(x)
+            and prod.masked_partial is None):
+        return MASKED_DZ
+    return None
+
+
+def _rider_partial(lib, rider, prod, d, cp: int, dev) -> Optional[torch.Tensor]:
+    """The (2, rows, cp) partial sums the data gradient of layer `d` writes for `rider`, left on the producer for its backward."""
+    if rider is None:
+        return None
+    rows = lib.tok_conv_dgrad_stat_rows(d)
+    partial = torch.empty((2, rows, cp), dtype=F32, device=dev)
+    if rider == MASKED_DZ:
+        prod.masked_partial = (partial, rows)
+    else:
+        prod.fused_partial = (partial, rows)
+    return partial
 
 
 # ---- unit 3 of a bottleneck: 1x1 conv -> BatchNorm -> + shortcut -> ReLU without the pre-normalisation tensor ----------
@@ -537,33 +545,19 @@ class _Unit3Node(Node):
             return
         # 5. d(x) = dz wa + x wb + cvec  (+ the BatchNorm-backward sums of the unit that produced x)
         prod = x.node
-        fuse = (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.wants_fused_bwd_stats()
-                and prod.fused_partial is None)
+        fuse = _dgrad_rider(x) == BN_SUMS        # (the masked-dz store is not an epilogue of these launches)
         tgt, acc = grad_target(x)
         dpp = _pointwise_desc(x, p)
+        part2 = _rider_partial(lib, BN_SUMS if fuse else None, prod, dpp, p, dev)
+        bn_y = ptr(prod.y) if fuse else None
+        bn_mask = ptr(prod.mask) if (fuse and prod.relu) else None
         if lib.tok_conv_dgrad2_ok(d, dpp):
             # both products in one launch of the ring kernel: d(x) is stored once
-            part2 = None
-            if fuse:
-                rows2 = lib.tok_conv_dgrad_stat_rows(dpp)
-                part2 = torch.empty((2, rows2, p), dtype=F32, device=dev)
-            _C.check(lib.tok_conv_dgrad2(d, ptr(dz), ptr(wa), dpp, ptr(x.data), ptr(wb), ptr(cvec), ptr(tgt), acc,
-                                         ptr(prod.y) if fuse else None, ptr(prod.mask) if (fuse and prod.relu) else None,
+            _C.check(lib.tok_conv_dgrad2(d, ptr(dz), ptr(wa), dpp, ptr(x.data), ptr(wb), ptr(cvec), ptr(tgt), acc, bn_y, bn_mask,
                                          ptr(part2), st), 'tok_conv_dgrad2')
-            if fuse:
-                prod.fused_partial = (part2, rows2)
-            if self.region is not None:
-                self.region.keep_until_join(dz, wa, wb, cvec, G, scratch)
-            return
-        _C.check(lib.tok_conv_dgrad(d, ptr(dz), ptr(wa), ptr(tgt), acc, st), 'tok_conv_dgrad')
-        if fuse:
-            rows2 = lib.tok_conv_dgrad_stat_rows(dpp)
-            part2 = torch.empty((2, rows2, p), dtype=F32, device=dev)
-            _C.check(lib.tok_conv_dgrad_bias(dpp, ptr(x.data), ptr(wb), ptr(cvec), ptr(tgt), 1, ptr(prod.y),
-                                             ptr(prod.mask) if prod.relu else None, ptr(part2), st), 'tok_conv_dgrad_bias')
-            prod.fused_partial = (part2, rows2)
         else:
-            _C.check(lib.tok_conv_dgrad_bias(dpp, ptr(x.data), ptr(wb), ptr(cvec), ptr(tgt), 1, None, None, None, st),
+            _C.check(lib.tok_conv_dgrad(d, ptr(dz), ptr(wa), ptr(tgt), acc, st), 'tok_conv_dgrad')
+            _C.check(lib.tok_conv_dgrad_bias(dpp, ptr(x.data), ptr(wb), ptr(cvec), ptr(tgt), 1, bn_y, bn_mask, ptr(part2), st),
                      'tok_conv_dgrad_bias')
         if self.region is not None:
             self.region.keep_until_join(dz, wa, wb, cvec, G, scratch)
