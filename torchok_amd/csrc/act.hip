@@ -3,30 +3,13 @@
 //   dz = dout * hswish'(z)     hswish'(z) = 0 (z < -3), z/3 + 0.5 (-3 <= z <= 3), 1 (z > 3)      dy = c1*dz + c2*y + c3
 // Nothing is kept between the passes but y: forward, reduce and apply each recompute z = fmaf(y, scale, shift) from the stored
 // bf16 y (the expression bn_act_fwd_kernel evaluates), so all three see the same z and the same branch of the derivative.
-// Geometry is that of bn.hip: min(C/8, 256) channel groups across the block, 8 channels (16 bytes) per lane, grid-stride
+// Geometry: make_geo (tok_common.h), min(C/8, 256) channel groups across the block, 8 channels (16 bytes) per lane, grid-stride
 // over rows; a lane keeps its channel group's coefficients in registers.  The reduce leaves partial[2][rows][C] in the row
 // layout of tok_bn_bwd_reduce (rows = tok_bn_bwd_rows): tok_bn_bwd_finalize folds it with dzy_form = 0.  Fixed summation
 // order, no atomics: two runs give the same bits.
 #include "tok_common.h"
 
 namespace {
-
-struct Geo {
-  int cge, rpb;
-};
-inline Geo make_geo(int c) {
-  Geo g;
-  g.cge = (c >> 3) < 256 ? (c >> 3) : 256;
-  g.rpb = 256 / g.cge;
-  return g;
-}
-
-__device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 __device__ __forceinline__ float hswish_f(float z) {
   return z * __builtin_amdgcn_fmed3f(z + 3.f, 0.f, 6.f) * (1.f / 6.f);

@@ -13,30 +13,11 @@ static thread_local hipEvent_t t_done_event = nullptr;
 
 namespace {
 
-// Block geometry shared by the streaming kernels: CGE = min(C/8, 256) channel groups across
-// the block, RPB = 256 / CGE rows per block iteration.
-struct Geo {
-  int cg_total, cge, rpb;
-};
-inline Geo make_geo(int c) {
-  Geo g;
-  g.cg_total = c / 8;
-  g.cge = g.cg_total < 256 ? g.cg_total : 256;
-  g.rpb = 256 / g.cge;
-  return g;
-}
 inline int stream_blocks(int64_t m, const Geo& g, int cap) {
   int64_t b = (m + g.rpb - 1) / g.rpb;
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
-}
-
-__device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 //   forward : out = bf16(x + (s_b * gamma[c]) * a)        s_b = row_scale[row / rows_per_sample] (1 without drop-path scales)
 //   backward: da (=|+=) bf16((s_b * gamma[c]) * dout);  partial[block][c] = sum over the block's rows of s_b * dout * a, folded
 //             by tok_colsum_f32 into dgamma (the tok_bn_bwd_reduce -> finalize pattern); dx = dout is the caller's (no pass).
-// Geometry is that of act.hip: min(d/8, 256) channel groups across the block, 8 channels (16 bytes) per lane, grid-stride over
+// Geometry: make_geo (tok_common.h), min(d/8, 256) channel groups across the block, 8 channels (16 bytes) per lane, grid-stride over
 // rows.  Fixed summation order, no atomics: two runs give the same bits.
 #include "tok_common.h"
 
@@ -10,26 +10,10 @@ namespace {
 
 constexpr int LS_BLOCKS = 512;     // block cap of both passes = partial rows of the backward
 
-struct Geo {
-  int cge, rpb;
-};
-inline Geo make_geo(int d) {
-  Geo g;
-  g.cge = (d >> 3) < 256 ? (d >> 3) : 256;
-  g.rpb = 256 / g.cge;
-  return g;
-}
 inline int blocks_for_rows(int64_t rows, int d) {
   const Geo g = make_geo(d);
   const int64_t b = (rows + g.rpb - 1) / g.rpb;
   return (int)(b < LS_BLOCKS ? b : LS_BLOCKS);
-}
-
-__device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
 __global__ __launch_bounds__(256) void layer_scale_fwd_kernel(const bf16* __restrict__ x, const bf16* __restrict__ a,

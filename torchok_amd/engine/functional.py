@@ -230,24 +230,69 @@ def _check_conv(conv: nn.Conv2d):
 
 # ---- conv + bn + (add) + relu ------------------------------------------------------------------------
 
+RELU = 'relu'
 HARD_SWISH = 'hard_swish'
 
 
-def _check_act(act, bn, shortcut=None, pool=False, defer_apply=False) -> bool:
-    """act=None: the unit's activation is what `relu` says.  act='hard_swish': BatchNorm + hard-swish on tok_bn_hswish_*, which
-    keeps no mask and knows no shortcut, pooled or deferred form (MobileNetV3 never activates after a residual add)."""
+def _check_act(relu, act, bn, shortcut=None, pool=False, defer_apply=False):
+    """The unit's one activation, None / RELU / HARD_SWISH, from the public keywords.  act=None: what `relu` says.
+    act='hard_swish' (`relu` is not looked at): BatchNorm + hard-swish on tok_bn_hswish_*, which keeps no mask and knows no
+    shortcut, pooled or deferred form (MobileNetV3 never activates after a residual add)."""
     if act is None:
-        return False
+        return RELU if relu else None
     if act != HARD_SWISH:
         raise NotImplementedError(f'torchok_amd activation {act!r}: None (ReLU / identity by `relu`) or {HARD_SWISH!r}')
     if bn is None or shortcut is not None or pool or defer_apply:
         raise NotImplementedError(f"act={HARD_SWISH!r}: BatchNorm units without shortcut, pool or defer_apply only")
-    return True
+    return HARD_SWISH
+
+
+# ---- the BatchNorm stage of a unit: every "producer -> BatchNorm -> activation" unit takes it from here ---------------
+
+def batch_stats(bn: nn.BatchNorm2d) -> bool:
+    """Does this BatchNorm normalise with the statistics of the batch (training mode, or no running statistics kept)?"""
+    return bn.training or bn.running_mean is None
+
+
+def bn_coeffs(lib, st, bn, stats, rows, m, kp, dev):
+    """(scale, shift, mean, rstd) per channel: from the producer's partial sums `stats` [2][rows][kp] over m rows (running
+    statistics updated when the module tracks them), or, stats=None, from the running statistics (mean = rstd = None)."""
+    # one allocation for the per-channel vectors (an allocator call costs the launch thread 2-3 us; HRNet-W48 makes 307
+    # of these units per step)
+    vec = torch.empty((4, kp), dtype=F32, device=dev)
+    scale, shift = vec[0], vec[1]
+    if stats is None:
+        _C.check(lib.tok_bn_eval_coeffs(ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+                                        float(bn.eps), kp, bn.num_features, ptr(scale), ptr(shift), st), 'tok_bn_eval_coeffs')
+        return scale, shift, None, None
+    if bn.momentum is None:
+        raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
+    mean, rstd = vec[2], vec[3]
+    track = bn.training and bn.track_running_stats and bn.running_mean is not None
+    _C.check(lib.tok_bn_finalize(ptr(stats), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(bn.bias),
+                                 ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
+                                 ptr(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps),
+                                 ptr(mean), ptr(rstd), ptr(scale), ptr(shift), st), 'tok_bn_finalize')
+    return scale, shift, mean, rstd
+
+
+def bn_apply(lib, st, y, scale, shift, act, shortcut, want_mask, m, kp):
+    """The plain apply pass out = act(y * scale + shift (+ shortcut)) -> (out_data, mask).  `want_mask` is the caller's
+    rule for keeping the ReLU bits; hard-swish keeps none."""
+    out_data = torch.empty_like(y)
+    if act == HARD_SWISH:
+        _C.check(lib.tok_bn_hswish_fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, kp, st), 'tok_bn_hswish_fwd')
+        return out_data, None
+    mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=y.device) if want_mask else None
+    _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), ptr(shortcut.data) if shortcut is not None else None,
+                                int(act == RELU), ptr(out_data), ptr(mask), m, kp, st), 'tok_bn_act_fwd')
+    return out_data, mask
 
 
 class _ConvBnActNode(Node):
     needs_backward = True
-    act = None                      # 'hard_swish': dz is recomputed from y in tok_bn_hswish_bwd_* (no mask, relu is False)
+    act = None                      # None / RELU / HARD_SWISH (dz is recomputed from y in tok_bn_hswish_bwd_*: no mask)
+    relu = property(lambda self: self.act == RELU)
 
     def __init__(self):
         self.x = self.out = self.shortcut = None
@@ -265,12 +310,12 @@ class _ConvBnActNode(Node):
     def wants_fused_bwd_stats(self) -> bool:
         """Can the kernel that completes d(out) also reduce sum(dz), sum(dz*y) for this unit?"""
         # (the dgrad epilogues know the ReLU mask only: a hard-swish producer takes the stand-alone reduce)
-        return (self.bn is not None and self.batch_stats and (not self.relu or self.mask is not None) and self.pool is None
-                and self.act is None)
+        return (self.bn is not None and self.batch_stats and self.pool is None
+                and (self.act is None or (self.act == RELU and self.mask is not None)))
 
     def _apply_bwd(self, lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp):
         """dy = c1*dz + c2*y + c3 (and the shortcut's dz) for the unit's activation."""
-        if self.act is not None:
+        if self.act == HARD_SWISH:
             _C.check(lib.tok_bn_hswish_bwd_apply(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(coef), ptr(dy), m, kp,
                                                  st), 'tok_bn_hswish_bwd_apply')
         else:
@@ -300,7 +345,7 @@ class _ConvBnActNode(Node):
                 _C.check(lib.tok_bn_pool_bwd_reduce(ptr(g), ptr(self.pool), ptr(self.y), ptr(self.scale), ptr(self.shift),
                                                     ptr(self.mean), ptr(self.rstd), n_, h_, w_, kp, ptr(partial), st),
                          'tok_bn_pool_bwd_reduce')
-            elif self.act is not None:
+            elif self.act == HARD_SWISH:
                 partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
                 _C.check(lib.tok_bn_hswish_bwd_reduce(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(self.mean),
                                                       ptr(self.rstd), m, kp, ptr(partial), st), 'tok_bn_hswish_bwd_reduce')
@@ -315,6 +360,29 @@ class _ConvBnActNode(Node):
                                          ptr(self.rstd), ptr(gbuf), ptr(bbuf), ptr(coef), acc, dzy, st), 'tok_bn_bwd_finalize')
         finish()
         return coef
+
+    def _bn_bwd(self, lib, st, g, m, kp, need_dy, apply=None):
+        """The BatchNorm (+ activation) backward of the unit: dgamma / dbeta, then dy — None when nobody needs it.
+        `apply(mask, coef, dy)` stands in for the plain apply launch (the conv unit's own forms)."""
+        bn = self.bn
+        g_need, b_need = bn.weight.requires_grad, bn.bias.requires_grad
+        mask = self.mask if self.act == RELU else None
+        if self.batch_stats:
+            coef = self._finalize_bwd(lib, st, g, mask, m, kp, g_need, b_need)
+        else:
+            # eval-mode BN: y -> out is a fixed affine map: dy = scale * dz, dgamma/dbeta unsupported
+            if g_need or b_need:
+                raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')
+            coef = torch.zeros((3, kp), dtype=F32, device=g.device)
+            coef[0] = self.scale
+        if not need_dy:
+            return None
+        dy = torch.empty_like(self.y)
+        if apply is not None:
+            apply(mask, coef, dy)
+        else:
+            self._apply_bwd(lib, st, g, mask, coef, dy, None, 0, m, kp)
+        return dy
 
     def backward(self):
         lib, st = _C.lib(), stream_ptr()
@@ -334,22 +402,11 @@ class _ConvBnActNode(Node):
         side = w_need and PG.goes_side(self, g, PG.CONV, m)
 
         if bn is not None:
-            g_need = bn.weight.requires_grad
-            b_need = bn.bias.requires_grad
             sc_need = sc is not None and sc.requires_grad
-            mask = self.mask if self.relu else None
-            need_dy = w_need or x_need or bias_need
-            if self.batch_stats:
-                coef = self._finalize_bwd(lib, st, g, mask, m, kp, g_need, b_need)
-            else:
-                # eval-mode BN: y -> out is a fixed affine map: dy = scale * dz, dgamma/dbeta unsupported
-                if g_need or b_need:
-                    raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')
-                coef = torch.zeros((3, kp), dtype=F32, device=g.device)
-                coef[0] = self.scale
-            if need_dy or sc_need:
-                dy = torch.empty_like(self.y)
-                if side and self.pool is None and self.act is None:
+
+            def apply(mask, coef, dy):
+                nonlocal apply_event
+                if side and self.pool is None and self.act != HARD_SWISH:
                     # the weight gradient will be forked to the side stream behind THIS apply pass: the pass carries the
                     # completion event itself (no event-record packet on the main queue)
                     apply_event = self.region.raw_event()     # armed right in front of the launch that carries it (below)
@@ -366,16 +423,15 @@ class _ConvBnActNode(Node):
                     n_, h_, w_, _ = self.y.shape
                     _C.check(lib.tok_bn_pool_bwd_apply(ptr(g), ptr(self.pool), ptr(self.y), ptr(self.scale), ptr(self.shift),
                                                        ptr(coef), n_, h_, w_, kp, ptr(dy), st), 'tok_bn_pool_bwd_apply')
-                else:
+                    return
+                if apply_event is not None:
+                    lib.tok_next_launch_event(apply_event)
+                try:
+                    self._apply_bwd(lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp)
+                finally:
                     if apply_event is not None:
-                        lib.tok_next_launch_event(apply_event)
-                    try:
-                        self._apply_bwd(lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp)
-                    finally:
-                        if apply_event is not None:
-                            lib.tok_next_launch_event(None)   # never left armed for an unrelated later launch
-            else:
-                dy = None
+                        lib.tok_next_launch_event(None)   # never left armed for an unrelated later launch
+            dy = self._bn_bwd(lib, st, g, m, kp, w_need or x_need or bias_need or sc_need, apply)
         else:
             dy = g  # plain conv (+bias): the output gradient IS dy
         out.grad = None
@@ -632,9 +688,8 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     the unit's usual one (it never reads the normalised values of a unit without activation)."""
     if pool and (bn is None or not relu or shortcut is not None or x.data.dim() != 4):
         raise ValueError('conv_bn_act(pool=True): BatchNorm + ReLU on a 4-D input, no shortcut')
-    hswish = _check_act(act, bn, shortcut, pool, defer_apply)
-    if hswish:
-        relu = False
+    act = _check_act(relu, act, bn, shortcut, pool, defer_apply)
+    relu = act == RELU
     await_ready(x, shortcut)
     lib, st = _C.lib(), stream_ptr()
     if isinstance(conv, nn.Linear):
@@ -655,12 +710,12 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     kp = pad8(k_real)
     if bn is not None and bn.num_features != k_real:
         raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {k_real}')
-    if (FUSE_UNIT3 and bn is not None and not hswish and (relu == (shortcut is not None)) and not pool
+    if (FUSE_UNIT3 and bn is not None and act != HARD_SWISH and (relu == (shortcut is not None)) and not pool
             and isinstance(conv, nn.Conv2d)
             and r == 1 and s == 1 and stride == 1 and pad == 0 and conv.bias is None and x.data.dim() == 4
             and x.c == x.cp and kp == k_real and x.cp <= 1024 and (shortcut is None or shortcut.cp == kp)
             and x.rows() >= UNIT3_MIN_ROWS and kp >= 2 * x.cp
-            and (bn.training or bn.running_mean is None) and conv.weight.permute(0, 2, 3, 1).is_contiguous()):
+            and batch_stats(bn) and conv.weight.permute(0, 2, 3, 1).is_contiguous()):
         # the residual unit of a bottleneck (conv3 + bn3 + shortcut + ReLU) and its stride-1 projection shortcut (conv + bn):
         # normalise (add, activate) in the GEMM epilogue — the wide pre-BatchNorm tensor is never stored
         return _unit3_forward(region, x, conv, bn, shortcut, kp, relu)
@@ -672,73 +727,42 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     dev = x.data.device
     y = torch.empty((d.n, d.p, d.q, kp), dtype=BF16, device=dev)
     m = d.n * d.p * d.q
-    batch_stats = bn is not None and (bn.training or bn.running_mean is None)
-    stats = None
-    if batch_stats:
+    batch = bn is not None and batch_stats(bn)
+    stats, rows = None, 0
+    if batch:
         rows = lib.tok_conv_fwd_stat_rows(d)
         stats = torch.empty((2, rows, kp), dtype=F32, device=dev)
     node = _ConvBnActNode()
     _C.check(lib.tok_conv_fwd(d, ptr(x4.data), ptr(pk.fwd), ptr(pk.bias), ptr(y), ptr(stats), st), 'tok_conv_fwd')
 
     if bn is not None:
-        # one allocation for the per-channel vectors (an allocator call costs the launch thread 2-3 us; HRNet-W48 makes 307
-        # of these units per step)
-        vec = torch.empty((4, kp), dtype=F32, device=dev)
-        scale, shift = vec[0], vec[1]
-        mean = rstd = None
-        if batch_stats:
-            if bn.momentum is None:
-                raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
-            mean, rstd = vec[2], vec[3]
-            track = bn.training and bn.track_running_stats and bn.running_mean is not None
-            _C.check(lib.tok_bn_finalize(ptr(stats), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(bn.bias),
-                                         ptr(bn.running_mean) if track else None,
-                                         ptr(bn.running_var) if track else None,
-                                         ptr(bn.num_batches_tracked) if track else None,
-                                         float(bn.momentum), float(bn.eps), ptr(mean), ptr(rstd),
-                                         ptr(scale), ptr(shift), st), 'tok_bn_finalize')
-        else:
-            _C.check(lib.tok_bn_eval_coeffs(ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                                            ptr(bn.running_var), float(bn.eps), kp, bn.num_features, ptr(scale), ptr(shift), st),
-                     'tok_bn_eval_coeffs')
-        mask = None
+        scale, shift, mean, rstd = bn_coeffs(lib, st, bn, stats, rows, m, kp, dev)
+        mask = cs_part = None
         deferred = bool(defer_apply and not relu and shortcut is None and not pool and x.data.dim() == 4)
         if deferred:
             out_data = y
-            cs_part = None
         elif pool:
             p2, q2 = (d.p + 2 - 3) // 2 + 1, (d.q + 2 - 3) // 2 + 1
             out_data = torch.empty((d.n, p2, q2, kp), dtype=BF16, device=dev)
             node.pool = torch.empty((d.n, p2, q2, kp), dtype=torch.uint8, device=dev)
-            if STEM_POOLED_STATS and region.grad_mode and batch_stats:
+            if STEM_POOLED_STATS and region.grad_mode and batch:
                 node.ypool = torch.empty_like(out_data)
             _C.check(lib.tok_bn_relu_maxpool_fwd(ptr(y), ptr(scale), ptr(shift), d.n, d.p, d.q, kp, ptr(out_data),
                                                  ptr(node.pool), ptr(node.ypool), st), 'tok_bn_relu_maxpool_fwd')
-        elif hswish:
-            out_data = torch.empty_like(y)
-            cs_part = None
-            _C.check(lib.tok_bn_hswish_fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, kp, st), 'tok_bn_hswish_fwd')
-        else:
-            out_data = torch.empty_like(y)
-            if relu and region.grad_mode:
-                # ReLU bits for the backward pass, running statistics included: the apply kernel's mask-less fallback
-                # recomputes the pattern from y alone and would leave out a shortcut added before the activation
-                mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=dev)
+        elif (FUSE_UNIT3 and r == 3 and relu and shortcut is None and m >= UNIT3_MIN_ROWS
+              and kp == k_real and kp <= 1024 and region.grad_mode and batch):
             # a 3x3 unit of a bottleneck feeds the fused residual unit, which wants colsum(z) of its input: the activation pass
             # has z in registers (saves that unit a stand-alone pass over z)
-            want_cs = (FUSE_UNIT3 and r == 3 and relu and shortcut is None and m >= UNIT3_MIN_ROWS
-                       and kp == k_real and kp <= 1024 and region.grad_mode and batch_stats)
-            cs_part = None
-            if want_cs:
-                cs_rows = lib.tok_bn_act_fwd_colsum_rows(m, kp)
-                cs_part = torch.empty((cs_rows, kp), dtype=F32, device=dev)
-            if want_cs:
-                _C.check(lib.tok_bn_act_fwd_colsum(ptr(y), ptr(scale), ptr(shift), None, int(relu), ptr(out_data), ptr(mask),
-                                                   m, kp, ptr(cs_part), st), 'tok_bn_act_fwd_colsum')
-            else:
-                _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift),
-                                            ptr(shortcut.data) if shortcut is not None else None,
-                                            int(relu), ptr(out_data), ptr(mask), m, kp, st), 'tok_bn_act_fwd')
+            out_data = torch.empty_like(y)
+            mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=dev)
+            cs_rows = lib.tok_bn_act_fwd_colsum_rows(m, kp)
+            cs_part = torch.empty((cs_rows, kp), dtype=F32, device=dev)
+            _C.check(lib.tok_bn_act_fwd_colsum(ptr(y), ptr(scale), ptr(shift), None, 1, ptr(out_data), ptr(mask),
+                                               m, kp, ptr(cs_part), st), 'tok_bn_act_fwd_colsum')
+        else:
+            # ReLU bits for the backward pass whenever gradients are on, running statistics included: the apply kernel's
+            # mask-less fallback recomputes the pattern from y alone and would leave out a shortcut added before the activation
+            out_data, mask = bn_apply(lib, st, y, scale, shift, act, shortcut, relu and region.grad_mode, m, kp)
         node.mask = mask
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
     else:
@@ -753,14 +777,12 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     out = TTensor(out_data, k_real, requires_grad=req)
     if bn is not None and deferred:
         out.affine = (scale, shift)
-    if bn is not None and not pool and cs_part is not None:
+    if bn is not None and cs_part is not None:
         out.colsum_part = (cs_part, cs_rows)
     if req:
         node.x, node.out, node.shortcut, node.y = x, out, shortcut, y
         node.conv, node.bn, node.desc, node.pk = conv, bn, d, pk
-        node.relu, node.batch_stats = relu, batch_stats
-        if hswish:
-            node.act = act
+        node.act, node.batch_stats = act, batch
         out.node = node
         node.sub_capable = False
         if x.requires_grad:
@@ -1004,24 +1026,15 @@ class _DwConvBnActNode(_ConvBnActNode):
         g = out.grad
         if g is None:
             return
-        conv, bn, x = self.conv, self.bn, self.x
+        conv, x = self.conv, self.x
         n, h, w, c = x.shape
         k, stride = conv.kernel_size[0], conv.stride[0]
         m, kp = self.y.numel() // self.y.shape[-1], self.y.shape[-1]
         w_need, x_need = conv.weight.requires_grad, x.requires_grad
-        mask = self.mask if self.relu else None
-        if self.batch_stats:
-            coef = self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
-        else:
-            if bn.weight.requires_grad or bn.bias.requires_grad:
-                raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')
-            coef = torch.zeros((3, kp), dtype=F32, device=g.device)
-            coef[0] = self.scale
+        dy = self._bn_bwd(lib, st, g, m, kp, w_need or x_need)
         out.grad = None
-        if not (w_need or x_need):
+        if dy is None:
             return
-        dy = torch.empty_like(self.y)
-        self._apply_bwd(lib, st, g, mask, coef, dy, None, 0, m, kp)
         if w_need:
             ws_bytes = lib.tok_dwconv_wgrad_ws_bytes(n, h, w, c, k, stride)
             ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
@@ -1040,9 +1053,7 @@ def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2
     """out = act(bn(conv(x))) for a depthwise `conv` ([timm] create_conv2d(depthwise=True) + BatchNormAct2d of the MnasNet
     and MobileNetV3 blocks).  act=None: `relu` decides; act='hard_swish': as in conv_bn_act.  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
     rows tok_bn_finalize folds); eval mode uses the running statistics; track_running_stats=False uses batch statistics."""
-    hswish = _check_act(act, bn)
-    if hswish:
-        relu = False
+    act = _check_act(relu, act, bn)
     await_ready(x)
     _check_dwconv(conv, x)
     if bn.num_features != conv.out_channels:
@@ -1052,46 +1063,24 @@ def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2
     k, stride = conv.kernel_size[0], conv.stride[0]
     p, q = (h - 1) // stride + 1, (w - 1) // stride + 1
     dev = x.data.device
-    batch_stats = bn.training or bn.running_mean is None
+    batch = batch_stats(bn)
     y = torch.empty((n, p, q, c), dtype=BF16, device=dev)
     stats, rows = None, 0
-    if batch_stats:
-        if bn.momentum is None:
-            raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
+    if batch:
         rows = lib.tok_dwconv_rows(n, h, w, c, k, stride)
         stats = torch.empty((2, rows, c), dtype=F32, device=dev)
     _C.check(lib.tok_dwconv_fwd(ptr(x.data), ptr(conv.weight), n, h, w, c, c, k, stride, ptr(y), ptr(stats), st),
              'tok_dwconv_fwd')
-    vec = torch.empty((4, c), dtype=F32, device=dev)
-    scale, shift = vec[0], vec[1]
-    mean = rstd = None
     m = n * p * q
-    if batch_stats:
-        mean, rstd = vec[2], vec[3]
-        track = bn.training and bn.track_running_stats and bn.running_mean is not None
-        _C.check(lib.tok_bn_finalize(ptr(stats), rows, m, c, c, ptr(bn.weight), ptr(bn.bias),
-                                     ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                                     ptr(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps),
-                                     ptr(mean), ptr(rstd), ptr(scale), ptr(shift), st), 'tok_bn_finalize')
-    else:
-        _C.check(lib.tok_bn_eval_coeffs(ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
-                                        float(bn.eps), c, c, ptr(scale), ptr(shift), st), 'tok_bn_eval_coeffs')
+    scale, shift, mean, rstd = bn_coeffs(lib, st, bn, stats, rows, m, c, dev)
     training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad
                                      or bn.bias.requires_grad)
-    mask = torch.empty((m, c // 8), dtype=torch.uint8, device=dev) if (relu and training) else None
-    out_data = torch.empty_like(y)
-    if hswish:
-        _C.check(lib.tok_bn_hswish_fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, c, st), 'tok_bn_hswish_fwd')
-    else:
-        _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), None, int(relu), ptr(out_data), ptr(mask), m, c, st),
-                 'tok_bn_act_fwd')
+    out_data, mask = bn_apply(lib, st, y, scale, shift, act, None, act == RELU and training, m, c)
     out = TTensor(out_data, c, requires_grad=bool(training))
     if training:
         node = _DwConvBnActNode()
-        if hswish:
-            node.act = act
         node.x, node.out, node.y, node.mask = x, out, y, mask
-        node.conv, node.bn, node.relu, node.batch_stats = conv, bn, relu, batch_stats
+        node.conv, node.bn, node.act, node.batch_stats = conv, bn, act, batch
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
         out.node = node
         if x.requires_grad:

@@ -49,21 +49,16 @@ class _CommutedNeckNode(EF._ConvBnActNode):
         g = out.grad
         if g is None:
             return
-        conv, bn = self.conv, self.bn
+        conv = self.conv
         kp = self.y.shape[-1]
         m = self.y.numel() // kp
         n, h, w, _ = self.y.shape
         w_need = conv.weight.requires_grad
         srcs: List[TTensor] = self.srcs
-        mask = self.mask if self.relu else None
-        coef = self._finalize_bwd(lib, st, g, mask, m, kp, bn.weight.requires_grad, bn.bias.requires_grad)
-        if not (w_need or any(t.requires_grad for t in srcs)):
-            out.grad = None
-            return
-        dy = torch.empty_like(self.y)
-        _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift), ptr(coef),
-                                      int(self.relu), ptr(dy), None, 0, m, kp, st), 'tok_bn_bwd_apply')
+        dy = self._bn_bwd(lib, st, g, m, kp, w_need or any(t.requires_grad for t in srcs))
         out.grad = None
+        if dy is None:
+            return
         ctot = sum(t.cp for t in srcs)
         wd = self.pk.dgrad.view(ctot, kp) if self.pk.dgrad is not None else None
         # d(y_j) = up_j^T d(y): the transposes of the interpolations over ALL kp channels of d(y) — one pass for the three
@@ -101,7 +96,7 @@ def commuted_ok(srcs: List[TTensor], size: Tuple[int, int], conv: nn.Module, bn:
     if conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or conv.bias is not None \
             or conv.groups != 1 or conv.dilation != (1, 1):
         return False
-    if not (bn.training or bn.running_mean is None) or bn.momentum is None:
+    if not EF.batch_stats(bn) or bn.momentum is None:
         return False
     x0 = srcs[0]
     if x0.data.dim() != 4 or (x0.shape[1], x0.shape[2]) != (int(size[0]), int(size[1])):
@@ -149,23 +144,15 @@ def upsample_concat_conv_bn_relu(region: Region, srcs: List[TTensor], size: Tupl
         low += [ptr(ys[j]), descs[j].h, descs[j].w] if j < len(ys) else [None, 1, 1]
     y = ys[0]
     _C.check(lib.tok_bilinear_sum_stats(ptr(y), *low, n, h, w, kp, ptr(y), ptr(stats), st), 'tok_bilinear_sum_stats')
-    vec = torch.empty((4, kp), dtype=F32, device=dev)
-    scale, shift, mean, rstd = vec[0], vec[1], vec[2], vec[3]
-    track = bn.training and bn.track_running_stats and bn.running_mean is not None
-    _C.check(lib.tok_bn_finalize(ptr(stats), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(bn.bias),
-                                 ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                                 ptr(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps),
-                                 ptr(mean), ptr(rstd), ptr(scale), ptr(shift), st), 'tok_bn_finalize')
-    out_data = torch.empty_like(y)
-    mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=dev) if (relu and training) else None
-    _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), None, int(relu), ptr(out_data), ptr(mask), m, kp, st),
-             'tok_bn_act_fwd')
+    act = EF._check_act(relu, None, bn)
+    scale, shift, mean, rstd = EF.bn_coeffs(lib, st, bn, stats, rows, m, kp, dev)
+    out_data, mask = EF.bn_apply(lib, st, y, scale, shift, act, None, relu and training, m, kp)
     out = TTensor(out_data, kp, requires_grad=bool(training))
     if training:
         node = _CommutedNeckNode()
         node.x, node.out, node.shortcut, node.y = None, out, None, y
         node.conv, node.bn, node.desc, node.pk = conv, bn, descs[0], pk
-        node.relu, node.batch_stats, node.mask = relu, True, mask
+        node.act, node.batch_stats, node.mask = act, True, mask
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
         node.srcs, node.descs, node.offs = list(srcs), descs, offs
         node.sub_capable = False

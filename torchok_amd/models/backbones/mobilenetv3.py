@@ -6,14 +6,14 @@ Mirrors the reference wiring ``torchok/models/backbones/mobilenetv3.py``: ``Mobi
 ``SqueezeExcite(gate_layer='hard_sigmoid', force_act_layer=nn.ReLU, rd_round_fn=round_channels)`` semantics restated here.
 Module / parameter names are those of timm, so reference checkpoints load.
 
-Each ``conv -> bn -> act`` group is one engine unit, as in ``efficientnet.py``; a block marked ``nre`` runs them with ReLU,
-every other block with the model's activation, hard-swish (``act='hard_swish'``: the mask-less path of csrc/act.hip).  The
-squeeze-excite keeps its ReLU inside and gates with a hard sigmoid.  The decoder and the builder live here, beside those of
-``efficientnet.py``, so that what the MnasNet entry points accept and refuse does not move; ``make_divisible``,
-``round_channels`` and ``_init_weight_goog`` are shared.  Not built: ``mobilenetv3_rw``, the ``tf_*`` variants (asymmetric
+The blocks, the block-string decoder and the builder are those of ``_efficientnet_blocks.py``, shared with
+``efficientnet.py``; this family passes what differs: the 'cn' block type and the 'nre' option (a block marked ``nre`` runs its
+units with ReLU, every other block with the model's activation, hard-swish: ``act='hard_swish'``, the mask-less path of
+csrc/act.hip), the squeeze-excite that keeps its ReLU inside, gates with a hard sigmoid and rounds its width with
+``round_channels``, ``se_from_exp=True`` and the stem feature.  Not built: ``mobilenetv3_rw``, the ``tf_*`` variants (asymmetric
 "same" padding), the ``minimal`` variants, ``fbnetv3_*`` and ``lcnet_*``.
 """
-import re
+from functools import partial
 from typing import List
 
 import torch
@@ -23,164 +23,20 @@ from ... import engine
 from ...constructor import BACKBONES
 from ...engine import functional as EF
 from ..base import BaseBackbone
-from .efficientnet import _init_weight_goog, make_divisible, round_channels
+from . import _efficientnet_blocks as B
+from ._efficientnet_blocks import init_weight_goog, round_channels
 
 
 def _unsupported(what: str):
     raise NotImplementedError(f'torchok_amd MobileNetV3: {what} not built')
 
 
-def _decode_block_str(block_str: str):
-    """[timm] _decode_block_str for the 'ds' / 'ir' / 'cn' block types with the options r k s e c se nre noskip."""
-    ops = block_str.split('_')
-    block_type, ops = ops[0], ops[1:]
-    if block_type not in ('ds', 'ir', 'cn'):
-        _unsupported(f'block type {block_type!r}')
-    opts, noskip, relu = {}, False, False
-    for op in ops:
-        if op == 'noskip':
-            noskip = True
-            continue
-        if op == 'nre':
-            relu = True
-            continue
-        m = re.match(r'^(se|[a-z])(.*)$', op)
-        key, value = m.group(1), m.group(2)
-        if key not in ('r', 'k', 's', 'e', 'c', 'se'):
-            _unsupported(f'block option {op!r}')
-        opts[key] = value
-    args = dict(block_type=block_type, kernel_size=int(opts['k']), out_chs=int(opts['c']), stride=int(opts['s']), relu=relu)
-    if block_type != 'cn':
-        args.update(se_ratio=float(opts['se']) if 'se' in opts else 0., noskip=noskip)
-    if block_type == 'ir':
-        args['exp_ratio'] = float(opts.get('e', 1.0))
-    return args, int(opts.get('r', 1))
-
-
-def decode_arch_def(arch_def) -> List[List[dict]]:
-    stages = []
-    for stack in arch_def:
-        blocks = []
-        for block_str in stack:
-            args, repeats = _decode_block_str(block_str)
-            blocks.extend(dict(args) for _ in range(repeats))
-        stages.append(blocks)
-    return stages
-
-
-class SqueezeExcite(nn.Module):
-    """[timm] efficientnet_blocks.SqueezeExcite with ReLU inside, the hard-sigmoid gate and the reduced width rounded by
-    round_channels (a multiple of 8); the two 1x1 convs are parameter containers."""
-
-    def __init__(self, in_chs, rd_ratio=0.25):
-        super().__init__()
-        rd_channels = round_channels(in_chs * rd_ratio)
-        self.conv_reduce = nn.Conv2d(in_chs, rd_channels, 1, bias=True)
-        self.conv_expand = nn.Conv2d(rd_channels, in_chs, 1, bias=True)
-
-    def run(self, r, x):
-        return EF.squeeze_excite(r, x, self, gate='hard_sigmoid')
-
-
-def _act(relu: bool):
-    """(relu, act) of a unit that activates: ReLU for an 'nre' block, the model's hard-swish otherwise."""
-    return dict(relu=True) if relu else dict(relu=False, act=EF.HARD_SWISH)
-
-
-class DepthwiseSeparableConv(nn.Module):
-    """[timm] 'ds' block: dw conv -> bn + act -> [se] -> 1x1 conv -> bn (-> + x)."""
-
-    def __init__(self, in_chs, out_chs, dw_kernel_size=3, stride=1, noskip=False, se_ratio=0., relu=False):
-        super().__init__()
-        self.has_skip = (stride == 1 and in_chs == out_chs) and not noskip
-        self.relu = relu
-        self.conv_dw = nn.Conv2d(in_chs, in_chs, dw_kernel_size, stride=stride, padding=dw_kernel_size // 2, groups=in_chs,
-                                 bias=False)
-        self.bn1 = nn.BatchNorm2d(in_chs)
-        self.se = SqueezeExcite(in_chs, rd_ratio=se_ratio) if se_ratio else nn.Identity()
-        self.conv_pw = nn.Conv2d(in_chs, out_chs, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(out_chs)
-
-    def forward(self, x):
-        r = engine.current_region()
-        y = EF.dwconv_bn_act(r, x, self.conv_dw, self.bn1, **_act(self.relu))
-        if isinstance(self.se, SqueezeExcite):
-            y = self.se.run(r, y)
-        return EF.conv_bn_act(r, y, self.conv_pw, self.bn2, relu=False, shortcut=x if self.has_skip else None)
-
-
-class InvertedResidual(nn.Module):
-    """[timm] 'ir' block: 1x1 conv -> bn + act -> dw conv -> bn + act -> [se] -> 1x1 conv -> bn (-> + x).  The
-    squeeze-excite ratio refers to the expanded width (se_from_exp=True)."""
-
-    def __init__(self, in_chs, out_chs, dw_kernel_size=3, stride=1, noskip=False, exp_ratio=1.0, se_ratio=0., relu=False):
-        super().__init__()
-        mid_chs = make_divisible(in_chs * exp_ratio)
-        self.has_skip = (in_chs == out_chs and stride == 1) and not noskip
-        self.relu = relu
-        self.conv_pw = nn.Conv2d(in_chs, mid_chs, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(mid_chs)
-        self.conv_dw = nn.Conv2d(mid_chs, mid_chs, dw_kernel_size, stride=stride, padding=dw_kernel_size // 2,
-                                 groups=mid_chs, bias=False)
-        self.bn2 = nn.BatchNorm2d(mid_chs)
-        self.se = SqueezeExcite(mid_chs, rd_ratio=se_ratio) if se_ratio else nn.Identity()
-        self.conv_pwl = nn.Conv2d(mid_chs, out_chs, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(out_chs)
-
-    def forward(self, x):
-        r = engine.current_region()
-        y = EF.conv_bn_act(r, x, self.conv_pw, self.bn1, **_act(self.relu))
-        y = EF.dwconv_bn_act(r, y, self.conv_dw, self.bn2, **_act(self.relu))
-        if isinstance(self.se, SqueezeExcite):
-            y = self.se.run(r, y)
-        return EF.conv_bn_act(r, y, self.conv_pwl, self.bn3, relu=False, shortcut=x if self.has_skip else None)
-
-
-class ConvBnAct(nn.Module):
-    """[timm] 'cn' block: conv -> bn + act (no skip: the block strings of this family never ask for one)."""
-
-    def __init__(self, in_chs, out_chs, kernel_size=1, stride=1, relu=False):
-        super().__init__()
-        self.has_skip = False
-        self.relu = relu
-        self.conv = nn.Conv2d(in_chs, out_chs, kernel_size, stride=stride, padding=kernel_size // 2, bias=False)
-        self.bn1 = nn.BatchNorm2d(out_chs)
-
-    def forward(self, x):
-        return EF.conv_bn_act(engine.current_region(), x, self.conv, self.bn1, **_act(self.relu))
-
-
-def _build_blocks(in_chs, block_args, round_chs_fn):
-    """[timm] EfficientNetBuilder.__call__ (output stride 32, no drop path, se_from_exp=True): stages of blocks and their
-    feature_info — the stem when the first block is strided, then the last block of every stage that is followed by a strided
-    stage, and of the last stage."""
-    stages, features = [], []
-    current_stride = 2
-    if block_args[0][0]['stride'] > 1:
-        features.append(dict(stage=0, reduction=current_stride, num_chs=in_chs, module='act1'))
-    for stack_idx, stack in enumerate(block_args):
-        blocks = []
-        for block_idx, ba in enumerate(stack):
-            stride = ba['stride'] if block_idx == 0 else 1
-            current_stride *= stride
-            out_chs = round_chs_fn(ba['out_chs'])
-            bt = ba['block_type']
-            if bt == 'ds':
-                blocks.append(DepthwiseSeparableConv(in_chs, out_chs, ba['kernel_size'], stride, ba['noskip'], ba['se_ratio'],
-                                                     ba['relu']))
-            elif bt == 'ir':
-                blocks.append(InvertedResidual(in_chs, out_chs, ba['kernel_size'], stride, ba['noskip'], ba['exp_ratio'],
-                                               ba['se_ratio'], ba['relu']))
-            else:
-                blocks.append(ConvBnAct(in_chs, out_chs, ba['kernel_size'], stride, ba['relu']))
-            in_chs = out_chs
-            if block_idx + 1 == len(stack):
-                nxt = stack_idx + 1
-                if nxt >= len(block_args) or block_args[nxt][0]['stride'] > 1:
-                    features.append(dict(stage=stack_idx + 1, reduction=current_stride, num_chs=out_chs,
-                                         module=f'blocks.{stack_idx}.{block_idx}'))
-        stages.append(nn.Sequential(*blocks))
-    return stages, features, in_chs
+# the family's arguments to the shared blocks: hard-swish where a block is not marked 'nre', the hard-sigmoid squeeze-excite
+# with the reduced width rounded by round_channels (a multiple of 8)
+SqueezeExcite = partial(B.SqueezeExcite, rd_round_fn=round_channels, gate='hard_sigmoid')
+DepthwiseSeparableConv = partial(B.DepthwiseSeparableConv, act=EF.HARD_SWISH, se_layer=SqueezeExcite)
+InvertedResidual = partial(B.InvertedResidual, act=EF.HARD_SWISH, se_layer=SqueezeExcite)
+ConvBnAct = partial(B.ConvBnAct, act=EF.HARD_SWISH)
 
 
 class MobileNetV3(BaseBackbone):
@@ -209,7 +65,8 @@ class MobileNetV3(BaseBackbone):
             stem_size = round_chs_fn(stem_size)
         conv_stem = nn.Conv2d(in_channels, stem_size, 3, stride=2, padding=1, bias=False)
         bn1 = nn.BatchNorm2d(stem_size)
-        stages, feature_info, out_chs = _build_blocks(stem_size, block_args, round_chs_fn)
+        stages, feature_info, out_chs = B.build_blocks(stem_size, block_args, round_chs_fn, se_from_exp=True, stem_feature=True,
+                                                       act=EF.HARD_SWISH, se_layer=SqueezeExcite)
         super().__init__(in_channels=in_channels, out_channels=out_chs)
         self.num_features = num_features
         self.conv_stem, self.bn1 = conv_stem, bn1
@@ -222,7 +79,7 @@ class MobileNetV3(BaseBackbone):
 
     def init_weights(self):
         for m in self.modules():
-            _init_weight_goog(m)
+            init_weight_goog(m)
 
     def _run(self, r, x: torch.Tensor, all_features: bool):
         t = r.input(x, c_pad_to=4 if x.shape[1] <= 4 else 8)
@@ -270,7 +127,8 @@ def _gen_mobilenet_v3(variant, channel_multiplier=1.0, pretrained=False, **kwarg
 
     def round_chs_fn(c):
         return round_channels(c, multiplier=channel_multiplier)
-    return MobileNetV3(block_args=decode_arch_def(_SMALL if small else _LARGE), num_features=1024 if small else 1280,
+    return MobileNetV3(block_args=B.decode_arch_def(_SMALL if small else _LARGE, _unsupported, ('ds', 'ir', 'cn'), nre=True),
+                       num_features=1024 if small else 1280,
                        stem_size=16, fix_stem=channel_multiplier < 0.75, round_chs_fn=round_chs_fn, **kwargs)
 
 
