@@ -237,8 +237,8 @@ def _ls_ref(x, a, gamma, scale, rps, dout):
 
 
 # (rows, d, rows per sample): one row; 5 tokens x 3 images; the real layer at B = 2; more rows than the 512-block cap covers in
-# one trip at d = 8 (256 rows per block)
-LS_SHAPES = [(1, 8, 1), (15, 128, 5), (394, 768, 197), (512 * 256 + 37 * 3 - 512 * 256 % 3, 8, 3)]
+# one trip at d = 8 (256 rows per block); d > 2048: two channel-group passes per lane, the second one ragged
+LS_SHAPES = [(1, 8, 1), (15, 128, 5), (394, 768, 197), (512 * 256 + 37 * 3 - 512 * 256 % 3, 8, 3), (36, 2176, 12)]
 
 
 @pytest.mark.parametrize('rows,d,rps', LS_SHAPES, ids=lambda v: str(v))

@@ -621,7 +621,8 @@ def test_conv_refusals():
 
 
 # ---- tok_relu_mask_reduce: the stand-alone form of the masked store (csrc/unit3.hip) ---------------------------------------------
-@pytest.mark.parametrize('m,c', [(1, 8), (777, 48), (4096 + 17, 256), (50176, 64), (300, 2048)])
+# (300, 2176): two channel-group passes per lane, the second one ragged (16 of 256 lanes live)
+@pytest.mark.parametrize('m,c', [(1, 8), (777, 48), (4096 + 17, 256), (50176, 64), (300, 2048), (300, 2176)])
 @pytest.mark.parametrize('mode', ['mask', 'in_place', 'no_mask'])
 def test_relu_mask_reduce_contract(m, c, mode):
     """dz = mask ? dout : 0 exactly (bf16 in, bf16 out); partial[2][tok_bn_bwd_rows(m, c)][c]: the first half folds to the column

@@ -1,4 +1,4 @@
-"""Kernel contracts of the mask-less activation path (csrc/act.hip: BatchNorm + hard-swish forward, backward reduce and
+"""Kernel contracts of the mask-less activation path (csrc/bn.hip: BatchNorm + hard-swish forward, backward reduce and
 backward apply) and of the gated squeeze-excite entry points (csrc/se.hip), against fp64 torch on the same bf16 inputs.
 Every operand sits between guard regions (helpers.gin / gout): a read or write outside it fails the case."""
 import pytest

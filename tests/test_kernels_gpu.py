@@ -924,7 +924,8 @@ def test_bilinear(libs, n, hs, ws, c, hd, wd, ld, off):
 @pytest.mark.parametrize('n,h,w,c,lows', [(2, 16, 16, 16, [(8, 8), (4, 4), (2, 2)]), (1, 32, 64, 720, [(16, 32), (8, 16), (4, 8)]),
                                          (2, 13, 20, 24, [(5, 7)]), (1, 8, 8, 2056, [(4, 4), (2, 2)]), (3, 8, 8, 8, []),
                                          (2, 48, 32, 40, [(6, 4), (24, 16)]), (1, 32, 32, 24, [(8, 8)]), (1, 16, 32, 8, []),
-                                         (1, 32, 32, 16, [(16, 16), (16, 16)]), (1, 32, 32, 16, [(11, 11)])])
+                                         (1, 32, 32, 16, [(16, 16), (16, 16)]), (1, 32, 32, 16, [(11, 11)]),
+                                         (1, 8, 8, 2176, [(4, 4)])])
 def test_bilinear_sum_stats(libs, n, h, w, c, lows):
     """y = y0 + sum_j up(t_j), in place, + the BatchNorm partial rows of the rounded sum (the commuted HRNet neck)."""
     lib, fake = libs

@@ -1,24 +1,20 @@
-// BatchNorm (training, batch statistics) + ReLU + residual add, NHWC bf16, fp32 statistics.
-// All passes are HBM-bound streaming kernels: 16-byte (8 x bf16) accesses per lane, a thread
-// keeps ONE 8-channel group for its whole life so scale/shift/coefficients live in registers.
+// BatchNorm (training, batch statistics) + ReLU / hard-swish + residual add, NHWC bf16, fp32 statistics.
+// All passes are HBM-bound streaming kernels on the row skeleton of row_stream.h: 16-byte (8 x bf16) accesses per lane, a
+// thread keeps ONE 8-channel group for a whole pass so scale/shift/coefficients live in registers.
 //
-// Forward :  conv epilogue partial sums -> tok_bn_finalize -> tok_bn_act_fwd
-// Backward:  tok_bn_bwd_reduce (partials) -> tok_bn_bwd_finalize -> tok_bn_bwd_apply
-//            dz = dout * mask ;  dy = a1*dz + a2*y + a3   (a* per channel)
-#include "tok_common.h"
+// Forward :  conv epilogue partial sums -> tok_bn_finalize -> tok_bn_act_fwd | tok_bn_hswish_fwd
+// Backward:  tok_bn_bwd_reduce (partials) -> tok_bn_bwd_finalize -> tok_bn_bwd_apply      (tok_bn_hswish_bwd_*: the same two
+//            kernels with the hard-swish derivative)
+//            dz = dout * act'(z) ;  dy = a1*dz + a2*y + a3   (a* per channel)
+// The reducing kernels leave partial[2][gridDim.x][C]; fixed summation order, no atomics: two runs give the same bits.
+// Under -ffp-contract=fast hipcc fuses a product into a following add or not depending on the surrounding code, so every
+// product that feeds an add in a row body is written as the fmaf the compiler has always made of it.
+#include "row_stream.h"
 #include <hip/hip_ext.h>
-#include <stdlib.h>
 
 static thread_local hipEvent_t t_done_event = nullptr;
 
 namespace {
-
-inline int stream_blocks(int64_t m, const Geo& g, int cap) {
-  int64_t b = (m + g.rpb - 1) / g.rpb;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* __restrict__ y,
@@ -28,24 +24,14 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* __restrict_
                                                          bf16* __restrict__ out, uint8_t* __restrict__ mask,
                                                          int64_t M, int C, int cge, int rpb,
                                                          float* __restrict__ csum /* may be null: [gridDim.x][C] */) {
-  __shared__ float cred[256][8];
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
-  if (rl >= rpb && csum == nullptr) return;
   const int cg_total = C >> 3;
-  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
-  for (int cg = cgl; cg < cg_end; cg += cge) {
-    const bool live = cg < cg_total;
-    float sc[8], sh[8], cs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sc[e] = 0.f; sh[e] = 0.f; cs[e] = 0.f; }
-    if (live) {
-      load8f(scale + cg * 8, sc);
-      load8f(shift + cg * 8, sh);
-    }
-    if (rl < rpb && live)
-    for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
-      const size_t off = (size_t)m * C + cg * 8;
+  // csum: column sums of the STORED values over this block's rows, one row of partials per block (the fused residual unit
+  // wants colsum(z) of its input; producing it here saves the stand-alone pass over z)
+  rows_reduce<1>(grid_rows(M, rpb), C, C, cge, rpb, csum, blockIdx.x, gridDim.x, [&](int cg) TOK_ROW_INLINE {
+    float sc[8], sh[8];
+    load8f(scale + cg * 8, sc);
+    load8f(shift + cg * 8, sh);
+    return [=](int64_t m, size_t off, float (&cs)[1][8]) TOK_ROW_INLINE {
       const bf16x8 v = ldg16(y + off);
       bf16x8 o;
       if (shortcut != nullptr) {
@@ -67,7 +53,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* __restrict_
       stg16(out + off, o);
       if (csum != nullptr) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) cs[e] += bf2f(o[e]);
+        for (int e = 0; e < 8; ++e) cs[0][e] += bf2f(o[e]);
       }
       if (mask != nullptr) {   // bit e = (out[e] > 0): the ReLU mask the backward kernels read (1/16 of `out`)
         unsigned bits = 0;
@@ -75,60 +61,20 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* __restrict_
         for (int e = 0; e < 8; ++e) bits |= (bf2f(o[e]) > 0.f ? 1u : 0u) << e;
         mask[(size_t)m * cg_total + cg] = (uint8_t)bits;
       }
-    }
-    if (csum != nullptr) {
-      // column sums of the STORED values over this block's rows: one row of partials per block (the fused residual unit
-      // wants colsum(z) of its input; producing it here saves the stand-alone pass over z)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) cred[tid][e] = cs[e];
-      __syncthreads();
-      if (rl == 0 && live) {
-        for (int r = 1; r < rpb; ++r)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) cs[e] += cred[r * cge + cgl][e];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) csum[(size_t)blockIdx.x * C + cg * 8 + e] = cs[e];
-      }
-      __syncthreads();
-    }
-  }
+    };
+  });
 }
 
 // generic per-channel (sum, sumsq) partials of an NHWC tensor: partial[2][gridDim.x][C]
 __global__ __launch_bounds__(256) void bn_stats_kernel(const bf16* __restrict__ y, int64_t M, int C,
                                                        int cge, int rpb, float* __restrict__ partial) {
-  __shared__ float red[2][256][8];
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
-  const int cg_total = C >> 3;
-  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
-  for (int cg = cgl; cg < cg_end; cg += cge) {
-    const bool live = cg < cg_total;
-    float s1[8], s2[8];
+  rows_reduce<2>(grid_rows(M, rpb), C, C, cge, rpb, partial, blockIdx.x, gridDim.x, [&](int) TOK_ROW_INLINE {
+    return [=](int64_t, size_t off, float (&s)[2][8]) TOK_ROW_INLINE {
+      const bf16x8 v = ldg16(y + off);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb && live) {
-      for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
-        const bf16x8 v = ldg16(y + (size_t)m * C + cg * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float f = bf2f(v[e]); s1[e] += f; s2[e] += f * f; }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
-    __syncthreads();
-    if (rl == 0 && live) {
-      for (int r = 1; r < rpb; ++r)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        partial[((size_t)0 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s1[e];
-        partial[((size_t)1 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s2[e];
-      }
-    }
-    __syncthreads();
-  }
+      for (int e = 0; e < 8; ++e) { const float f = bf2f(v[e]); s[0][e] += f; s[1][e] = fmaf(f, f, s[1][e]); }
+    };
+  });
 }
 
 // Per-lane fold of partial rows rl, rl+64, ... for both sums: 8 loads in flight (the serial version was bound by the
@@ -265,68 +211,75 @@ __global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, con
   }
 }
 
-// partial[2][gridDim.x][C] = (sum dz, sum dz * xhat)
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
-    const bf16* __restrict__ dout, const bf16* __restrict__ y, const uint8_t* __restrict__ mask,
-    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
-    const float* __restrict__ rstd, int relu, int64_t M, int C, int cge, int rpb,
-    float* __restrict__ partial) {
-  __shared__ float red[2][256][8];
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
-  const int cg_total = C >> 3;
-  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
-  for (int cg = cgl; cg < cg_end; cg += cge) {
-    const bool live = cg < cg_total;
-    float s1[8], s2[8];
+// The activation-derivative rule of the backward passes, written once: dz = dout * act'(z), z = fmaf(y, scale, shift), for
+// the lane's 8 channels, and its running sum s1 += dz (the apply pass drops the sum).
+// ReLU (relu == 0: no activation) by the forward's mask bit where there is one, else recomputed from z > 0.
+struct ReluD {
+  int relu;
+  const uint8_t* mask;
+  __device__ __forceinline__ void operator()(int64_t m, int cg, int cg_total, const bf16x8& g, const bf16x8& v,
+                                             const float (&sc)[8], const float (&sh)[8], float (&dz)[8],
+                                             float (&s1)[8]) const {
+    if (relu && mask != nullptr) {
+      const unsigned bits = mask[(size_t)m * cg_total + cg];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb && live) {
-      float sc[8], sh[8], mu[8], rs[8];
-      load8f(scale + cg * 8, sc);
-      load8f(shift + cg * 8, sh);
-      load8f(mean + cg * 8, mu);
-      load8f(rstd + cg * 8, rs);
-      for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
-        const size_t off = (size_t)m * C + cg * 8;
-        const bf16x8 g = ldg16(dout + off);
-        const bf16x8 v = ldg16(y + off);
-        if (relu && mask != nullptr) {
-          const unsigned bits = mask[(size_t)m * cg_total + cg];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float yf = bf2f(v[e]);
-            const float dz = ((bits >> e) & 1u) ? bf2f(g[e]) : 0.f;
-            s1[e] += dz;
-            s2[e] = fmaf(dz, (yf - mu[e]) * rs[e], s2[e]);
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float yf = bf2f(v[e]);
-            float dz = bf2f(g[e]);
-            if (relu && !(fmaf(yf, sc[e], sh[e]) > 0.f)) dz = 0.f;
-            s1[e] += dz;
-            s2[e] = fmaf(dz, (yf - mu[e]) * rs[e], s2[e]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
-    __syncthreads();
-    if (rl == 0 && live) {
-      for (int r = 1; r < rpb; ++r)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
+      for (int e = 0; e < 8; ++e) dz[e] = ((bits >> e) & 1u) ? bf2f(g[e]) : 0.f;
+    } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        partial[((size_t)0 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s1[e];
-        partial[((size_t)1 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s2[e];
+        dz[e] = bf2f(g[e]);
+        if (relu && !(fmaf(bf2f(v[e]), sc[e], sh[e]) > 0.f)) dz[e] = 0.f;
       }
     }
-    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s1[e] += dz[e];
   }
+};
+// Hard-swish (MobileNetV3), the mask-less path: nothing is kept between the passes but y; forward, reduce and apply each
+// recompute z from the stored bf16 y, so all three see the same z and the same branch of the derivative.
+//   hswish(z) = z * min(max(z + 3, 0), 6) / 6      hswish'(z) = 0 (z < -3), z/3 + 0.5 (-3 <= z <= 3), 1 (z > 3)
+__device__ __forceinline__ float hswish_f(float z) {
+  return z * __builtin_amdgcn_fmed3f(z + 3.f, 0.f, 6.f) * (1.f / 6.f);
+}
+// what torch.nn.functional.hardswish differentiates to (the kinks belong to the middle branch)
+__device__ __forceinline__ float hswish_d(float z) {
+  const float mid = fmaf(z, 1.f / 3.f, 0.5f);
+  return z < -3.f ? 0.f : (z <= 3.f ? mid : 1.f);
+}
+struct HswishD {
+  __device__ __forceinline__ void operator()(int64_t, int, int, const bf16x8& g, const bf16x8& v, const float (&sc)[8],
+                                             const float (&sh)[8], float (&dz)[8], float (&s1)[8]) const {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float gf = bf2f(g[e]), d = hswish_d(fmaf(bf2f(v[e]), sc[e], sh[e]));
+      dz[e] = gf * d;
+      s1[e] = fmaf(gf, d, s1[e]);     // the product fused into the sum, dz rounded on its own
+    }
+  }
+};
+
+// partial[2][gridDim.x][C] = (sum dz, sum dz * xhat)
+template <class ActD>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
+    const bf16* __restrict__ dout, const bf16* __restrict__ y, ActD act, const float* __restrict__ scale,
+    const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ rstd, int64_t M, int C,
+    int cge, int rpb, float* __restrict__ partial) {
+  const int cg_total = C >> 3;
+  rows_reduce<2>(grid_rows(M, rpb), C, C, cge, rpb, partial, blockIdx.x, gridDim.x, [&](int cg) TOK_ROW_INLINE {
+    float sc[8], sh[8], mu[8], rs[8];
+    load8f(scale + cg * 8, sc);
+    load8f(shift + cg * 8, sh);
+    load8f(mean + cg * 8, mu);
+    load8f(rstd + cg * 8, rs);
+    return [=](int64_t m, size_t off, float (&s)[2][8]) TOK_ROW_INLINE {
+      const bf16x8 g = ldg16(dout + off);
+      const bf16x8 v = ldg16(y + off);
+      float dz[8];
+      act(m, cg, cg_total, g, v, sc, sh, dz, s[0]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[1][e] = fmaf(dz[e], (bf2f(v[e]) - mu[e]) * rs[e], s[1][e]);
+    };
+  });
 }
 
 template <int CW>
@@ -375,37 +328,24 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
 }
 
 // dout / dshortcut may alias (in-place masking of the incoming gradient): no restrict on them.
+template <class ActD>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
-    const bf16* dout, const bf16* __restrict__ y, const uint8_t* __restrict__ mask,
-    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ coef,
-    int relu, bf16* __restrict__ dy, bf16* dshortcut, int ds_acc, int64_t M, int C, int cge, int rpb) {
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
-  if (rl >= rpb) return;
+    const bf16* dout, const bf16* __restrict__ y, ActD act, const float* __restrict__ scale,
+    const float* __restrict__ shift, const float* __restrict__ coef, bf16* __restrict__ dy, bf16* dshortcut, int ds_acc,
+    int64_t M, int C, int cge, int rpb) {
   const int cg_total = C >> 3;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
+  rows_map(grid_rows(M, rpb), C, C, cge, rpb, [&](int cg) TOK_ROW_INLINE {
     float sc[8], sh[8], c1[8], c2[8], c3[8];
     load8f(scale + cg * 8, sc);
     load8f(shift + cg * 8, sh);
     load8f(coef + cg * 8, c1);
     load8f(coef + C + cg * 8, c2);
     load8f(coef + 2 * C + cg * 8, c3);
-    for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
-      const size_t off = (size_t)m * C + cg * 8;
+    return [=](int64_t m, size_t off) TOK_ROW_INLINE {
       const bf16x8 g = ldg16(dout + off);
       const bf16x8 v = ldg16(y + off);
-      float dz[8];
-      if (relu && mask != nullptr) {
-        const unsigned bits = mask[(size_t)m * cg_total + cg];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dz[e] = ((bits >> e) & 1u) ? bf2f(g[e]) : 0.f;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          dz[e] = bf2f(g[e]);
-          if (relu && !(fmaf(bf2f(v[e]), sc[e], sh[e]) > 0.f)) dz[e] = 0.f;
-        }
-      }
+      float dz[8], unused[8] = {};
+      act(m, cg, cg_total, g, v, sc, sh, dz, unused);
       bf16x8 o;
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = f2bf(fmaf(c1[e], dz[e], fmaf(c2[e], bf2f(v[e]), c3[e])));
@@ -422,8 +362,26 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
         }
         stg16(dshortcut + off, d);
       }
-    }
-  }
+    };
+  });
+}
+
+// out = hswish(y*scale + shift)
+__global__ __launch_bounds__(256) void bn_hswish_fwd_kernel(const bf16* __restrict__ y, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, bf16* __restrict__ out,
+                                                            int64_t M, int C, int cge, int rpb) {
+  rows_map(grid_rows(M, rpb), C, C, cge, rpb, [&](int cg) TOK_ROW_INLINE {
+    float sc[8], sh[8];
+    load8f(scale + cg * 8, sc);
+    load8f(shift + cg * 8, sh);
+    return [=](int64_t, size_t off) TOK_ROW_INLINE {
+      const bf16x8 v = ldg16(y + off);
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = f2bf(hswish_f(fmaf(bf2f(v[e]), sc[e], sh[e])));
+      stg16(out + off, o);
+    };
+  });
 }
 
 
@@ -534,83 +492,79 @@ __device__ __forceinline__ void pooled_dz(const bf16* __restrict__ dpool, const 
   }
 }
 
-// REDUCE: partial[2][gridDim.x][C] = (sum dz, sum dz * xhat), geometry and order of bn_bwd_reduce_kernel
-// else:   dy = c1 * dz + c2 * y + c3, geometry of bn_bwd_apply_kernel
-template <bool REDUCE>
-__global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const bf16* __restrict__ dpool,
-                                                          const uint8_t* __restrict__ argmax, const bf16* __restrict__ y,
-                                                          const float* __restrict__ scale, const float* __restrict__ shift,
-                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          const float* __restrict__ coef, int64_t M, int H, int W, int C,
-                                                          int P, int Q, int cge, int rpb, float* __restrict__ partial,
-                                                          bf16* __restrict__ dy) {
-  __shared__ float red[REDUCE ? 2 : 1][REDUCE ? 256 : 1][8];
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
-  const int cg_total = C >> 3;
-  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
-  for (int cg = cgl; cg < cg_end; cg += cge) {
-    const bool live = cg < cg_total;
-    float s1[8], s2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb && live) {
-      float sc[8], sh[8], a[8], b[8], c3[8];
-      load8f(scale + cg * 8, sc);
-      load8f(shift + cg * 8, sh);
-      if (REDUCE) {
-        load8f(mean + cg * 8, a);
-        load8f(rstd + cg * 8, b);
-      } else {
-        load8f(coef + cg * 8, a);
-        load8f(coef + C + cg * 8, b);
-        load8f(coef + 2 * C + cg * 8, c3);
-      }
-      // (n, h, w) of row m advance with the row stride: no division inside the loop
-      const int64_t m0 = (int64_t)blockIdx.x * rpb + rl, step = (int64_t)gridDim.x * rpb;
-      int w = (int)(m0 % W), h = (int)((m0 / W) % H), n = (int)(m0 / ((int64_t)W * H));
-      const int dw = (int)(step % W), dh = (int)((step / W) % H), dn = (int)(step / ((int64_t)W * H));
-      for (int64_t m = m0; m < M; m += step) {
-        const size_t off = (size_t)m * C + cg * 8;
-        const bf16x8 v = ldg16(y + off);
-        float dz[8];
-        pooled_dz(dpool, argmax, v, sc, sh, n, h, w, C, P, Q, cg, dz);
-        w += dw;
-        if (w >= W) { w -= W; ++h; }
-        h += dh;
-        if (h >= H) { h -= H; ++n; }
-        n += dn;
-        if (REDUCE) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            s1[e] += dz[e];
-            s2[e] = fmaf(dz[e], (bf2f(v[e]) - a[e]) * b[e], s2[e]);
-          }
-        } else {
-          bf16x8 o;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(fmaf(a[e], dz[e], fmaf(b[e], bf2f(v[e]), c3[e])));
-          stg16(dy + off, o);
-        }
-      }
-    }
-    if (REDUCE) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
-      __syncthreads();
-      if (rl == 0 && live) {
-        for (int r = 1; r < rpb; ++r)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          partial[((size_t)0 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s1[e];
-          partial[((size_t)1 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s2[e];
-        }
-      }
-      __syncthreads();
-    }
+// (n, h, w) of the lane's current row, advanced with the row stride: no division inside the row loop
+struct PixelWalk {
+  int n, h, w, dn, dh, dw, H, W;
+  __device__ __forceinline__ PixelWalk(int64_t m0, int64_t step, int H_, int W_) : H(H_), W(W_) {
+    w = (int)(m0 % W); h = (int)((m0 / W) % H); n = (int)(m0 / ((int64_t)W * H));
+    dw = (int)(step % W); dh = (int)((step / W) % H); dn = (int)(step / ((int64_t)W * H));
   }
+  __device__ __forceinline__ void next() {
+    w += dw;
+    if (w >= W) { w -= W; ++h; }
+    h += dh;
+    if (h >= H) { h -= H; ++n; }
+    n += dn;
+  }
+};
+
+// partial[2][gridDim.x][C] = (sum dz, sum dz * xhat), geometry and order of bn_bwd_reduce_kernel
+__global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const bf16* __restrict__ dpool,
+                                                                 const uint8_t* __restrict__ argmax,
+                                                                 const bf16* __restrict__ y, const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift,
+                                                                 const float* __restrict__ mean,
+                                                                 const float* __restrict__ rstd, int64_t M, int H, int W, int C,
+                                                                 int P, int Q, int cge, int rpb, float* __restrict__ partial) {
+  const RowSpan rows = grid_rows(M, rpb);
+  rows_reduce<2>(rows, C, C, cge, rpb, partial, blockIdx.x, gridDim.x, [&](int cg) TOK_ROW_INLINE {
+    float sc[8], sh[8], mu[8], rs[8];
+    load8f(scale + cg * 8, sc);
+    load8f(shift + cg * 8, sh);
+    load8f(mean + cg * 8, mu);
+    load8f(rstd + cg * 8, rs);
+    PixelWalk px(rows.first + threadIdx.x / cge, rows.step, H, W);
+    return [=](int64_t, size_t off, float (&s)[2][8]) TOK_ROW_INLINE mutable {
+      const bf16x8 v = ldg16(y + off);
+      float dz[8];
+      pooled_dz(dpool, argmax, v, sc, sh, px.n, px.h, px.w, C, P, Q, cg, dz);
+      px.next();
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        s[0][e] += dz[e];
+        s[1][e] = fmaf(dz[e], (bf2f(v[e]) - mu[e]) * rs[e], s[1][e]);
+      }
+    };
+  });
+}
+
+// dy = c1 * dz + c2 * y + c3, geometry of bn_bwd_apply_kernel
+__global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const bf16* __restrict__ dpool,
+                                                                const uint8_t* __restrict__ argmax,
+                                                                const bf16* __restrict__ y, const float* __restrict__ scale,
+                                                                const float* __restrict__ shift, const float* __restrict__ coef,
+                                                                int64_t M, int H, int W, int C, int P, int Q, int cge, int rpb,
+                                                                bf16* __restrict__ dy) {
+  const RowSpan rows = grid_rows(M, rpb);
+  rows_map(rows, C, C, cge, rpb, [&](int cg) TOK_ROW_INLINE {
+    float sc[8], sh[8], c1[8], c2[8], c3[8];
+    load8f(scale + cg * 8, sc);
+    load8f(shift + cg * 8, sh);
+    load8f(coef + cg * 8, c1);
+    load8f(coef + C + cg * 8, c2);
+    load8f(coef + 2 * C + cg * 8, c3);
+    PixelWalk px(rows.first + threadIdx.x / cge, rows.step, H, W);
+    return [=](int64_t, size_t off) TOK_ROW_INLINE mutable {
+      const bf16x8 v = ldg16(y + off);
+      float dz[8];
+      pooled_dz(dpool, argmax, v, sc, sh, px.n, px.h, px.w, C, P, Q, cg, dz);
+      px.next();
+      bf16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = f2bf(fmaf(c1[e], dz[e], fmaf(c2[e], bf2f(v[e]), c3[e])));
+      stg16(dy + off, o);
+    };
+  });
 }
 
 
@@ -625,53 +579,27 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_pooled_kernel(const bf
                                                                         const float* __restrict__ mean,
                                                                         const float* __restrict__ rstd, int64_t M, int C,
                                                                         int cge, int rpb, float* __restrict__ partial) {
-  __shared__ float red[2][256][8];
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
-  const int cg_total = C >> 3;
-  const int cg_end = (cg_total + cge - 1) / cge * cge;   // block-uniform trip count: the barriers below sit inside this loop
-  for (int cg = cgl; cg < cg_end; cg += cge) {
-    const bool live = cg < cg_total;
-    float s1[8], s2[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb && live) {
-      float mu[8], rs[8];
-      load8f(mean + cg * 8, mu);
-      load8f(rstd + cg * 8, rs);
-      for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
-        const size_t off = (size_t)m * C + cg * 8;
-        const bf16x8 g = ldg16(dpool + off), z = ldg16(pooled + off), yv = ldg16(ypool + off);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float dz = bf2f(z[e]) > 0.f ? bf2f(g[e]) : 0.f;
-          s1[e] += dz;
-          s2[e] = fmaf(dz, (bf2f(yv[e]) - mu[e]) * rs[e], s2[e]);
-        }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
-    __syncthreads();
-    if (rl == 0 && live) {
-      for (int r = 1; r < rpb; ++r)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
+  rows_reduce<2>(grid_rows(M, rpb), C, C, cge, rpb, partial, blockIdx.x, gridDim.x, [&](int cg) TOK_ROW_INLINE {
+    float mu[8], rs[8];
+    load8f(mean + cg * 8, mu);
+    load8f(rstd + cg * 8, rs);
+    return [=](int64_t, size_t off, float (&s)[2][8]) TOK_ROW_INLINE {
+      const bf16x8 g = ldg16(dpool + off), z = ldg16(pooled + off), yv = ldg16(ypool + off);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        partial[((size_t)0 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s1[e];
-        partial[((size_t)1 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s2[e];
+        const float dz = bf2f(z[e]) > 0.f ? bf2f(g[e]) : 0.f;
+        s[0][e] += dz;
+        s[1][e] = fmaf(dz, (bf2f(yv[e]) - mu[e]) * rs[e], s[1][e]);
       }
-    }
-    __syncthreads();
-  }
+    };
+  });
 }
 
 }  // namespace
 
 static int stream_cap() {   // blocks of the elementwise kernels (TOK_BN_BLOCKS overrides).  1024 = 4 per CU = half the wave slots: the
                             // weight-gradient kernels of the side stream run beside them (2048 measured 1.7 % slower end to end)
-  static const int v = [] { const char* e = getenv("TOK_BN_BLOCKS"); return (int)(e ? atoi(e) : 1024); }();
+  static const int v = tok_env_int("TOK_BN_BLOCKS", 1024);
   return v;
 }
 #define kStreamCap stream_cap()
@@ -711,13 +639,13 @@ extern "C" int tok_bn_eval_coeffs(const float* gamma, const float* beta, const f
 
 extern "C" int tok_bn_stats_rows(int64_t m, int c) {
   if (m <= 0 || c <= 0 || c % 8) return TOK_ERR_INVALID;
-  return stream_blocks(m, make_geo(c), kReduceCap);
+  return row_blocks(m, make_geo(c), kReduceCap);
 }
 
 extern "C" int tok_bn_stats(const void* y, int64_t m, int c, float* stats, void* stream) {
   TOK_CHECK_ARG(y && stats && m > 0 && c > 0 && c % 8 == 0, "tok_bn_stats: bad args");
   const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(stream_blocks(m, g, kReduceCap)), dim3(256), 0,
+  hipLaunchKernelGGL(bn_stats_kernel, dim3(row_blocks(m, g, kReduceCap)), dim3(256), 0,
                      tok_stream(stream), (const bf16*)y, m, c, g.cge, g.rpb, stats);
   TOK_CHECK_LAUNCH("tok_bn_stats");
   return TOK_OK;
@@ -730,7 +658,7 @@ extern "C" int tok_bn_act_fwd(const void* y, const float* scale, const float* sh
   if (tok_dbg_skip(8)) return TOK_OK;
   if (tok_dbg_skip(32) && !relu && shortcut == nullptr) return TOK_OK;     // ablation: the apply passes of units WITHOUT activation (HRNet's fuse-path terms, projection shortcuts)
   const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(stream_blocks(m, g, kStreamCap)), dim3(256), 0,
+  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0,
                      tok_stream(stream), (const bf16*)y, scale, shift, (const bf16*)shortcut, relu,
                      (bf16*)out, mask, m, c, g.cge, g.rpb, (float*)nullptr);
   TOK_CHECK_LAUNCH("tok_bn_act_fwd");
@@ -741,7 +669,7 @@ extern "C" int tok_bn_act_fwd(const void* y, const float* scale, const float* sh
 // partial[tok_bn_act_fwd_colsum_rows(m, c)][c], to be folded by tok_colsum_f32
 extern "C" int tok_bn_act_fwd_colsum_rows(int64_t m, int c) {
   if (m <= 0 || c <= 0 || c % 8 != 0) return 0;
-  return stream_blocks(m, make_geo(c), kStreamCap);
+  return row_blocks(m, make_geo(c), kStreamCap);
 }
 
 extern "C" int tok_bn_act_fwd_colsum(const void* y, const float* scale, const float* shift, const void* shortcut, int relu,
@@ -750,7 +678,7 @@ extern "C" int tok_bn_act_fwd_colsum(const void* y, const float* scale, const fl
   TOK_CHECK_ARG(c <= 2048, "tok_bn_act_fwd_colsum: c <= 2048 (one channel-group pass per thread: uniform barriers)");
   if (tok_dbg_skip(8)) return TOK_OK;
   const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(stream_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream), (const bf16*)y,
+  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream), (const bf16*)y,
                      scale, shift, (const bf16*)shortcut, relu, (bf16*)out, mask, m, c, g.cge, g.rpb, partial);
   TOK_CHECK_LAUNCH("tok_bn_act_fwd_colsum");
   return TOK_OK;
@@ -764,9 +692,9 @@ extern "C" int tok_bn_bwd_reduce(const void* dout, const void* y, const uint8_t*
   TOK_CHECK_ARG(dout && y && scale && shift && mean && rstd && partial, "tok_bn_bwd_reduce: null pointer");
   TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "tok_bn_bwd_reduce: bad sizes");
   const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(stream_blocks(m, g, kReduceCap)), dim3(256), 0,
-                     tok_stream(stream), (const bf16*)dout, (const bf16*)y, mask, scale, shift,
-                     mean, rstd, relu, m, c, g.cge, g.rpb, partial);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<ReluD>, dim3(row_blocks(m, g, kReduceCap)), dim3(256), 0,
+                     tok_stream(stream), (const bf16*)dout, (const bf16*)y, ReluD{relu, mask}, scale, shift,
+                     mean, rstd, m, c, g.cge, g.rpb, partial);
   TOK_CHECK_LAUNCH("tok_bn_bwd_reduce");
   return TOK_OK;
 }
@@ -801,23 +729,60 @@ extern "C" int tok_bn_bwd_apply(const void* dout, const void* y, const uint8_t* 
   }
   if (tok_dbg_skip(8)) { t_done_event = nullptr; return TOK_OK; }
   const Geo g = make_geo(c);
+  const ReluD act{relu, mask};
   if (t_done_event != nullptr) {
     // completion event attached to THIS dispatch (hipExtLaunchKernelGGL stop event): a side stream can wait for the kernel
     // without a separate event-record packet on the main queue (a ~7 us bubble per fork)
     hipEvent_t ev = t_done_event;
     t_done_event = nullptr;
-    hipExtLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream), nullptr, ev,
-                          0, (const bf16*)dout, (const bf16*)y, mask, scale, shift, coef, relu, (bf16*)dy, (bf16*)dshortcut,
-                          dshortcut_accumulate, m, c, g.cge, g.rpb);
+    hipExtLaunchKernelGGL(bn_bwd_apply_kernel<ReluD>, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
+                          nullptr, ev, 0, (const bf16*)dout, (const bf16*)y, act, scale, shift, coef, (bf16*)dy,
+                          (bf16*)dshortcut, dshortcut_accumulate, m, c, g.cge, g.rpb);
   } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_blocks(m, g, kStreamCap)), dim3(256), 0,
-                       tok_stream(stream), (const bf16*)dout, (const bf16*)y, mask, scale, shift,
-                       coef, relu, (bf16*)dy, (bf16*)dshortcut, dshortcut_accumulate, m, c, g.cge, g.rpb);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<ReluD>, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0,
+                       tok_stream(stream), (const bf16*)dout, (const bf16*)y, act, scale, shift,
+                       coef, (bf16*)dy, (bf16*)dshortcut, dshortcut_accumulate, m, c, g.cge, g.rpb);
   }
   TOK_CHECK_LAUNCH("tok_bn_bwd_apply");
   return TOK_OK;
 }
 
+
+// ---- hard-swish units: the ReLU path's geometry, block caps and partial-row layout with the hard-swish rule ------------------
+extern "C" int tok_bn_hswish_fwd(const void* y, const float* scale, const float* shift, void* out, int64_t m, int c,
+                                 void* stream) {
+  TOK_CHECK_ARG(y && scale && shift && out && m > 0 && c > 0 && c % 8 == 0, "tok_bn_hswish_fwd: bad args");
+  if (tok_dbg_skip(8)) return TOK_OK;
+  const Geo g = make_geo(c);
+  hipLaunchKernelGGL(bn_hswish_fwd_kernel, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)y, scale, shift, (bf16*)out, m, c, g.cge, g.rpb);
+  TOK_CHECK_LAUNCH("tok_bn_hswish_fwd");
+  return TOK_OK;
+}
+
+extern "C" int tok_bn_hswish_bwd_reduce(const void* dout, const void* y, const float* scale, const float* shift,
+                                        const float* mean, const float* rstd, int64_t m, int c, float* partial, void* stream) {
+  TOK_CHECK_ARG(dout && y && scale && shift && mean && rstd && partial, "tok_bn_hswish_bwd_reduce: null pointer");
+  TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "tok_bn_hswish_bwd_reduce: bad sizes");
+  const Geo g = make_geo(c);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<HswishD>, dim3(row_blocks(m, g, kReduceCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)dout, (const bf16*)y, HswishD{}, scale, shift, mean, rstd, m, c, g.cge, g.rpb, partial);
+  TOK_CHECK_LAUNCH("tok_bn_hswish_bwd_reduce");
+  return TOK_OK;
+}
+
+extern "C" int tok_bn_hswish_bwd_apply(const void* dout, const void* y, const float* scale, const float* shift,
+                                       const float* coef, void* dy, int64_t m, int c, void* stream) {
+  TOK_CHECK_ARG(dout && y && scale && shift && coef && dy, "tok_bn_hswish_bwd_apply: null pointer");
+  TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "tok_bn_hswish_bwd_apply: bad sizes");
+  if (tok_dbg_skip(8)) return TOK_OK;
+  const Geo g = make_geo(c);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel<HswishD>, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)dout, (const bf16*)y, HswishD{}, scale, shift, coef, (bf16*)dy, (bf16*)nullptr, 0, m, c,
+                     g.cge, g.rpb);
+  TOK_CHECK_LAUNCH("tok_bn_hswish_bwd_apply");
+  return TOK_OK;
+}
 
 // ---- completion events carried by a launch (two-stream schedule without record packets) ------------------------------------
 extern "C" void* tok_event_create(void) {
@@ -856,9 +821,9 @@ extern "C" int tok_bn_pool_bwd_reduce(const void* dpool, const uint8_t* argmax, 
                 c % 8 == 0, "tok_bn_pool_bwd_reduce: bad args");
   const int64_t m = (int64_t)n * h * w;
   const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_pool_bwd_kernel<true>, dim3(stream_blocks(m, g, kReduceCap)), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)dpool, argmax, (const bf16*)y, scale, shift, mean, rstd, (const float*)nullptr, m, h, w, c,
-                     (h + 2 - 3) / 2 + 1, (w + 2 - 3) / 2 + 1, g.cge, g.rpb, partial, (bf16*)nullptr);
+  hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(row_blocks(m, g, kReduceCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)dpool, argmax, (const bf16*)y, scale, shift, mean, rstd, m, h, w, c, (h + 2 - 3) / 2 + 1,
+                     (w + 2 - 3) / 2 + 1, g.cge, g.rpb, partial);
   TOK_CHECK_LAUNCH("tok_bn_pool_bwd_reduce");
   return TOK_OK;
 }
@@ -870,9 +835,9 @@ extern "C" int tok_bn_pool_bwd_apply(const void* dpool, const uint8_t* argmax, c
                 "tok_bn_pool_bwd_apply: bad args");
   const int64_t m = (int64_t)n * h * w;
   const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_pool_bwd_kernel<false>, dim3(stream_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)dpool, argmax, (const bf16*)y, scale, shift, (const float*)nullptr, (const float*)nullptr,
-                     coef, m, h, w, c, (h + 2 - 3) / 2 + 1, (w + 2 - 3) / 2 + 1, g.cge, g.rpb, (float*)nullptr, (bf16*)dy);
+  hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)dpool, argmax, (const bf16*)y, scale, shift, coef, m, h, w, c, (h + 2 - 3) / 2 + 1,
+                     (w + 2 - 3) / 2 + 1, g.cge, g.rpb, (bf16*)dy);
   TOK_CHECK_LAUNCH("tok_bn_pool_bwd_apply");
   return TOK_OK;
 }
@@ -882,7 +847,7 @@ extern "C" int tok_bn_pool_bwd_reduce_pooled(const void* dpool, const void* pool
   TOK_CHECK_ARG(dpool && pooled && ypool && mean && rstd && partial && m_pooled > 0 && c > 0 && c % 8 == 0,
                 "tok_bn_pool_bwd_reduce_pooled: bad args");
   const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_pool_bwd_reduce_pooled_kernel, dim3(stream_blocks(m_pooled, g, kReduceCap)), dim3(256), 0,
+  hipLaunchKernelGGL(bn_pool_bwd_reduce_pooled_kernel, dim3(row_blocks(m_pooled, g, kReduceCap)), dim3(256), 0,
                      tok_stream(stream), (const bf16*)dpool, (const bf16*)pooled, (const bf16*)ypool, mean, rstd, m_pooled, c,
                      g.cge, g.rpb, partial);
   TOK_CHECK_LAUNCH("tok_bn_pool_bwd_reduce_pooled");

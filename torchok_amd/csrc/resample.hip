@@ -5,7 +5,7 @@
 //                           (necks/segmentation/hrnet.py:36-39, written straight into its slice of the
 //                           concat buffer, :41) and SegmentationHead (heads/segmentation/base.py:37)
 // All four are HBM streaming kernels; the backward passes are gathers (deterministic, no atomics).
-#include "tok_common.h"
+#include "row_stream.h"
 #include <stdlib.h>
 
 namespace {
@@ -390,70 +390,63 @@ struct UpSumArgs {
   int nt, n, h, w, c;
 };
 
+// a * b + c * d with both products rounded on their own, whatever the surrounding code
+__device__ __forceinline__ float mul2_add(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  return a * b + c * d;
+}
+// hy * (hx * a + lx * b) + ly * (hx * c + lx * d) of channel e of the lane's eight, with every rounding written out.  Left to
+// -ffp-contract=fast the form depends on the surrounding code AND on the channel (hipcc packs the eight channels in pairs and
+// fuses a different product of each sum in the two halves of a pair; the last pair keeps some sums unfused).  This is the form
+// the kernel has always computed; the bits of the HRNet neck rest on it.
+__device__ __forceinline__ float blend4(int e, float hx, float lx, float hy, float ly, float a, float b, float c, float d) {
+  if (e == 6) return mul2_add(hy, mul2_add(hx, a, lx, b), ly, mul2_add(hx, c, lx, d));
+  const float u = fmaf(lx, b, hx * a), w = fmaf(hx, c, lx * d);
+  if (e == 7) return mul2_add(hy, u, ly, w);
+  return (e & 1) ? fmaf(hy, u, ly * w) : fmaf(ly, w, hy * u);
+}
+
 __global__ __launch_bounds__(256) void bilinear_sum_stats_kernel(const bf16* y0, bf16* y, UpSumArgs a, int cge, int rpb,
                                                                  float* __restrict__ partial) {
-  __shared__ float red[2][256][8];
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
-  const int cg_total = a.c >> 3;
   const int M = a.n * a.h * a.w;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
-    float s1[8], s2[8];
+  rows_reduce<2>(grid_rows(M, rpb), a.c, a.c, cge, rpb, partial, blockIdx.x, gridDim.x, [&](int cg) TOK_ROW_INLINE {
+    // (`a` by reference: a copy indexed by the runtime j would live in scratch)
+    return [&a, y0, y, cg](int64_t row, size_t off, float (&s)[2][8]) TOK_ROW_INLINE {
+      const int m = (int)row;
+      const int x = m % a.w;
+      const int t2 = m / a.w;
+      const int yy = t2 % a.h;
+      const int b = t2 / a.h;
+      const bf16x8 v0 = ldg16(y0 + off);
+      float acc[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
-    if (rl < rpb) {
-      for (int m = blockIdx.x * rpb + rl; m < M; m += gridDim.x * rpb) {
-        const int x = m % a.w;
-        const int t2 = m / a.w;
-        const int yy = t2 % a.h;
-        const int b = t2 / a.h;
-        const bf16x8 v0 = ldg16(y0 + (size_t)m * a.c + cg * 8);
-        float acc[8];
+      for (int e = 0; e < 8; ++e) acc[e] = bf2f(v0[e]);
+      for (int j = 0; j < a.nt; ++j) {
+        int r0, r1, c0, c1;
+        float ly, lx;
+        src_index(a.sh[j], yy, a.hs[j], r0, r1, ly);
+        src_index(a.sw[j], x, a.ws[j], c0, c1, lx);
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        const bf16* base = a.t[j] + (size_t)b * a.hs[j] * a.ws[j] * a.c + cg * 8;
+        const bf16x8 v00 = ldg16(base + ((size_t)r0 * a.ws[j] + c0) * a.c);
+        const bf16x8 v01 = ldg16(base + ((size_t)r0 * a.ws[j] + c1) * a.c);
+        const bf16x8 v10 = ldg16(base + ((size_t)r1 * a.ws[j] + c0) * a.c);
+        const bf16x8 v11 = ldg16(base + ((size_t)r1 * a.ws[j] + c1) * a.c);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = bf2f(v0[e]);
-        for (int j = 0; j < a.nt; ++j) {
-          int r0, r1, c0, c1;
-          float ly, lx;
-          src_index(a.sh[j], yy, a.hs[j], r0, r1, ly);
-          src_index(a.sw[j], x, a.ws[j], c0, c1, lx);
-          const float hy = 1.f - ly, hx = 1.f - lx;
-          const bf16* base = a.t[j] + (size_t)b * a.hs[j] * a.ws[j] * a.c + cg * 8;
-          const bf16x8 v00 = ldg16(base + ((size_t)r0 * a.ws[j] + c0) * a.c);
-          const bf16x8 v01 = ldg16(base + ((size_t)r0 * a.ws[j] + c1) * a.c);
-          const bf16x8 v10 = ldg16(base + ((size_t)r1 * a.ws[j] + c0) * a.c);
-          const bf16x8 v11 = ldg16(base + ((size_t)r1 * a.ws[j] + c1) * a.c);
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            acc[e] += hy * (hx * bf2f(v00[e]) + lx * bf2f(v01[e])) + ly * (hx * bf2f(v10[e]) + lx * bf2f(v11[e]));
-        }
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          o[e] = f2bf(acc[e]);
-          const float f = bf2f(o[e]);
-          s1[e] += f;
-          s2[e] += f * f;
-        }
-        stg16(y + (size_t)m * a.c + cg * 8, o);
+        for (int e = 0; e < 8; ++e)
+          acc[e] += blend4(e, hx, lx, hy, ly, bf2f(v00[e]), bf2f(v01[e]), bf2f(v10[e]), bf2f(v11[e]));
       }
-    }
-    if (partial != nullptr) {
+      bf16x8 o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { red[0][tid][e] = s1[e]; red[1][tid][e] = s2[e]; }
-      __syncthreads();
-      if (rl == 0) {
-        for (int r = 1; r < rpb; ++r)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { s1[e] += red[0][r * cge + cgl][e]; s2[e] += red[1][r * cge + cgl][e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          partial[((size_t)0 * gridDim.x + blockIdx.x) * a.c + cg * 8 + e] = s1[e];
-          partial[((size_t)1 * gridDim.x + blockIdx.x) * a.c + cg * 8 + e] = s2[e];
-        }
+      for (int e = 0; e < 8; ++e) {
+        o[e] = f2bf(acc[e]);
+        const float f = bf2f(o[e]);
+        s[0][e] += f;
+        s[1][e] = fmaf(f, f, s[1][e]);
       }
-      __syncthreads();
-    }
-  }
+      stg16(y + off, o);
+    };
+  });
 }
 
 __global__ __launch_bounds__(256) void bilinear_bwd_generic_kernel(const bf16* __restrict__ ddst, bf16* dsrc, BilArgs a,
@@ -782,6 +775,8 @@ extern "C" int tok_bilinear_sum_stats_rows(int n, int h, int w, int c) {
   return tok_bn_stats_rows((int64_t)n * h * w, c);
 }
 
+// Any c % 8 == 0: above 2048 channels a lane of the generic kernel walks several channel groups and the skeleton keeps the
+// barrier count uniform.
 extern "C" int tok_bilinear_sum_stats(const void* y0, const void* t1, int h1, int w1, const void* t2, int h2, int w2,
                                       const void* t3, int h3, int w3, int n, int h, int w, int c, void* y, float* stats,
                                       void* stream) {
@@ -817,9 +812,9 @@ extern "C" int tok_bilinear_sum_stats(const void* y0, const void* t1, int h1, in
     hipLaunchKernelGGL(bilinear_sum_tiled_kernel, dim3(rows), dim3(256), 0, tok_stream(stream), u);
   } else {
     // (any grid works for the generic kernel: blocks beyond the rows write zero partials)
-    const int cg_total = c / 8, cge = cg_total < 256 ? cg_total : 256, rpb = 256 / cge;
+    const Geo g = make_geo(c);
     hipLaunchKernelGGL(bilinear_sum_stats_kernel, dim3(rows), dim3(256), 0, tok_stream(stream), (const bf16*)y0, (bf16*)y, a,
-                       cge, rpb, stats);
+                       g.cge, g.rpb, stats);
   }
   TOK_CHECK_LAUNCH("tok_bilinear_sum_stats");
   return TOK_OK;

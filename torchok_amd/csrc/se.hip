@@ -9,7 +9,7 @@
 // Backward: per-(image, chunk) sums of dout * x (= d(out)/ds) -> one block per image: ds, d(hidden), d(mean) -> the four
 //           parameter gradients summed over the images in image order -> dx (=|+=) dout * s + d(mean) / hw in one pass.
 // Every sum folds in a fixed order (no float atomics): bit-reproducible run to run.
-#include "tok_common.h"
+#include "row_stream.h"
 
 namespace {
 
@@ -22,9 +22,10 @@ struct SeGeo {
 };
 
 SeGeo se_geo(int n, int hw, int c) {
+  const Geo rg = make_geo(c);
   SeGeo g;
-  g.cge = (c >> 3) < 256 ? (c >> 3) : 256;
-  g.rpb = 256 / g.cge;
+  g.cge = rg.cge;
+  g.rpb = rg.rpb;
   int want = (hw + 4 * g.rpb - 1) / (4 * g.rpb);        // at least 4 rows per lane
   const int cap = (kCap + n - 1) / n;
   if (want > cap) want = cap;
@@ -32,44 +33,27 @@ SeGeo se_geo(int n, int hw, int c) {
   return g;
 }
 
-// part[img][chunk][c] = sum over the chunk's pixels of a (* b when b != NULL)
+// part[img][chunk][c] = sum over the chunk's pixels of a (* b when b != NULL): a block walks the pixel range of its chunk of
+// one image instead of grid-striding over the whole matrix
 __global__ __launch_bounds__(256) void se_sum_kernel(const bf16* __restrict__ a, const bf16* __restrict__ b, int hw, int C,
                                                      int ld, int cge, int rpb, float* __restrict__ part) {
-  __shared__ float red[256][8];
-  const int tid = threadIdx.x, cgl = tid % cge, rl = tid / cge;
   const int img = blockIdx.y, chunk = blockIdx.x, chunks = gridDim.x;
   const int len = (hw + chunks - 1) / chunks;
   const int p0 = chunk * len, p1 = p0 + len < hw ? p0 + len : hw;
-  for (int cg = cgl; cg < (C >> 3); cg += cge) {     // (same trip count in every lane: cge divides the groups or one pass)
-    float s[8];
+  const RowSpan rows = {(int64_t)img * hw + p0, (int64_t)img * hw + p1, rpb};
+  rows_reduce<1>(rows, C, ld, cge, rpb, part, (size_t)img * chunks + chunk, 0, [&](int) TOK_ROW_INLINE {
+    return [=](int64_t, size_t off, float (&s)[1][8]) TOK_ROW_INLINE {
+      const bf16x8 va = ldg16(a + off);
+      if (b != nullptr) {
+        const bf16x8 vb = ldg16(b + off);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = 0.f;
-    if (rl < rpb) {
-      for (int p = p0 + rl; p < p1; p += rpb) {
-        const size_t off = ((size_t)img * hw + p) * ld + cg * 8;
-        const bf16x8 va = ldg16(a + off);
-        if (b != nullptr) {
-          const bf16x8 vb = ldg16(b + off);
+        for (int e = 0; e < 8; ++e) s[0][e] = fmaf(bf2f(va[e]), bf2f(vb[e]), s[0][e]);
+      } else {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) s[e] = fmaf(bf2f(va[e]), bf2f(vb[e]), s[e]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) s[e] += bf2f(va[e]);
-        }
+        for (int e = 0; e < 8; ++e) s[0][e] += bf2f(va[e]);
       }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[tid][e] = s[e];
-    __syncthreads();
-    if (rl == 0) {
-      for (int r = 1; r < rpb; ++r)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s[e] += red[r * cge + cgl][e];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) part[((size_t)img * chunks + chunk) * C + cg * 8 + e] = s[e];
-    }
-    __syncthreads();
-  }
+    };
+  });
 }
 
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + __expf(-v)); }

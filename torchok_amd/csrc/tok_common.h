@@ -155,26 +155,6 @@ __device__ __forceinline__ f32x2 gelu_d2(f32x2 x) {          // the two-wide gel
   return __builtin_elementwise_fma(x, pdf, cdf);
 }
 
-// Row-streaming geometry of the per-channel passes (bn.hip, act.hip, layer_scale.hip): CGE = min(C/8, 256) channel groups
-// across the block, RPB = 256 / CGE rows per block iteration; a lane keeps ONE 8-channel group (16 bytes of bf16) for its life.
-struct Geo {
-  int cg_total, cge, rpb;
-};
-inline Geo make_geo(int c) {
-  Geo g;
-  g.cg_total = c / 8;
-  g.cge = g.cg_total < 256 ? g.cg_total : 256;
-  g.rpb = 256 / g.cge;
-  return g;
-}
-// the lane's 8 per-channel fp32 coefficients
-__device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
 __device__ __forceinline__ bf16x8 zero8() {
   bf16x8 z;
 #pragma unroll

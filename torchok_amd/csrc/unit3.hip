@@ -15,7 +15,7 @@
 //       dW_k  = c1_k G_k + c2_k (Z w_k) + c3_k colsum(z)
 //       dz_in = dz (diag(c1) W) + z (W^T diag(c2) W) + c3^T W           (two GEMMs on tensors that exist + a bias)
 // tok_bn3_bwd_prepare produces dgamma / dbeta / dW and the bf16 operands Wa = diag(c1) W, Wb = W^T diag(c2) W, cvec = c3^T W.
-#include "tok_common.h"
+#include "row_stream.h"
 
 namespace {
 
@@ -278,42 +278,21 @@ __global__ __launch_bounds__(1024) void bn3_wb_block_kernel(const float* __restr
 __global__ __launch_bounds__(256) void relu_mask_reduce_kernel(const bf16* dout, const uint8_t* __restrict__ mask, int64_t M,
                                                                int C, int cge, int rpb, bf16* dz,
                                                                float* __restrict__ partial) {
-  __shared__ float red[256][8];
-  const int tid = threadIdx.x;
-  const int cgl = tid % cge, rl = tid / cge;
   const int cg_total = C >> 3;
-  for (int cg = cgl; cg < cg_total; cg += cge) {
-    float s1[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s1[e] = 0.f;
-    if (rl < rpb) {
-      for (int64_t m = (int64_t)blockIdx.x * rpb + rl; m < M; m += (int64_t)gridDim.x * rpb) {
-        const size_t off = (size_t)m * C + cg * 8;
-        bf16x8 g = ldg16(dout + off);
-        const unsigned bits = mask != nullptr ? mask[(size_t)m * cg_total + cg] : 0xffu;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          if (!((bits >> e) & 1u)) g[e] = (bf16)0.f;
-          s1[e] += bf2f(g[e]);
-        }
-        if (mask != nullptr || dz != dout) stg16(dz + off, g);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[tid][e] = s1[e];
-    __syncthreads();
-    if (rl == 0) {
-      for (int r = 1; r < rpb; ++r)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s1[e] += red[r * cge + cgl][e];
+  rows_reduce<1>(grid_rows(M, rpb), C, C, cge, rpb, partial, blockIdx.x, gridDim.x, [&](int cg) TOK_ROW_INLINE {
+    return [=](int64_t m, size_t off, float (&s1)[1][8]) TOK_ROW_INLINE {
+      bf16x8 g = ldg16(dout + off);
+      const unsigned bits = mask != nullptr ? mask[(size_t)m * cg_total + cg] : 0xffu;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        partial[((size_t)0 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = s1[e];
-        partial[((size_t)1 * gridDim.x + blockIdx.x) * C + cg * 8 + e] = 0.f;
+        if (!((bits >> e) & 1u)) g[e] = (bf16)0.f;
+        s1[0][e] += bf2f(g[e]);
       }
-    }
-    __syncthreads();
-  }
+      if (mask != nullptr || dz != dout) stg16(dz + off, g);
+    };
+  });
+  float* zero = partial + ((size_t)gridDim.x + blockIdx.x) * C;
+  for (int c = threadIdx.x; c < C; c += 256) zero[c] = 0.f;
 }
 
 // ---- backward prepare, launch 1: 16 output channels k per workgroup (one wave walks 4 of them) --------------------------------
@@ -397,13 +376,6 @@ __global__ __launch_bounds__(1024) void bn3_prepare_rows_kernel(
   }
 }
 
-inline int mr_geo(int c, int& cge, int& rpb) {
-  const int cg_total = c / 8;
-  cge = cg_total < 256 ? cg_total : 256;
-  rpb = 256 / cge;
-  return cg_total;
-}
-
 }  // namespace
 
 extern "C" int tok_bn_bwd_rows(int64_t m, int c);
@@ -459,14 +431,14 @@ extern "C" int tok_bn_gram_finalize(const float* Z, const float* zsum, const flo
   return TOK_OK;
 }
 
+// Any c % 8 == 0: above 2048 channels a lane walks several channel groups and the skeleton keeps the barrier count uniform.
 extern "C" int tok_relu_mask_reduce(const void* dout, const uint8_t* mask, int64_t m, int c, void* dz, float* partial,
                                     void* stream) {
   TOK_CHECK_ARG(dout && dz && partial && m > 0 && c > 0 && c % 8 == 0, "tok_relu_mask_reduce: bad args");
-  int cge, rpb;
-  mr_geo(c, cge, rpb);
+  const Geo g = make_geo(c);
   const int rows = tok_bn_bwd_rows(m, c);
-  hipLaunchKernelGGL(relu_mask_reduce_kernel, dim3(rows), dim3(256), 0, tok_stream(stream), (const bf16*)dout, mask, m, c, cge,
-                     rpb, (bf16*)dz, partial);
+  hipLaunchKernelGGL(relu_mask_reduce_kernel, dim3(rows), dim3(256), 0, tok_stream(stream), (const bf16*)dout, mask, m, c,
+                     g.cge, g.rpb, (bf16*)dz, partial);
   TOK_CHECK_LAUNCH("tok_relu_mask_reduce");
   return TOK_OK;
 }

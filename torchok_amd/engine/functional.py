@@ -12,7 +12,7 @@ dwconv_bn_act             depthwise conv -> batch_norm -> relu           ([timm]
 squeeze_excite            x * gate(expand(relu(reduce(mean(x)))))        ([timm] efficientnet_blocks.SqueezeExcite;
                           gate = sigmoid or hard sigmoid)
 
-conv_bn_act / dwconv_bn_act take act='hard_swish' (MobileNetV3): the mask-less activation path of csrc/act.hip.
+conv_bn_act / dwconv_bn_act take act='hard_swish' (MobileNetV3): the mask-less activation path of csrc/bn.hip.
 """
 import weakref
 from typing import Optional

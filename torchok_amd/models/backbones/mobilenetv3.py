@@ -9,7 +9,7 @@ Module / parameter names are those of timm, so reference checkpoints load.
 The blocks, the block-string decoder and the builder are those of ``_efficientnet_blocks.py``, shared with
 ``efficientnet.py``; this family passes what differs: the 'cn' block type and the 'nre' option (a block marked ``nre`` runs its
 units with ReLU, every other block with the model's activation, hard-swish: ``act='hard_swish'``, the mask-less path of
-csrc/act.hip), the squeeze-excite that keeps its ReLU inside, gates with a hard sigmoid and rounds its width with
+csrc/bn.hip), the squeeze-excite that keeps its ReLU inside, gates with a hard sigmoid and rounds its width with
 ``round_channels``, ``se_from_exp=True`` and the stem feature.  Not built: ``mobilenetv3_rw``, the ``tf_*`` variants (asymmetric
 "same" padding), the ``minimal`` variants, ``fbnetv3_*`` and ``lcnet_*``.
 """
