@@ -63,8 +63,9 @@ def _inputs(b, n, heads, seed):
 
 
 # (batch, n, heads): smallest; 2x2 grid; exactly one tile; one key and one query past the tile; the real layer; 384 px; and a
-# batch larger than the d(bias) chunk count can cover with one image each (64 chunks at most), so chunks hold two images
-SHAPES = [(1, 2, 1), (3, 5, 2), (2, 64, 1), (2, 65, 2), (4, 197, 12), (1, 577, 1), (70, 5, 1)]
+# batch larger than the d(bias) chunk count can cover with one image each (64 chunks at most), so chunks hold two images; the
+# same with 2 x 2 tiles that have a tail in both directions, three images per chunk and a last chunk of one image
+SHAPES = [(1, 2, 1), (3, 5, 2), (2, 64, 1), (2, 65, 2), (4, 197, 12), (1, 577, 1), (70, 5, 1), (130, 65, 1)]
 _cache = {}
 
 
@@ -81,6 +82,7 @@ def test_the_chunk_fold_runs():
     lib = _C.lib()
     assert lib.tok_global_attn_bias_bwd_chunks(70, 5, 1) == 35          # two images per chunk, 35 partials folded
     assert lib.tok_global_attn_bias_bwd_chunks(3, 5, 2) == 3
+    assert lib.tok_global_attn_bias_bwd_chunks(130, 65, 1) == 44        # 4 tiles: 64 chunks wanted, 3 images each, the last holds 1
     assert lib.tok_global_attn_bias_bwd_chunks(256, 197, 12) == 11      # 192 tiles x 11 chunks = 2112 workgroups
 
 

@@ -11,6 +11,13 @@
 //           order: no float atomics, bit-reproducible run to run.
 // Bias    : BEiT's relative-position bias ([timm 0.6.13] beit.Attention) is one more template argument of the same kernels:
 //           softmax(q k^T * 64^-0.5 + bias[h]); its gradient is a reduction over the images (gattn_dbias_kernel).
+// Pieces  : the four MFMA kernels (fwd, dkv, dq, dbias) are written on load_rows16 (16 token rows as an A operand), frag_x_tile
+//           (operand x row-major LDS tile), rows_x_tile_t (staged rows x transposed LDS tile), load_row_stats (LSE and delta of a
+//           lane's four queries), prob and ds_tile (P and dS = P (dP - delta), shared by dq and dbias).  What these pieces
+//           multiply and add is written as fmaf where it is fused and as mul_rn / sub_rn where it is not, so that hipcc's
+//           contraction cannot differ between the callers; the three forms of the bias term are listed at prob.
+//           On the host one launcher serves both forward entry points and one routine both backward ones (bias == nullptr picks
+//           the un-biased kernels).
 #include "tok_common.h"
 
 namespace {
@@ -48,6 +55,90 @@ __device__ __forceinline__ float sum16(float v) {
   return v;
 }
 
+// ---- the pieces the four MFMA kernels are written on ---------------------------------------------------------------------------
+// A lane is (l15, g) = (lane & 15, lane >> 4) of its wave.  Element (j, r) of a product, j the f32x4 of four and r its component,
+// is row 4 g + r of the A operand's 16 rows against row 16 j + l15 of the 64-row LDS tile.  Every accumulator takes t = 0, then
+// t = 1 (the two halves of the 64-wide reduction): the bits of every output depend on that order.
+
+// a * b and a - b rounded on their own.  hipcc contracts a * b + c wherever both operations allow it, and the __fmul_rn / __fsub_rn
+// of this toolchain are the plain operators, which fuse like any other: what must stay unfused is written under contract(off),
+// what is fused is written fmaf.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
+// token rows [r0, r0 + 16) of the 64-wide column block `col` as an A operand (the lane: row r0 + l15, columns 32 t + 8 g ... + 7);
+// rows past n are zero
+__device__ __forceinline__ void load_rows16(const bf16* __restrict__ base, int ld, int col, int r0, int n, int l15, int g,
+                                            bf16x8 (&f)[2]) {
+  const int row = r0 + l15;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) f[t] = row < n ? ldg16(base + (size_t)row * ld + col + 32 * t + 8 * g) : zero8();
+}
+
+// acc = a x tile^T, tile a row-major LDS tile [64][PT]
+__device__ __forceinline__ void frag_x_tile(const bf16x8 (&a)[2], const bf16* tile, int l15, int g, f32x4 (&acc)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+      acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], lds8(tile + (j * 16 + l15) * PT + 32 * t + 8 * g), acc[j], 0, 0, 0);
+  }
+}
+
+// acc += rows x tile_t^T: the [16][PT] rows a wave staged in LDS (P, dS or their transposes) times a transposed LDS tile [d][PT]
+__device__ __forceinline__ void rows_x_tile_t(const bf16* rows, const bf16* tile_t, int l15, int g, f32x4 (&acc)[4]) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const bf16x8 a = lds8(rows + l15 * PT + 32 * t + 8 * g);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, lds8(tile_t + (j * 16 + l15) * PT + 32 * t + 8 * g), acc[j], 0, 0, 0);
+  }
+}
+
+// log-sum-exp in log2 units (INFINITY past n: P = 0) and delta (0 past n) of the query rows q ... q + 3
+__device__ __forceinline__ void load_row_stats(const float* __restrict__ lrow, const float* __restrict__ drow, int q, int n,
+                                               float (&lr)[4], float (&dr)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    lr[r] = q + r < n ? mul_rn(lrow[q + r], LOG2E) : INFINITY;
+    dr[r] = q + r < n ? drow[q + r] : 0.f;
+  }
+}
+
+// P = exp2(s * 64^-0.5 * log2e - lb) in one fused multiply-subtract; lb is the query's log-sum-exp less the bias term, both in
+// log2 units.
+// The bias term enters in three forms, each pinned to what its kernel has always computed, so the caller forms it:
+//   forward          bl = bias * log2e rounded, then fma(s, sc, bl)
+//   dK/dV and dQ     lb = fma(-bias, log2e, lse): one rounding
+//   d(bias)          lb = lse - bl with bl = bias * log2e rounded: two roundings (bl is loaded once per tile, outside the image loop)
+// so the P of the backward is not the same float in d(bias) as in dQ.  Making them one form changes output bits.
+__device__ __forceinline__ float prob(float s, float lb) { return exp2f(fmaf(s, SCALE * LOG2E, -lb)); }
+
+// dS = P (dP - delta) of the wave's 16 queries against the 64 keys from k0: sink(kj, r, p, d) takes the two factors of element
+// (kj, r), dS = p * d, with p = 0 for a key past n.  lb(kj, r, live) is the caller's log-sum-exp less bias term (see prob).
+// gattn_dq_kernel rounds the product to bf16, gattn_dbias_kernel fuses it into its sum over the images.
+template <class Lb, class Sink>
+__device__ __forceinline__ void ds_tile(const f32x4 (&s)[4], const f32x4 (&dp)[4], const float (&dr)[4], int k0, int n, int l15,
+                                        Lb&& lb, Sink&& sink) {
+#pragma unroll
+  for (int kj = 0; kj < 4; ++kj) {
+    const bool live = k0 + kj * 16 + l15 < n;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float p = prob(s[kj][r], lb(kj, r, live));
+      sink(kj, r, live ? p : 0.f, dp[kj][r] - dr[r]);
+    }
+  }
+}
+
 // BIAS: logits get + bias[h][query][key] (fp32, row pitch ldb, shared by every image); columns >= N of a bias row and rows of
 // queries >= N are never loaded.  Without it the kernel is the one the un-biased entry point has always launched.
 template <bool BIAS>
@@ -62,11 +153,7 @@ __global__ __launch_bounds__(256) void gattn_fwd_kernel(const bf16* __restrict__
   const int q0 = blockIdx.x * TL + wv * 16;
   const bf16* base = qkv + (size_t)b * N * ldq;
   bf16x8 qf[2];
-  {
-    const int qr = q0 + l15;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) qf[s] = qr < N ? ldg16(base + (size_t)qr * ldq + h * HD + 32 * s + 8 * g) : zero8();
-  }
+  load_rows16(base, ldq, h * HD, q0, N, l15, g, qf);
   float m[4], l[4];
   f32x4 o[4];
 #pragma unroll
@@ -82,12 +169,7 @@ __global__ __launch_bounds__(256) void gattn_fwd_kernel(const bf16* __restrict__
     stage_tile(base, ldq, 2 * C + h * HD, k0, N, nullptr, vt);
     __syncthreads();
     f32x4 s[4];
-#pragma unroll
-    for (int kj = 0; kj < 4; ++kj) {
-      s[kj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 2; ++t) s[kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t], lds8(ks + (kj * 16 + l15) * PT + 32 * t + 8 * g), s[kj], 0, 0, 0);
-    }
+    frag_x_tile(qf, ks, l15, g, s);
     // element (kj, r): query 4g + r of the wave's 16, key k0 + 16 kj + l15
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -97,8 +179,8 @@ __global__ __launch_bounds__(256) void gattn_fwd_kernel(const bf16* __restrict__
         const int key = k0 + kj * 16 + l15;
         if constexpr (BIAS) {
           const int q = q0 + 4 * g + r;
-          const float bl = (key < N && q < N) ? bias[((size_t)h * N + q) * ldb + key] * LOG2E : 0.f;
-          v[kj] = (key < N) ? s[kj][r] * sc + bl : -INFINITY;
+          const float bl = (key < N && q < N) ? mul_rn(bias[((size_t)h * N + q) * ldb + key], LOG2E) : 0.f;
+          v[kj] = (key < N) ? fmaf(s[kj][r], sc, bl) : -INFINITY;
         } else {
           v[kj] = (key < N) ? s[kj][r] * sc : -INFINITY;
         }
@@ -119,13 +201,7 @@ __global__ __launch_bounds__(256) void gattn_fwd_kernel(const bf16* __restrict__
       for (int dj = 0; dj < 4; ++dj) o[dj][r] *= alpha;
     }
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const bf16x8 pf = lds8(ps[wv] + l15 * PT + 32 * t + 8 * g);
-#pragma unroll
-      for (int dj = 0; dj < 4; ++dj)
-        o[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, lds8(vt + (dj * 16 + l15) * PT + 32 * t + 8 * g), o[dj], 0, 0, 0);
-    }
+    rows_x_tile_t(ps[wv], vt, l15, g, o);
   }
   // o[dj][r]: query q0 + 4g + r, dim 16 dj + l15
 #pragma unroll
@@ -180,18 +256,11 @@ __global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__
   const float* lrow = lse + ((size_t)b * H + h) * N;
   const float* drow = delta + ((size_t)b * H + h) * N;
   bf16x8 kf[2], vf[2];
-  {
-    const int kr = k0 + l15;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      kf[t] = kr < N ? ldg16(base + (size_t)kr * ldq + C + h * HD + 32 * t + 8 * g) : zero8();
-      vf[t] = kr < N ? ldg16(base + (size_t)kr * ldq + 2 * C + h * HD + 32 * t + 8 * g) : zero8();
-    }
-  }
+  load_rows16(base, ldq, C + h * HD, k0, N, l15, g, kf);
+  load_rows16(base, ldq, 2 * C + h * HD, k0, N, l15, g, vf);
   f32x4 dk[4], dv[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) dk[j] = dv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float sc = SCALE * LOG2E;
   for (int q0 = 0; q0 < N; q0 += TL) {
     __syncthreads();
     stage_tile(base, ldq, h * HD, q0, N, qs, qt);
@@ -203,15 +272,12 @@ __global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__
     }
     __syncthreads();
     f32x4 st[4], dpt[4];
-#pragma unroll
-    for (int qj = 0; qj < 4; ++qj) {
-      st[qj] = dpt[qj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        st[qj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t], lds8(qs + (qj * 16 + l15) * PT + 32 * t + 8 * g), st[qj], 0, 0, 0);
-        dpt[qj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[t], lds8(dos + (qj * 16 + l15) * PT + 32 * t + 8 * g), dpt[qj], 0, 0, 0);
-      }
-    }
+    frag_x_tile(kf, qs, l15, g, st);
+    frag_x_tile(vf, dos, l15, g, dpt);
+    // S^T and dP^T leave the accumulator file here, in one go: without it hipcc schedules a v_accvgpr_read of the next element
+    // onto the data register of a ds_write_b16 of P^T still in flight (tools/isa_lint.py; the note at the delta reduction of
+    // attn_bwd_mfma_kernel in transformer.hip)
+    asm volatile("" : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(dpt[0]), "+v"(dpt[1]), "+v"(dpt[2]), "+v"(dpt[3]));
     // element (qj, r): key k0 + 4g + r, query q0 + 16 qj + l15
     float dsv[4][4];
 #pragma unroll
@@ -226,37 +292,25 @@ __global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__
           const float4 b4 = *reinterpret_cast<const float4*>(bias + ((size_t)h * N + q) * ldb + kb);
           const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-          for (int r = 0; r < 4; ++r) lqb[r] = kb + r < N ? lq - bv[r] * LOG2E : lq;
+          for (int r = 0; r < 4; ++r) lqb[r] = kb + r < N ? fmaf(-bv[r], LOG2E, lq) : lq;
         }
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = exp2f(st[qj][r] * sc - (BIAS ? lqb[r] : lq));
+        const float p = prob(st[qj][r], lqb[r]);
         ws[wv][(4 * g + r) * PT + ql] = f2bf(p);
         dsv[qj][r] = p * (dpt[qj][r] - dq);
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const bf16x8 pf = lds8(ws[wv] + l15 * PT + 32 * t + 8 * g);
-#pragma unroll
-      for (int dj = 0; dj < 4; ++dj)
-        dv[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, lds8(dot + (dj * 16 + l15) * PT + 32 * t + 8 * g), dv[dj], 0, 0, 0);
-    }
+    rows_x_tile_t(ws[wv], dot, l15, g, dv);
     __syncthreads();
 #pragma unroll
     for (int qj = 0; qj < 4; ++qj)
 #pragma unroll
       for (int r = 0; r < 4; ++r) ws[wv][(4 * g + r) * PT + qj * 16 + l15] = f2bf(dsv[qj][r]);
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const bf16x8 sf = lds8(ws[wv] + l15 * PT + 32 * t + 8 * g);
-#pragma unroll
-      for (int dj = 0; dj < 4; ++dj)
-        dk[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, lds8(qt + (dj * 16 + l15) * PT + 32 * t + 8 * g), dk[dj], 0, 0, 0);
-    }
+    rows_x_tile_t(ws[wv], qt, l15, g, dk);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -285,67 +339,34 @@ __global__ __launch_bounds__(256) void gattn_dq_kernel(const bf16* __restrict__ 
   const int b = blockIdx.y / H, h = blockIdx.y % H, C = H * HD;
   const int q0 = blockIdx.x * TL + wv * 16;
   const bf16* base = qkv + (size_t)b * N * ldq;
-  const float* lrow = lse + ((size_t)b * H + h) * N;
-  const float* drow = delta + ((size_t)b * H + h) * N;
   bf16x8 qf[2], df[2];
-  {
-    const int qr = q0 + l15;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      qf[t] = qr < N ? ldg16(base + (size_t)qr * ldq + h * HD + 32 * t + 8 * g) : zero8();
-      df[t] = qr < N ? ldg16(dout + ((size_t)b * N + qr) * ldo + h * HD + 32 * t + 8 * g) : zero8();
-    }
-  }
+  load_rows16(base, ldq, h * HD, q0, N, l15, g, qf);
+  load_rows16(dout + (size_t)b * N * ldo, ldo, h * HD, q0, N, l15, g, df);
   float lr[4], dr[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int q = q0 + 4 * g + r;
-    lr[r] = q < N ? lrow[q] * LOG2E : INFINITY;
-    dr[r] = q < N ? drow[q] : 0.f;
-  }
+  load_row_stats(lse + ((size_t)b * H + h) * N, delta + ((size_t)b * H + h) * N, q0 + 4 * g, N, lr, dr);
   f32x4 dq[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) dq[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float sc = SCALE * LOG2E;
   for (int k0 = 0; k0 < N; k0 += TL) {
     __syncthreads();
     stage_tile(base, ldq, C + h * HD, k0, N, ks, kt);
     stage_tile(base, ldq, 2 * C + h * HD, k0, N, vs, nullptr);
     __syncthreads();
     f32x4 s[4], dp[4];
-#pragma unroll
-    for (int kj = 0; kj < 4; ++kj) {
-      s[kj] = dp[kj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        s[kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t], lds8(ks + (kj * 16 + l15) * PT + 32 * t + 8 * g), s[kj], 0, 0, 0);
-        dp[kj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[t], lds8(vs + (kj * 16 + l15) * PT + 32 * t + 8 * g), dp[kj], 0, 0, 0);
-      }
-    }
+    frag_x_tile(qf, ks, l15, g, s);
+    frag_x_tile(df, vs, l15, g, dp);
     // element (kj, r): query q0 + 4g + r, key k0 + 16 kj + l15
-#pragma unroll
-    for (int kj = 0; kj < 4; ++kj) {
-      const int key = k0 + kj * 16 + l15;
-      const bool live = key < N;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float lb = lr[r];
-        if constexpr (BIAS) {
-          const int q = q0 + 4 * g + r;
-          if (live && q < N) lb = lr[r] - bias[((size_t)h * N + q) * ldb + key] * LOG2E;
-        }
-        const float p = live ? exp2f(s[kj][r] * sc - lb) : 0.f;
-        ws[wv][(4 * g + r) * PT + kj * 16 + l15] = f2bf(p * (dp[kj][r] - dr[r]));
-      }
-    }
+    ds_tile(s, dp, dr, k0, N, l15,
+            [&](int kj, int r, bool live) {
+              if constexpr (BIAS) {
+                const int q = q0 + 4 * g + r;
+                if (live && q < N) return fmaf(-bias[((size_t)h * N + q) * ldb + k0 + kj * 16 + l15], LOG2E, lr[r]);
+              }
+              return lr[r];
+            },
+            [&](int kj, int r, float p, float d) { ws[wv][(4 * g + r) * PT + kj * 16 + l15] = f2bf(p * d); });
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const bf16x8 sf = lds8(ws[wv] + l15 * PT + 32 * t + 8 * g);
-#pragma unroll
-      for (int dj = 0; dj < 4; ++dj)
-        dq[dj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, lds8(kt + (dj * 16 + l15) * PT + 32 * t + 8 * g), dq[dj], 0, 0, 0);
-    }
+    rows_x_tile_t(ws[wv], kt, l15, g, dq);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -378,51 +399,27 @@ __global__ __launch_bounds__(256) void gattn_dbias_kernel(const bf16* __restrict
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = q0 + 4 * g + r, key = k0 + kj * 16 + l15;
-      bl[kj][r] = (q < N && key < N) ? bias[((size_t)h * N + q) * ldb + key] * LOG2E : 0.f;
+      bl[kj][r] = (q < N && key < N) ? mul_rn(bias[((size_t)h * N + q) * ldb + key], LOG2E) : 0.f;
     }
   f32x4 acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const float sc = SCALE * LOG2E;
   for (int b = b_lo; b < b_hi; ++b) {
     const bf16* base = qkv + (size_t)b * N * ldq;
-    const float* lrow = lse + ((size_t)b * H + h) * N;
-    const float* drow = delta + ((size_t)b * H + h) * N;
     __syncthreads();                                    // the previous image's tiles have been consumed by every wave
     stage_tile(base, ldq, C + h * HD, k0, N, ks, nullptr);
     stage_tile(base, ldq, 2 * C + h * HD, k0, N, vs, nullptr);
     bf16x8 qf[2], df[2];
-    {
-      const int qr = q0 + l15;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        qf[t] = qr < N ? ldg16(base + (size_t)qr * ldq + h * HD + 32 * t + 8 * g) : zero8();
-        df[t] = qr < N ? ldg16(dout + ((size_t)b * N + qr) * ldo + h * HD + 32 * t + 8 * g) : zero8();
-      }
-    }
+    load_rows16(base, ldq, h * HD, q0, N, l15, g, qf);
+    load_rows16(dout + (size_t)b * N * ldo, ldo, h * HD, q0, N, l15, g, df);
     float lr[4], dr[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + 4 * g + r;
-      lr[r] = q < N ? lrow[q] * LOG2E : INFINITY;
-      dr[r] = q < N ? drow[q] : 0.f;
-    }
+    load_row_stats(lse + ((size_t)b * H + h) * N, delta + ((size_t)b * H + h) * N, q0 + 4 * g, N, lr, dr);
     __syncthreads();
-#pragma unroll
-    for (int kj = 0; kj < 4; ++kj) {
-      f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f}, dp = s;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[t], lds8(ks + (kj * 16 + l15) * PT + 32 * t + 8 * g), s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[t], lds8(vs + (kj * 16 + l15) * PT + 32 * t + 8 * g), dp, 0, 0, 0);
-      }
-      const bool live = k0 + kj * 16 + l15 < N;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = live ? exp2f(s[r] * sc - (lr[r] - bl[kj][r])) : 0.f;
-        acc[kj][r] += p * (dp[r] - dr[r]);
-      }
-    }
+    f32x4 s[4], dp[4];
+    frag_x_tile(qf, ks, l15, g, s);
+    frag_x_tile(df, vs, l15, g, dp);
+    ds_tile(s, dp, dr, k0, N, l15, [&](int kj, int r, bool) { return sub_rn(lr[r], bl[kj][r]); },
+            [&](int kj, int r, float p, float d) { acc[kj][r] = fmaf(p, d, acc[kj][r]); });
   }
   float* dst = part + (size_t)blockIdx.z * H * N * ldb;
 #pragma unroll
@@ -552,68 +549,61 @@ __global__ __launch_bounds__(256) void rows_select_kernel(const bf16* __restrict
 
 unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-}  // namespace
-
-#define GA_CHECK_GEO(who)                                                                                                   \
-  TOK_CHECK_ARG(head_dim == HD, "%s: head_dim %d is not served (64 only)", who, head_dim);                                  \
-  TOK_CHECK_ARG(batch > 0 && heads > 0 && n >= 1 && n <= TOK_GLOBAL_ATTN_MAX_TOKENS, "%s: %d tokens (1 ... %d served)", who, \
-                n, TOK_GLOBAL_ATTN_MAX_TOKENS);                                                                              \
-  TOK_CHECK_ARG(ldq >= 3 * heads * HD && ldq % 8 == 0 && ldo >= heads * HD && ldo % 8 == 0,                                 \
-                "%s: row pitches ldq %d / ldo %d (>= 3C / C, multiples of 8)", who, ldq, ldo);                               \
-  TOK_CHECK_ARG((size_t)batch * heads <= 65535u, "%s: batch * heads %d > 65535", who, batch * heads)
-
-extern "C" int tok_global_attn_fwd(const void* qkv, int ldq, int batch, int n, int heads, int head_dim, void* out, int ldo,
-                                   float* lse, void* stream) {
-  GA_CHECK_GEO("tok_global_attn_fwd");
-  TOK_CHECK_ARG(qkv && out && lse, "tok_global_attn_fwd: null pointer");
-  hipLaunchKernelGGL(gattn_fwd_kernel<false>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)qkv, ldq, n, heads, (bf16*)out, ldo, lse, (const float*)nullptr, 0);
-  TOK_CHECK_LAUNCH("tok_global_attn_fwd");
+// the geometry every attention entry point serves; `who` opens each refusal
+int check_geo(const char* who, int ldq, int batch, int n, int heads, int head_dim, int ldo) {
+  TOK_CHECK_ARG(head_dim == HD, "%s: head_dim %d is not served (64 only)", who, head_dim);
+  TOK_CHECK_ARG(batch > 0 && heads > 0 && n >= 1 && n <= TOK_GLOBAL_ATTN_MAX_TOKENS, "%s: %d tokens (1 ... %d served)", who, n,
+                TOK_GLOBAL_ATTN_MAX_TOKENS);
+  TOK_CHECK_ARG(ldq >= 3 * heads * HD && ldq % 8 == 0 && ldo >= heads * HD && ldo % 8 == 0,
+                "%s: row pitches ldq %d / ldo %d (>= 3C / C, multiples of 8)", who, ldq, ldo);
+  TOK_CHECK_ARG((size_t)batch * heads <= 65535u, "%s: batch * heads %d > 65535", who, batch * heads);
   return TOK_OK;
 }
 
-#define GA_CHECK_BIAS(who)                                                                                                    \
-  TOK_CHECK_ARG(bias && ldb >= n && ldb % 4 == 0 && ((uintptr_t)bias & 15) == 0,                                            \
-                "%s: bias pointer / row pitch ldb %d (16-byte aligned, >= n, a multiple of 4)", who, ldb)
+int check_bias(const char* who, const float* bias, int ldb, int n) {
+  TOK_CHECK_ARG(bias && ldb >= n && ldb % 4 == 0 && ((uintptr_t)bias & 15) == 0,
+                "%s: bias pointer / row pitch ldb %d (16-byte aligned, >= n, a multiple of 4)", who, ldb);
+  return TOK_OK;
+}
+
+// TOK_CHECK_LAUNCH for the launch "<who><stage>"
+int launched(const char* who, const char* stage) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return TOK_OK;
+  tok_set_error("%s%s: launch failed: %s", who, stage, hipGetErrorString(e));
+  return TOK_ERR_LAUNCH;
+}
+
+// bias == nullptr: the un-biased kernel
+int launch_fwd(const char* who, const void* qkv, int ldq, const float* bias, int ldb, int batch, int n, int heads, void* out,
+               int ldo, float* lse, void* stream) {
+  hipLaunchKernelGGL(bias ? gattn_fwd_kernel<true> : gattn_fwd_kernel<false>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0,
+                     tok_stream(stream), (const bf16*)qkv, ldq, n, heads, (bf16*)out, ldo, lse, bias, ldb);
+  return launched(who, "");
+}
+
+}  // namespace
+
+extern "C" int tok_global_attn_fwd(const void* qkv, int ldq, int batch, int n, int heads, int head_dim, void* out, int ldo,
+                                   float* lse, void* stream) {
+  const char* who = "tok_global_attn_fwd";
+  if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
+  TOK_CHECK_ARG(qkv && out && lse, "%s: null pointer", who);
+  return launch_fwd(who, qkv, ldq, nullptr, 0, batch, n, heads, out, ldo, lse, stream);
+}
 
 extern "C" int tok_global_attn_bias_fwd(const void* qkv, int ldq, const float* bias, int ldb, int batch, int n, int heads,
                                         int head_dim, void* out, int ldo, float* lse, void* stream) {
-  GA_CHECK_GEO("tok_global_attn_bias_fwd");
-  TOK_CHECK_ARG(qkv && out && lse, "tok_global_attn_bias_fwd: null pointer");
-  GA_CHECK_BIAS("tok_global_attn_bias_fwd");
-  hipLaunchKernelGGL(gattn_fwd_kernel<true>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)qkv, ldq, n, heads, (bf16*)out, ldo, lse, bias, ldb);
-  TOK_CHECK_LAUNCH("tok_global_attn_bias_fwd");
-  return TOK_OK;
+  const char* who = "tok_global_attn_bias_fwd";
+  if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
+  TOK_CHECK_ARG(qkv && out && lse, "%s: null pointer", who);
+  if (int rc = check_bias(who, bias, ldb, n)) return rc;
+  return launch_fwd(who, qkv, ldq, bias, ldb, batch, n, heads, out, ldo, lse, stream);
 }
 
 extern "C" size_t tok_global_attn_bwd_ws_bytes(int batch, int n, int heads) {
   if (batch <= 0 || n <= 0 || heads <= 0) return 0;
   return ((size_t)batch * heads * n * sizeof(float) + 255) / 256 * 256;
-}
-
-extern "C" int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
-                                   int batch, int n, int heads, int head_dim, void* dqkv, int ldd, void* ws, size_t ws_bytes,
-                                   void* stream) {
-  GA_CHECK_GEO("tok_global_attn_bwd");
-  TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "tok_global_attn_bwd: null pointer");
-  TOK_CHECK_ARG(ldd >= 3 * heads * HD && ldd % 8 == 0, "tok_global_attn_bwd: ldd %d", ldd);
-  if (ws_bytes < tok_global_attn_bwd_ws_bytes(batch, n, heads)) {
-    tok_set_error("tok_global_attn_bwd: workspace %zu < %zu bytes", ws_bytes, tok_global_attn_bwd_ws_bytes(batch, n, heads));
-    return TOK_ERR_WORKSPACE;
-  }
-  hipStream_t st = tok_stream(stream);
-  float* delta = (float*)ws;
-  hipLaunchKernelGGL(gattn_delta_kernel, dim3(blocks_of((int64_t)batch * n * heads)), dim3(256), 0, st, (const bf16*)out,
-                     (const bf16*)dout, ldo, batch, n, heads, delta);
-  TOK_CHECK_LAUNCH("tok_global_attn_bwd(delta)");
-  hipLaunchKernelGGL(gattn_dkv_kernel<false>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
-                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, (const float*)nullptr, 0);
-  TOK_CHECK_LAUNCH("tok_global_attn_bwd(dkv)");
-  hipLaunchKernelGGL(gattn_dq_kernel<false>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
-                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, (const float*)nullptr, 0);
-  TOK_CHECK_LAUNCH("tok_global_attn_bwd(dq)");
-  return TOK_OK;
 }
 
 // images per d(bias) chunk: enough (tile, head, chunk) workgroups for eight per CU of the 256 where the batch allows it
@@ -637,40 +627,60 @@ extern "C" size_t tok_global_attn_bias_bwd_ws_bytes(int batch, int n, int heads,
          (size_t)tok_global_attn_bias_bwd_chunks(batch, n, heads) * heads * n * ldb * sizeof(float);
 }
 
-extern "C" int tok_global_attn_bias_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
-                                        const float* bias, int ldb, int batch, int n, int heads, int head_dim, void* dqkv,
-                                        int ldd, float* dbias, int dbias_accumulate, void* ws, size_t ws_bytes, void* stream) {
-  GA_CHECK_GEO("tok_global_attn_bias_bwd");
-  TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "tok_global_attn_bias_bwd: null pointer");
-  GA_CHECK_BIAS("tok_global_attn_bias_bwd");
-  TOK_CHECK_ARG(ldd >= 3 * heads * HD && ldd % 8 == 0, "tok_global_attn_bias_bwd: ldd %d", ldd);
+// delta, dK / dV, dQ, then with dbias the chunk partials and their fold.  bias == nullptr: the un-biased kernels (dbias is null
+// then).  The workspace is [delta | partials].
+static int launch_bwd(const char* who, const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
+                      const float* bias, int ldb, int batch, int n, int heads, void* dqkv, int ldd, float* dbias, int accumulate,
+                      void* ws, size_t ws_bytes, void* stream) {
   // without dbias only delta lives in the workspace: a frozen table pays for no chunk partials
   const size_t ws_need = dbias ? tok_global_attn_bias_bwd_ws_bytes(batch, n, heads, ldb) : tok_global_attn_bwd_ws_bytes(batch, n, heads);
   if (ws_bytes < ws_need) {
-    tok_set_error("tok_global_attn_bias_bwd: workspace %zu < %zu bytes", ws_bytes, ws_need);
+    tok_set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, ws_need);
     return TOK_ERR_WORKSPACE;
   }
   hipStream_t st = tok_stream(stream);
-  float* delta = (float*)ws;
-  float* part = (float*)((char*)ws + tok_global_attn_bwd_ws_bytes(batch, n, heads));
+  const float* delta = (const float*)ws;
+  const dim3 tiles(tok_cdiv(n, TL), batch * heads);
   hipLaunchKernelGGL(gattn_delta_kernel, dim3(blocks_of((int64_t)batch * n * heads)), dim3(256), 0, st, (const bf16*)out,
-                     (const bf16*)dout, ldo, batch, n, heads, delta);
-  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(delta)");
-  hipLaunchKernelGGL(gattn_dkv_kernel<true>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
-                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, bias, ldb);
-  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(dkv)");
-  hipLaunchKernelGGL(gattn_dq_kernel<true>, dim3(tok_cdiv(n, TL), batch * heads), dim3(256), 0, st, (const bf16*)qkv, ldq,
-                     (const bf16*)dout, ldo, lse, (const float*)delta, n, heads, (bf16*)dqkv, ldd, bias, ldb);
-  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(dq)");
+                     (const bf16*)dout, ldo, batch, n, heads, (float*)ws);
+  if (int rc = launched(who, "(delta)")) return rc;
+  hipLaunchKernelGGL(bias ? gattn_dkv_kernel<true> : gattn_dkv_kernel<false>, tiles, dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, delta, n, heads, (bf16*)dqkv, ldd, bias, ldb);
+  if (int rc = launched(who, "(dkv)")) return rc;
+  hipLaunchKernelGGL(bias ? gattn_dq_kernel<true> : gattn_dq_kernel<false>, tiles, dim3(256), 0, st, (const bf16*)qkv, ldq,
+                     (const bf16*)dout, ldo, lse, delta, n, heads, (bf16*)dqkv, ldd, bias, ldb);
+  if (int rc = launched(who, "(dq)")) return rc;
   if (!dbias) return TOK_OK;
+  float* part = (float*)((char*)ws + tok_global_attn_bwd_ws_bytes(batch, n, heads));
   const int per = dbias_per_chunk(batch, n, heads), chunks = tok_cdiv(batch, per), nt = tok_cdiv(n, TL);
   hipLaunchKernelGGL(gattn_dbias_kernel, dim3(nt * nt, heads, chunks), dim3(256), 0, st, (const bf16*)qkv, ldq, (const bf16*)dout,
-                     ldo, lse, (const float*)delta, bias, ldb, batch, n, heads, per, part);
-  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(dbias)");
+                     ldo, lse, delta, bias, ldb, batch, n, heads, per, part);
+  if (int rc = launched(who, "(dbias)")) return rc;
   hipLaunchKernelGGL(gattn_dbias_fold_kernel, dim3(blocks_of((int64_t)heads * n * n)), dim3(256), 0, st, (const float*)part,
-                     chunks, heads, n, ldb, dbias, dbias_accumulate ? 1 : 0);
-  TOK_CHECK_LAUNCH("tok_global_attn_bias_bwd(fold)");
-  return TOK_OK;
+                     chunks, heads, n, ldb, dbias, accumulate ? 1 : 0);
+  return launched(who, "(fold)");
+}
+
+extern "C" int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
+                                   int batch, int n, int heads, int head_dim, void* dqkv, int ldd, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  const char* who = "tok_global_attn_bwd";
+  if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
+  TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "%s: null pointer", who);
+  TOK_CHECK_ARG(ldd >= 3 * heads * HD && ldd % 8 == 0, "%s: ldd %d", who, ldd);
+  return launch_bwd(who, qkv, ldq, out, dout, ldo, lse, nullptr, 0, batch, n, heads, dqkv, ldd, nullptr, 0, ws, ws_bytes, stream);
+}
+
+extern "C" int tok_global_attn_bias_bwd(const void* qkv, int ldq, const void* out, const void* dout, int ldo, const float* lse,
+                                        const float* bias, int ldb, int batch, int n, int heads, int head_dim, void* dqkv,
+                                        int ldd, float* dbias, int dbias_accumulate, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "tok_global_attn_bias_bwd";
+  if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
+  TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "%s: null pointer", who);
+  if (int rc = check_bias(who, bias, ldb, n)) return rc;
+  TOK_CHECK_ARG(ldd >= 3 * heads * HD && ldd % 8 == 0, "%s: ldd %d", who, ldd);
+  return launch_bwd(who, qkv, ldq, out, dout, ldo, lse, bias, ldb, batch, n, heads, dqkv, ldd, dbias, dbias_accumulate, ws, ws_bytes,
+                    stream);
 }
 
 extern "C" int tok_patch_gather(const void* img, int n, int h, int w, int p, void* rows, void* stream) {

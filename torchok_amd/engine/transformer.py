@@ -715,22 +715,19 @@ class _GlobalAttnNode(Node):
         if acc:
             raise RuntimeError('global_attention: qkv has a single consumer')
         bn = self.bias_node
-        if bn is None:
-            ws_bytes = int(lib.tok_global_attn_bwd_ws_bytes(b, n, heads))
-            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-            _C.check(lib.tok_global_attn_bwd(ptr(qkv.data), qkv.cp, ptr(o.data), ptr(g), o.cp, ptr(self.lse), b, n, heads, 64,
-                                             ptr(tgt), qkv.cp, ptr(ws), ws_bytes, st), 'tok_global_attn_bwd')
-        else:
+        what, dbias, bias_args, dbias_args = 'tok_global_attn_bwd', None, (), ()
+        if bn is not None:
             bias = bn.gather()             # gathered again: no block keeps its [heads][N][N] bias across the step
             ldb = bias.shape[-1]
             dbias = torch.empty_like(bias) if bn.table.requires_grad else None
-            # a frozen table needs delta only, not the chunk partials of d(bias)
-            ws_bytes = int(lib.tok_global_attn_bias_bwd_ws_bytes(b, n, heads, ldb) if dbias is not None
-                           else lib.tok_global_attn_bwd_ws_bytes(b, n, heads))
-            ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
-            _C.check(lib.tok_global_attn_bias_bwd(ptr(qkv.data), qkv.cp, ptr(o.data), ptr(g), o.cp, ptr(self.lse), ptr(bias), ldb,
-                                                  b, n, heads, 64, ptr(tgt), qkv.cp, ptr(dbias), 0, ptr(ws), ws_bytes, st),
-                     'tok_global_attn_bias_bwd')
+            what, bias_args, dbias_args = 'tok_global_attn_bias_bwd', (ptr(bias), ldb), (ptr(dbias), 0)
+        # a frozen table needs delta only, not the chunk partials of d(bias)
+        ws_bytes = int(lib.tok_global_attn_bwd_ws_bytes(b, n, heads) if dbias is None
+                       else lib.tok_global_attn_bias_bwd_ws_bytes(b, n, heads, ldb))
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
+        _C.check(getattr(lib, what)(ptr(qkv.data), qkv.cp, ptr(o.data), ptr(g), o.cp, ptr(self.lse), *bias_args, b, n, heads, 64,
+                                    ptr(tgt), qkv.cp, *dbias_args, ptr(ws), ws_bytes, st), what)
+        if bn is not None:
             bn.dbias = dbias
         c = heads * 64
         if qkv.cp != 3 * c:
@@ -809,16 +806,14 @@ def global_attention(region: Region, qkv: TTensor, batch: int, tokens: int, head
     dev = qkv.data.device
     out_data = torch.empty((batch * tokens, c), dtype=BF16, device=dev)
     lse = torch.empty((batch, heads, tokens), dtype=F32, device=dev)
-    if bias is None:
-        what = 'tok_global_attn_fwd'
-        rc = lib.tok_global_attn_fwd(ptr(qkv.data), qkv.cp, batch, tokens, heads, head_dim, ptr(out_data), c, ptr(lse), st)
-    else:
+    what, bias_args = 'tok_global_attn_fwd', ()
+    if bias is not None:
         what = 'tok_global_attn_bias_fwd'
-        bias_data, bias_node = bias
+        bias_data = bias[0]
         if tuple(bias_data.shape[:2]) != (heads, tokens):
             raise ValueError(f'global_attention: bias {tuple(bias_data.shape)} for {heads} heads, {tokens} tokens')
-        rc = lib.tok_global_attn_bias_fwd(ptr(qkv.data), qkv.cp, ptr(bias_data), bias_data.shape[-1], batch, tokens, heads,
-                                          head_dim, ptr(out_data), c, ptr(lse), st)
+        bias_args = (ptr(bias_data), bias_data.shape[-1])
+    rc = getattr(lib, what)(ptr(qkv.data), qkv.cp, *bias_args, batch, tokens, heads, head_dim, ptr(out_data), c, ptr(lse), st)
     if rc != 0 and head_dim != 64:
         raise NotImplementedError(f'global_attention: head_dim {head_dim} (64 only)')
     _C.check(rc, what)
