@@ -457,6 +457,18 @@ int tok_bilinear_fwd(const void* src, int n, int hs, int ws, int c, int ld_src, 
                      int wd, int ld_dst, int ch_off, void* stream);
 int tok_bilinear_bwd(const void* ddst, int n, int hd, int wd, int ld_dst, int ch_off, void* dsrc,
                      int hs, int ws, int c, int ld_src, int accumulate, void* stream);
+/* F.interpolate(mode='nearest') (necks/segmentation/unet.py: the decoder's scale_factor=2 upsample and the resize of a skip
+ * whose height differs) with the same slice addressing and argument order as tok_bilinear_*: dst[n][y][x][ch_off + k] =
+ * src[n][iy(y)][ix(x)][k], k < c, iy(y) = min((int)floorf(y * ((float)hs / (float)hd)), hs - 1) (ATen's source index), a
+ * copy bit for bit; every other element of dst is left alone.  Backward = exact transpose, gather form: each dsrc element is
+ * the fp32 sum, in row-major order of dst, of the ddst elements that map to it (starting from the old dsrc when
+ * `accumulate`), rounded once; a source no destination maps to (hd < hs) gets 0 without `accumulate`; channels [c, ld_src)
+ * of dsrc are not written.  16 bytes per lane when c, ch_off, ld_src and ld_dst are multiples of 8, one element per lane
+ * otherwise; 64-bit element offsets.                                                                                     */
+int tok_nearest_fwd(const void* src, int n, int hs, int ws, int c, int ld_src, void* dst, int hd,
+                    int wd, int ld_dst, int ch_off, void* stream);
+int tok_nearest_bwd(const void* ddst, int n, int hd, int wd, int ld_dst, int ch_off, void* dsrc,
+                    int hs, int ws, int c, int ld_src, int accumulate, void* stream);
 /* y = y0 + sum_j bilinear(t_j -> h x w) (align_corners=False as above; t_j NULL = absent), every map [..][c] bf16 with row
  * pitch c, summed in fp32 and rounded once; y may be y0.  stats (nullable): float[2][tok_bilinear_sum_stats_rows(n, h, w, c)][c]
  * per-channel partial (sum, sum of squares) of the rounded y, the rows tok_bn_finalize folds.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Fold the parity distances the -m gpu tests measured (tests/helpers.py: record_distance, JSON lines under gpurun_out/)
 into the committed record:   python tools/parity_record.py gpurun_out/parity_distances.jsonl profiles/r03_parity_distances.json
+(a third argument: keep only the tests whose name starts with one of these comma-separated prefixes; `source` says so)
 
 Per test: every tensor with its relative-L2 distances (HIP vs the bf16-autocast oracle, HIP vs the fp32 oracle, the
 autocast oracle vs the fp32 oracle = what bf16 storage itself costs), plus medians / maxima; at the top, the largest
@@ -19,6 +20,7 @@ from collections import OrderedDict
 
 def main():
     src, dst = sys.argv[1], sys.argv[2]
+    keep = tuple(sys.argv[3].split(',')) if len(sys.argv) > 3 else ()
     tests = OrderedDict()
     with open(src) as f:
         for line in f:
@@ -27,6 +29,8 @@ def main():
                 continue
             r = json.loads(line)
             t = r.pop('test')
+            if keep and not t.startswith(keep):
+                continue
             tests.setdefault(t, OrderedDict())[r.pop('tensor')] = r      # a re-run of a test overwrites its tensors
     out = OrderedDict()
     unit_worst = (0.0, None)
@@ -78,6 +82,12 @@ def main():
                'tests': out}
     elif bound_worst[1] is not None:
         doc['largest_err_over_bound'] = bounded
+    if keep:
+        doc['source'] += '; only the tests whose name starts with ' + ' / '.join(keep)
+        if unit_worst[1] is None:
+            doc.pop('largest_unit_hip_vs_autocast', None)        # these two describe units/ tests only
+        if real_worst[1] is None:
+            doc.pop('largest_real_width_unit_hip_over_autocast_distance_to_fp32', None)
     with open(dst, 'w') as f:
         json.dump(doc, f, indent=1)
     print(f'{dst}: {len(out)} tests, {sum(len(v["per_tensor"]) for v in out.values())} tensors; '

@@ -9,6 +9,8 @@ bilinear_concat      F.interpolate(bilinear, align_corners=False) x3 + torch.cat
                      channel slice of the concat buffer
 bilinear_resize      F.interpolate(segm_logits, size=input.shape[2:], mode='bilinear')
                      (heads/segmentation/base.py:37)
+nearest_concat       F.interpolate(x, scale_factor=2, mode='nearest'), F.interpolate(skip, size, mode='nearest') +
+                     torch.cat (necks/segmentation/unet.py:47-53): the twin of bilinear_concat on tok_nearest_*
 """
 from typing import List, Sequence, Tuple
 
@@ -88,6 +90,7 @@ def fuse_sum_relu(region: Region, terms: Sequence[Tuple[TTensor, int]], relu: bo
 
 class _BilinearNode(Node):
     needs_backward = True
+    bwd = 'tok_bilinear_bwd'
 
     def backward(self):
         g = self.out.grad
@@ -102,8 +105,7 @@ class _BilinearNode(Node):
                 tgt, acc = grad_target(t)
                 if cw != cp and not acc:
                     tgt.zero_()           # padding channels of a fresh gradient buffer
-                _C.check(lib.tok_bilinear_bwd(ptr(g), n, hd, wd, ld, off, ptr(tgt), hs, ws, cw, cp, acc, st),
-                         'tok_bilinear_bwd')
+                _C.check(getattr(lib, self.bwd)(ptr(g), n, hd, wd, ld, off, ptr(tgt), hs, ws, cw, cp, acc, st), self.bwd)
             off += cw
         self.out.grad = None
 
@@ -111,8 +113,11 @@ class _BilinearNode(Node):
         self.srcs = self.out = self.widths = None
 
 
-def bilinear_concat(region: Region, srcs: List[TTensor], size: Tuple[int, int]) -> TTensor:
-    """cat([interpolate(s, size, 'bilinear', align_corners=False) for s in srcs], dim=channel)."""
+class _NearestNode(_BilinearNode):
+    bwd = 'tok_nearest_bwd'
+
+
+def _resample_concat(region: Region, srcs: List[TTensor], size: Tuple[int, int], fwd: str, node_cls) -> TTensor:
     await_ready(*srcs)
     n = srcs[0].shape[0]
     hd, wd = int(size[0]), int(size[1])
@@ -127,13 +132,12 @@ def bilinear_concat(region: Region, srcs: List[TTensor], size: Tuple[int, int]) 
     off = 0
     for t, cw in zip(srcs, widths):
         _, hs, ws, cp = t.shape
-        _C.check(lib.tok_bilinear_fwd(ptr(t.data), n, hs, ws, cw, cp, ptr(out_data), hd, wd, ld, off, st),
-                 'tok_bilinear_fwd')
+        _C.check(getattr(lib, fwd)(ptr(t.data), n, hs, ws, cw, cp, ptr(out_data), hd, wd, ld, off, st), fwd)
         off += cw
     req = region.grad_mode and any(t.requires_grad for t in srcs)
     out = TTensor(out_data, sum(t.c for t in srcs), requires_grad=req)
     if req:
-        node = _BilinearNode()
+        node = node_cls()
         node.srcs, node.out, node.widths = list(srcs), out, widths
         out.node = node
         for t in srcs:
@@ -141,6 +145,17 @@ def bilinear_concat(region: Region, srcs: List[TTensor], size: Tuple[int, int]) 
                 t.uses += 1
         region.add(node)
     return out
+
+
+def bilinear_concat(region: Region, srcs: List[TTensor], size: Tuple[int, int]) -> TTensor:
+    """cat([interpolate(s, size, 'bilinear', align_corners=False) for s in srcs], dim=channel)."""
+    return _resample_concat(region, srcs, size, 'tok_bilinear_fwd', _BilinearNode)
+
+
+def nearest_concat(region: Region, srcs: List[TTensor], size: Tuple[int, int]) -> TTensor:
+    """cat([interpolate(s, size, 'nearest') for s in srcs], dim=channel); sources may differ in size (the U-Net decoder's
+    upsampled map and its skip)."""
+    return _resample_concat(region, srcs, size, 'tok_nearest_fwd', _NearestNode)
 
 
 def bilinear_resize(region: Region, x: TTensor, size: Tuple[int, int]) -> TTensor:
