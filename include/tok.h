@@ -388,7 +388,10 @@ int tok_regression_loss_bwd(const void* x, const float* target, const float* gsc
 /* On-device classification statistics behind the Accuracy / F1Score metrics the reference configs log every step
  * (metrics/metrics_manager.py:147-158, classification_cifar10.yaml:134-150; torchmetrics itself is third-party):
  * counts int64 [3][classes] += {true positives, predicted, actual} per class.  Predictions are bf16 logits
- * [rows][ld] (first maximum, as torch.argmax) or int64 labels; rows whose target is ignore_index are skipped.   */
+ * [rows][ld] (first maximum, as torch.argmax: a row of equal logits, a row of -inf included, predicts class 0) or int64
+ * labels; rows whose target is ignore_index or outside [0, classes) are skipped, a predicted label outside [0, classes)
+ * is in no column but its row still counts as actual.  A NaN logit is outside the contract: torch.argmax returns the
+ * NaN's column, the kernel's comparisons skip it.                                                                 */
 int tok_cls_stats_update(const void* logits, const int64_t* labels, const int64_t* target, int64_t rows,
                          int classes, int ld, int64_t ignore_index, int64_t* counts, void* stream);
 /* ConfusionMatrix (metrics/__init__.py:53): confusion int64 [classes][classes], [target][prediction] += 1, same inputs */

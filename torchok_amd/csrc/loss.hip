@@ -919,11 +919,14 @@ __global__ __launch_bounds__(256) void cls_stats_kernel(const bf16* __restrict__
     const int64_t t = target[row];
     if (t == ignore_index || t < 0 || t >= classes) continue;
     int pred;
-    if (labels != nullptr) {
-      pred = (int)labels[row];
+    if (labels != nullptr) {       // compared as int64: a label such as 2^40 must not wrap into a class index
+      const int64_t p64 = labels[row];
+      pred = (p64 >= 0 && p64 < (int64_t)classes) ? (int)p64 : -1;
     } else {                       // first maximum, as torch.argmax
+      // a lane that owns a column starts from that column's index, so a row of -inf (a fully masked row) resolves to
+      // column 0 like any other row of equal logits; only a lane without a column keeps the index that cannot win
       float best = -INFINITY;
-      int bi = 0x7fffffff;
+      int bi = lane < classes ? lane : 0x7fffffff;
       for (int c = lane; c < classes; c += 64) {
         const float v = bf2f(logits[row * ld + c]);
         if (v > best) { best = v; bi = c; }
