@@ -1057,7 +1057,7 @@ def test_bn_padded_channels(libs):
     assert float(dv[id(coef)][:, cr:].abs().max()) == 0.0
 
 
-# ---- token-major transformer kernels (transformer.hip) ---------------------------------------------------------
+# ---- token-major transformer kernels (layernorm.hip, window_attn.hip, transformer.hip) -------------------------
 @pytest.mark.parametrize('rows,c,ld,sc,rs', [(37, 96, 96, 0, 0), (64, 768, 768, 1, 1), (50, 18, 24, 1, 0),
                                              (4096, 192, 192, 1, 1), (333, 384, 384, 1, 0), (130, 1024, 1024, 0, 1)])
 def test_layernorm(libs, rows, c, ld, sc, rs):
@@ -1173,7 +1173,7 @@ def test_window_attention_is_bit_reproducible(libs, b, h, w, heads, ws, shift):
     """The SwinV2-T stage geometries at sizes where a workgroup walks several images (units >= 3072): the same launch, six
     times, gives the same bits in d(qkv), the d(logits) partial rows and the d(logit_scale) partials, and every element is
     written.  Round 3 found a few hundred wrong d(q) / d(k) elements per launch, different ones every run (a register reused
-    under two ds_bpermute in flight, transformer.hip: the value barrier after the delta reduction); only the full-size model
+    under two ds_bpermute in flight, window_attn.hip: the value barrier after the delta reduction); only the full-size model
     test saw it."""
     lib, _ = libs
     c, n, nw = heads * 32, ws * ws, (h // ws) * (w // ws)
@@ -1278,7 +1278,7 @@ def test_colsum_partial(libs, m, n):
 @pytest.mark.parametrize('acc', [0, 1])
 def test_colsum_f32_wide_matrices(libs, rows, cols, acc):
     """The fold of window attention's d(bias) partial rows (heads x 49 x 49 columns: odd for three heads) on the wide kernel
-    (cols >= 2048, csrc/transformer.hip: colsum_f32_wide_kernel): column sums in fp64 order-of-rows, accumulate, run twice
+    (cols >= 2048, csrc/layernorm.hip: colsum_f32_wide_kernel): column sums in fp64 order-of-rows, accumulate, run twice
     bit-identical, nothing written past the last column."""
     lib, _ = libs
     g = torch.Generator(device='cuda').manual_seed(rows + cols)

@@ -1,4 +1,4 @@
-"""tok_layernorm_fwd / _bwd (csrc/transformer.hip: ln_*_vec_kernel<LPR, VPL> and the one-wave-per-row fallback) element by
+"""tok_layernorm_fwd / _bwd (csrc/layernorm.hip: ln_*_vec_kernel<LPR, VPL> and the one-wave-per-row fallback) element by
 element against fp64 of the same bf16 inputs; the bounds are derived in tests/layernorm_ref.py.  Widths on both sides of every
 dispatch boundary (c / 8 <= 16 / 32 / 64 / else, the fallback at c != ld, c % 8 and c > 1024), row counts that leave partial
 waves for every lanes-per-row, a row count over the backward's grid cap (grid-stride loop and second row slot), with and
@@ -47,7 +47,7 @@ def _run(tag, rows, c, ld, sc, rs, seed, pair=False):
     check_fwd(tag, ref, og.value(), mg.value()[0], rg.value()[0])
     # backward, alone: fed the fp32-rounded fp64 statistics
     r = lib.tok_layernorm_bwd_rows(rows, c)
-    assert r == min((rows + 3) // 4, 1024), f'{r} partial rows: is TOK_LN_BWD_BLOCKS set in the environment?'
+    assert r == min((rows + 3) // 4, 1024), f'{r} partial rows: has tok_layernorm_bwd_rows (csrc/layernorm.hip) left its cap of 1024?'
     gg = Guarded(rows, c, ld, init=dev['dout'], nan_pad=True)
     m32, r32 = ref.mean32.cuda(), ref.rstd32.cuda()
     for acc in (0, 1):

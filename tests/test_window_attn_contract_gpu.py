@@ -1,4 +1,4 @@
-"""The window-attention kernels (csrc/transformer.hip: two MFMA kernels for windows of up to 64 tokens, two scalar ones above)
+"""The window-attention kernels (csrc/window_attn.hip: two MFMA kernels for windows of up to 64 tokens, two scalar ones above)
 across the contract of include/tok.h, element by element against the fp64 reference of tests/window_attn_ref.py (whose
 docstring derives every bound; tests/test_window_attn_ref.py shows that an exact kernel with the device's operand formats
 stays inside half of each).  Covered here and nowhere else: non-square maps, workgroups that walk 2 / 3 / 16 images with a
@@ -63,13 +63,13 @@ def _launch(dims, qkv, dout, ls, bias, mask, backward=True):
 
 
 def _expect_rows(dims, bpw):
-    """the case must run the path it names: tok_window_attn_bwd_rows == ceil(B / bpw) * nW at the default divisor 1536 / cap 16"""
+    """the case must run the path it names: tok_window_attn_bwd_rows == ceil(B / bpw) * nW at the divisor 1536 / cap 16"""
     b, h, w, heads, ws, _ = dims
     nw = (h // ws) * (w // ws)
     assert bpw == max(1, min(16, b * nw * heads // 1536, b))
     got = _C.lib().tok_window_attn_bwd_rows(b, h, w, heads, ws)
-    assert got == cdiv(b, bpw) * nw, (f'{got} scratch rows, {cdiv(b, bpw) * nw} expected for {bpw} images per workgroup: is '
-                                      f'TOK_ATTN_BPW_DIV / TOK_ATTN_BPW_CAP set in the environment?')
+    assert got == cdiv(b, bpw) * nw, (f'{got} scratch rows, {cdiv(b, bpw) * nw} expected for {bpw} images per workgroup: has '
+                                      f'attn_bpw (csrc/window_attn.hip) left divisor 1536 / cap 16?')
     return got
 
 

@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void gattn_dkv_kernel(const bf16* __restrict__
     frag_x_tile(vf, dos, l15, g, dpt);
     // S^T and dP^T leave the accumulator file here, in one go: without it hipcc schedules a v_accvgpr_read of the next element
     // onto the data register of a ds_write_b16 of P^T still in flight (tools/isa_lint.py; the note at the delta reduction of
-    // attn_bwd_mfma_kernel in transformer.hip)
+    // attn_bwd_mfma_kernel in window_attn.hip)
     asm volatile("" : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(dpt[0]), "+v"(dpt[1]), "+v"(dpt[2]), "+v"(dpt[3]));
     // element (qj, r): key k0 + 4g + r, query q0 + 16 qj + l15
     float dsv[4][4];
