@@ -680,6 +680,27 @@ int tok_dwconv_dgrad(const void* dout, const float* w, int n, int h, int wd, int
 size_t tok_dwconv_wgrad_ws_bytes(int n, int h, int wd, int c, int k, int stride);
 int tok_dwconv_wgrad(const void* x, const void* dout, int n, int h, int wd, int c, int ld, int k, int stride, float* dw,
                      int accumulate, float* ws, size_t ws_bytes, void* stream);
+/* ---- ResNeXt grouped unit ([timm] resnet.Bottleneck.conv2 with groups = cardinality) ------------------------------------------
+ * Grouped 3 x 3 convolution without bias, padding 1, stride in {1, 2}, no dilation, any h and w (n h w < 2^31 - 64 pixels;
+ * element offsets are 64-bit); c input and c output channels
+ * in `groups` >= 2 groups of cg = c / groups in {4, 8, 16, 32, 64} (anything else: TOK_ERR_INVALID; groups == 1 is tok_conv_*).
+ * x / out / dout / dx bf16 NHWC [n][h][w][ld] (c % 8 == 0, ld >= c, ld % 8 == 0; one pitch for every tensor of a call; pad
+ * channels are never read into a result and never written), w the fp32 master (c, cg, 3, 3): [c][cg][3][3] in memory
+ * (w_krsc = 0) or channels-last [c][3][3][cg] (w_krsc = 1); products are bf16 x bf16-rounded weight, accumulated in fp32.
+ * Output size p = (h - 1) / stride + 1, likewise q.  The arithmetic does not grow with `groups` (block-diagonal MFMA tiles).
+ * tok_gconv_fwd: out = conv(x); stats (nullable) = per-channel (sum, sum of squares) of the ROUNDED output, fp32
+ *   [2][tok_gconv_rows(...)][c] — the partial rows tok_bn_finalize folds (no separate statistics pass).
+ * tok_gconv_dgrad: dx (=|+=) the transposed correlation of dout (h, wd: the size of dx).
+ * tok_gconv_wgrad: dw fp32 in the layout w_krsc names (=|+=); ws fp32 workspace of tok_gconv_wgrad_ws_bytes(...) bytes: per-wave
+ *   partial sums, folded in a fixed order.  Every reduction is bit-reproducible (no float atomics).                           */
+int tok_gconv_rows(int n, int h, int wd, int c, int groups, int stride);
+int tok_gconv_fwd(const void* x, const float* w, int w_krsc, int n, int h, int wd, int c, int ld, int groups, int stride,
+                  void* out, float* stats, void* stream);
+int tok_gconv_dgrad(const void* dout, const float* w, int w_krsc, int n, int h, int wd, int c, int ld, int groups, int stride,
+                    void* dx, int accumulate, void* stream);
+size_t tok_gconv_wgrad_ws_bytes(int n, int h, int wd, int c, int groups, int stride);
+int tok_gconv_wgrad(const void* x, const void* dout, int n, int h, int wd, int c, int ld, int groups, int stride, float* dw,
+                    int w_krsc, int accumulate, float* ws, size_t ws_bytes, void* stream);
 /* Squeeze-excite gate s[n][c] = sigmoid(b2 + W2 relu(b1 + W1 mean_hw(x[n]))); the product x * s is tok_channel_scale.
  * x / dout / dx bf16 [n][hw][ld] (c % 8 == 0, c <= 2048), W1 fp32 [rd][c] (conv_reduce), W2 fp32 [c][rd] (conv_expand),
  * 1 <= rd <= 256.  tok_se_fwd writes mean fp32 [n][c], hid fp32 [n][rd] (after the ReLU) and gate fp32 [n][c]: what

@@ -184,6 +184,11 @@ PROTOTYPES = {
     'tok_dwconv_dgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     'tok_dwconv_wgrad_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'tok_dwconv_wgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),
+    'tok_gconv_rows': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    'tok_gconv_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    'tok_gconv_dgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    'tok_gconv_wgrad_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    'tok_gconv_wgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, _P, c_size_t, _P]),
     'tok_se_ws_floats': (c_size_t, [c_int, c_int, c_int, c_int]),
     'tok_se_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tok_se_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int,

@@ -9,6 +9,7 @@ max_pool_3x3_s2           nn.MaxPool2d(3, 2, 1)                          (resnet
 global_avg_pool           SelectAdaptivePool2d('avg', flatten=True)      (pooling.py:7-12)
 linear                    nn.Linear                                      (linear_head.py:31)
 dwconv_bn_act             depthwise conv -> batch_norm -> relu           ([timm] DepthwiseSeparableConv / InvertedResidual)
+gconv_bn_act              grouped 3x3 conv -> batch_norm -> relu         ([timm] Bottleneck.conv2 with groups = cardinality: ResNeXt)
 squeeze_excite            x * gate(expand(relu(reduce(mean(x)))))        ([timm] efficientnet_blocks.SqueezeExcite;
                           gate = sigmoid or hard sigmoid)
 
@@ -220,7 +221,9 @@ def _conv_desc(x: TTensor, k_pad: int, r: int, s: int, stride: int, pad: int) ->
 
 def _check_conv(conv: nn.Conv2d):
     if conv.groups != 1 or tuple(conv.dilation) != (1, 1):
-        raise NotImplementedError('torchok_amd conv: groups == 1 and dilation == 1 only')
+        raise NotImplementedError('torchok_amd conv: dilation == 1 and groups == 1 (dense, conv_bn_act), groups == channels '
+                                  '(depthwise 3x3 / 5x5, dwconv_bn_act) or a grouped 3x3 of group width 4, 8, 16, 32 or 64 '
+                                  '(gconv_bn_act) only')
     if conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1] \
             or conv.padding[0] != conv.padding[1] or isinstance(conv.padding, str):
         raise NotImplementedError('torchok_amd conv: square kernel / stride / padding only')
@@ -688,6 +691,9 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     the unit's usual one (it never reads the normalised values of a unit without activation)."""
     if pool and (bn is None or not relu or shortcut is not None or x.data.dim() != 4):
         raise ValueError('conv_bn_act(pool=True): BatchNorm + ReLU on a 4-D input, no shortcut')
+    if (isinstance(conv, nn.Conv2d) and _is_grouped(conv) and bn is not None and shortcut is None and not pool
+            and not defer_apply):
+        return gconv_bn_act(region, x, conv, bn, relu=relu, act=act)       # (anything else grouped: _check_conv refuses below)
     act = _check_act(relu, act, bn, shortcut, pool, defer_apply)
     relu = act == RELU
     await_ready(x, shortcut)
@@ -1016,9 +1022,32 @@ def _check_dwconv(conv: nn.Conv2d, x: TTensor):
         raise NotImplementedError('torchok_amd depthwise conv: a 4-D input whose channel count is a multiple of 8')
 
 
-class _DwConvBnActNode(_ConvBnActNode):
-    """relu(bn(depthwise_conv(x))).  The BatchNorm backward is the one of _ConvBnActNode (tok_bn_bwd_*; a consumer conv's data
-    gradient may reduce its sums, see wants_fused_bwd_stats); then tok_dwconv_wgrad / tok_dwconv_dgrad on dy."""
+class _SameWidthConvBnActNode(_ConvBnActNode):
+    """act(bn(conv(x))) for a convolution with as many output as input channels that has kernels of its own (depthwise,
+    grouped 3x3).  The BatchNorm backward is the one of _ConvBnActNode (tok_bn_bwd_*; a consumer conv's data gradient may
+    reduce its sums, see wants_fused_bwd_stats); then the family's weight and data gradient on dy.  A family states its five
+    library calls; `geo` is (n, h, w, c, c, kernel size | groups, stride), the sizes every one of them takes."""
+
+    # -- what a family provides (the weight is read, and its gradient written, as the master lies in memory) --
+    @staticmethod
+    def stat_rows(lib, conv, geo): raise NotImplementedError
+
+    @staticmethod
+    def launch_fwd(lib, conv, geo, x, y, stats, st): raise NotImplementedError
+
+    @staticmethod
+    def wgrad_ws_bytes(lib, conv, geo): raise NotImplementedError
+
+    @staticmethod
+    def launch_wgrad(lib, conv, geo, x, dy, slot, acc, ws, ws_bytes, st): raise NotImplementedError
+
+    @staticmethod
+    def launch_dgrad(lib, conv, geo, dy, tgt, acc, st): raise NotImplementedError
+
+    @staticmethod
+    def geo(conv, x: TTensor):
+        n, h, w, c = x.shape
+        return n, h, w, c, c, conv.kernel_size[0], conv.stride[0]
 
     def backward(self):
         lib, st = _C.lib(), stream_ptr()
@@ -1027,8 +1056,7 @@ class _DwConvBnActNode(_ConvBnActNode):
         if g is None:
             return
         conv, x = self.conv, self.x
-        n, h, w, c = x.shape
-        k, stride = conv.kernel_size[0], conv.stride[0]
+        geo = self.geo(conv, x)
         m, kp = self.y.numel() // self.y.shape[-1], self.y.shape[-1]
         w_need, x_need = conv.weight.requires_grad, x.requires_grad
         dy = self._bn_bwd(lib, st, g, m, kp, w_need or x_need)
@@ -1036,41 +1064,33 @@ class _DwConvBnActNode(_ConvBnActNode):
         if dy is None:
             return
         if w_need:
-            ws_bytes = lib.tok_dwconv_wgrad_ws_bytes(n, h, w, c, k, stride)
+            ws_bytes = self.wgrad_ws_bytes(lib, conv, geo)
             ws = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
             slot, acc = PG.sink(conv.weight)
-            _C.check(lib.tok_dwconv_wgrad(ptr(x.data), ptr(dy), n, h, w, c, c, k, stride, ptr(slot), acc, ptr(ws), ws_bytes, st),
-                     'tok_dwconv_wgrad')
+            self.launch_wgrad(lib, conv, geo, x.data, dy, slot, acc, ws, ws_bytes, st)
             PG.commit(conv.weight, slot, acc)
         if x_need:
             tgt, acc = grad_target(x)
-            _C.check(lib.tok_dwconv_dgrad(ptr(dy), ptr(conv.weight), n, h, w, c, c, k, stride, ptr(tgt), acc, st),
-                     'tok_dwconv_dgrad')
+            self.launch_dgrad(lib, conv, geo, dy, tgt, acc, st)
 
 
-def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True,
-                  act: Optional[str] = None) -> TTensor:
-    """out = act(bn(conv(x))) for a depthwise `conv` ([timm] create_conv2d(depthwise=True) + BatchNormAct2d of the MnasNet
-    and MobileNetV3 blocks).  act=None: `relu` decides; act='hard_swish': as in conv_bn_act.  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
-    rows tok_bn_finalize folds); eval mode uses the running statistics; track_running_stats=False uses batch statistics."""
-    act = _check_act(relu, act, bn)
+def _same_width_conv_bn_act(node_cls, region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, act) -> TTensor:
+    """The forward of a _SameWidthConvBnActNode family (the caller has checked the layer and resolved `act`)."""
     await_ready(x)
-    _check_dwconv(conv, x)
     if bn.num_features != conv.out_channels:
         raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {conv.out_channels}')
     lib, st = _C.lib(), stream_ptr()
-    n, h, w, c = x.shape
-    k, stride = conv.kernel_size[0], conv.stride[0]
+    geo = node_cls.geo(conv, x)
+    n, h, w, c, stride = geo[0], geo[1], geo[2], geo[3], geo[-1]
     p, q = (h - 1) // stride + 1, (w - 1) // stride + 1
     dev = x.data.device
     batch = batch_stats(bn)
     y = torch.empty((n, p, q, c), dtype=BF16, device=dev)
     stats, rows = None, 0
     if batch:
-        rows = lib.tok_dwconv_rows(n, h, w, c, k, stride)
+        rows = node_cls.stat_rows(lib, conv, geo)
         stats = torch.empty((2, rows, c), dtype=F32, device=dev)
-    _C.check(lib.tok_dwconv_fwd(ptr(x.data), ptr(conv.weight), n, h, w, c, c, k, stride, ptr(y), ptr(stats), st),
-             'tok_dwconv_fwd')
+    node_cls.launch_fwd(lib, conv, geo, x.data, y, stats, st)
     m = n * p * q
     scale, shift, mean, rstd = bn_coeffs(lib, st, bn, stats, rows, m, c, dev)
     training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad
@@ -1078,7 +1098,7 @@ def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2
     out_data, mask = bn_apply(lib, st, y, scale, shift, act, None, act == RELU and training, m, c)
     out = TTensor(out_data, c, requires_grad=bool(training))
     if training:
-        node = _DwConvBnActNode()
+        node = node_cls()
         node.x, node.out, node.y, node.mask = x, out, y, mask
         node.conv, node.bn, node.act, node.batch_stats = conv, bn, act, batch
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
@@ -1087,6 +1107,117 @@ def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2
             x.uses += 1
         region.add(node)
     return out
+
+
+class _DwConvBnActNode(_SameWidthConvBnActNode):
+    """relu(bn(depthwise_conv(x))) on tok_dwconv_*; geo[5] is the kernel size."""
+
+    @staticmethod
+    def stat_rows(lib, conv, geo):
+        n, h, w, c, _, k, stride = geo
+        return lib.tok_dwconv_rows(n, h, w, c, k, stride)
+
+    @staticmethod
+    def launch_fwd(lib, conv, geo, x, y, stats, st):
+        _C.check(lib.tok_dwconv_fwd(ptr(x), ptr(conv.weight), *geo, ptr(y), ptr(stats), st), 'tok_dwconv_fwd')
+
+    @staticmethod
+    def wgrad_ws_bytes(lib, conv, geo):
+        n, h, w, c, _, k, stride = geo
+        return lib.tok_dwconv_wgrad_ws_bytes(n, h, w, c, k, stride)
+
+    @staticmethod
+    def launch_wgrad(lib, conv, geo, x, dy, slot, acc, ws, ws_bytes, st):
+        _C.check(lib.tok_dwconv_wgrad(ptr(x), ptr(dy), *geo, ptr(slot), acc, ptr(ws), ws_bytes, st), 'tok_dwconv_wgrad')
+
+    @staticmethod
+    def launch_dgrad(lib, conv, geo, dy, tgt, acc, st):
+        _C.check(lib.tok_dwconv_dgrad(ptr(dy), ptr(conv.weight), *geo, ptr(tgt), acc, st), 'tok_dwconv_dgrad')
+
+
+def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True,
+                  act: Optional[str] = None) -> TTensor:
+    """out = act(bn(conv(x))) for a depthwise `conv` ([timm] create_conv2d(depthwise=True) + BatchNormAct2d of the MnasNet
+    and MobileNetV3 blocks).  act=None: `relu` decides; act='hard_swish': as in conv_bn_act.  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
+    rows tok_bn_finalize folds); eval mode uses the running statistics; track_running_stats=False uses batch statistics."""
+    act = _check_act(relu, act, bn)
+    _check_dwconv(conv, x)
+    return _same_width_conv_bn_act(_DwConvBnActNode, region, x, conv, bn, act)
+
+
+# ---- grouped 3x3 conv + bn + relu (ResNeXt) ------------------------------------------------------------------------------
+
+GCONV_WIDTHS = (4, 8, 16, 32, 64)      # group widths csrc/conv_group.hip serves
+
+
+def _is_grouped(conv: nn.Conv2d) -> bool:
+    """A grouped convolution that is neither dense nor depthwise: the grouped unit's to serve or to refuse."""
+    return conv.groups > 1 and conv.groups != conv.in_channels
+
+
+def _check_gconv(conv: nn.Conv2d, x: TTensor):
+    g = conv.groups
+    if (g < 2 or conv.in_channels != conv.out_channels or conv.in_channels % g != 0 or conv.in_channels // g not in GCONV_WIDTHS
+            or conv.bias is not None or conv.kernel_size != (3, 3) or tuple(conv.stride) not in ((1, 1), (2, 2))
+            or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != 'zeros'):
+        raise NotImplementedError(f'torchok_amd grouped conv: 3x3, groups >= 2, as many output as input channels, group width '
+                                  f'in {GCONV_WIDTHS}, no bias, stride 1 or 2, padding 1, no dilation')
+    if x.data.dim() != 4 or x.c != x.cp or x.c != conv.in_channels:
+        raise NotImplementedError('torchok_amd grouped conv: a 4-D input whose channel count is a multiple of 8')
+
+
+def _w_krsc(weight: torch.Tensor) -> int:
+    """Which of the two layouts tok_gconv_* reads the (K, cg, 3, 3) master (and writes its gradient slot) in: 1 channels-last
+    [k][3][3][cg], 0 [k][cg][3][3]."""
+    if weight.is_contiguous():
+        return 0
+    if weight.permute(0, 2, 3, 1).is_contiguous():
+        return 1
+    raise RuntimeError('grouped conv weight must be contiguous or channels-last')
+
+
+class _GConvBnActNode(_SameWidthConvBnActNode):
+    """relu(bn(grouped_conv(x))) on tok_gconv_*; geo[5] is the number of groups.  The gradient slot has the master's strides, so
+    one layout flag serves the weight and its gradient."""
+
+    @staticmethod
+    def geo(conv, x: TTensor):
+        n, h, w, c = x.shape
+        return n, h, w, c, c, conv.groups, conv.stride[0]
+
+    @staticmethod
+    def stat_rows(lib, conv, geo):
+        n, h, w, c, _, groups, stride = geo
+        return lib.tok_gconv_rows(n, h, w, c, groups, stride)
+
+    @staticmethod
+    def launch_fwd(lib, conv, geo, x, y, stats, st):
+        _C.check(lib.tok_gconv_fwd(ptr(x), ptr(conv.weight), _w_krsc(conv.weight), *geo, ptr(y), ptr(stats), st), 'tok_gconv_fwd')
+
+    @staticmethod
+    def wgrad_ws_bytes(lib, conv, geo):
+        n, h, w, c, _, groups, stride = geo
+        return lib.tok_gconv_wgrad_ws_bytes(n, h, w, c, groups, stride)
+
+    @staticmethod
+    def launch_wgrad(lib, conv, geo, x, dy, slot, acc, ws, ws_bytes, st):
+        _C.check(lib.tok_gconv_wgrad(ptr(x), ptr(dy), *geo, ptr(slot), _w_krsc(conv.weight), acc, ptr(ws), ws_bytes, st),
+                 'tok_gconv_wgrad')
+
+    @staticmethod
+    def launch_dgrad(lib, conv, geo, dy, tgt, acc, st):
+        _C.check(lib.tok_gconv_dgrad(ptr(dy), ptr(conv.weight), _w_krsc(conv.weight), *geo, ptr(tgt), acc, st), 'tok_gconv_dgrad')
+
+
+def gconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True,
+                 act: Optional[str] = None) -> TTensor:
+    """out = act(bn(conv(x))) for a grouped 3x3 `conv` ([timm] Bottleneck.conv2 + bn2 + act2 of the ResNeXts).  act=None: `relu`
+    decides; act='hard_swish': as in conv_bn_act.  The kernels read the fp32 master itself (rounded to bf16 as a wave builds its
+    fragments): there is no packed copy that an optimizer step could leave stale.  The BatchNorm stage is dwconv_bn_act's.  The
+    output carries no `colsum_part`: a fused residual unit that consumes it sums the columns itself (_unit3_forward)."""
+    act = _check_act(relu, act, bn)
+    _check_gconv(conv, x)
+    return _same_width_conv_bn_act(_GConvBnActNode, region, x, conv, bn, act)
 
 
 # ---- squeeze-excite (MnasNet-A1) -----------------------------------------------------------------------------------------

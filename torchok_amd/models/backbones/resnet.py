@@ -11,9 +11,10 @@ Execution differs completely: each ``conv -> bn -> (+shortcut) -> relu`` group i
 pass), activations stay NHWC bf16 in HBM between units, and the whole backbone is a single
 autograd node.  The nn.Conv2d / nn.BatchNorm2d children are parameter containers only.
 
-Only the plain (v1.5) family is built: no SE / anti-aliasing / drop-block / avg-down / deep stem
-(plus the other plain-architecture entrypoints at the end of the file; the d/s/t-stem, grouped, SE/ECA, blur-pool and
-RS variants of the reference are outside the hot-path scope).
+Only the plain (v1.5) family is built: no SE / anti-aliasing / drop-block
+(plus the other plain-architecture entrypoints at the end of the file, the d / t stems and the ResNeXts of group width
+4 ... 64 on the grouped 3x3 unit; the s-stem, SE/ECA, blur-pool and RS variants of the reference are outside the hot-path
+scope).
 """
 import math
 from typing import List
@@ -72,15 +73,16 @@ class Bottleneck(nn.Module):
                  reduce_first=1, dilation=1, first_dilation=None, act_layer=nn.ReLU, norm_layer=nn.BatchNorm2d,
                  attn_layer=None, aa_layer=None, drop_block=None, drop_path=None):
         super().__init__()
-        _unsupported(cardinality=cardinality != 1, dilation=dilation != 1, attn_layer=attn_layer,
-                     aa_layer=aa_layer, drop_block=drop_block, drop_path=drop_path)
+        _unsupported(dilation=dilation != 1, attn_layer=attn_layer, aa_layer=aa_layer, drop_block=drop_block,
+                     drop_path=drop_path)
         width = int(math.floor(planes * (base_width / 64)) * cardinality)
         first_planes = width // reduce_first
         outplanes = planes * self.expansion
         self.conv1 = nn.Conv2d(inplanes, first_planes, kernel_size=1, bias=False)
         self.bn1 = norm_layer(first_planes)
         self.act1 = act_layer(inplace=True)
-        self.conv2 = nn.Conv2d(first_planes, width, kernel_size=3, stride=stride, padding=1, bias=False)
+        # cardinality > 1 (ResNeXt): a grouped 3x3, which conv_bn_act hands to the grouped unit (EF.gconv_bn_act)
+        self.conv2 = nn.Conv2d(first_planes, width, kernel_size=3, stride=stride, padding=1, groups=cardinality, bias=False)
         self.bn2 = norm_layer(width)
         self.act2 = act_layer(inplace=True)
         self.conv3 = nn.Conv2d(width, outplanes, kernel_size=1, bias=False)
@@ -336,3 +338,20 @@ resnet50t = _plain('resnet50t', Bottleneck, [3, 4, 6, 3], 'resnet.py:665-671', *
 resnet101d = _plain('resnet101d', Bottleneck, [3, 4, 23, 3], 'resnet.py:682-687', **_D)
 resnet152d = _plain('resnet152d', Bottleneck, [3, 8, 36, 3], 'resnet.py:698-704', **_D)
 resnet200d = _plain('resnet200d', Bottleneck, [3, 24, 36, 3], 'resnet.py:715-721', **_D)
+# ResNeXt: Bottleneck.conv2 is a grouped 3x3 (csrc/conv_group.hip serves group widths 4 ... 64: the 32x4d, 32x8d and 64x4d
+# families).  The 32x16d / 32x32d / 32x48d entries of the reference need group widths up to 384 and stay unregistered.
+_X4 = dict(cardinality=32, base_width=4)
+_X8 = dict(cardinality=32, base_width=8)
+resnext50_32x4d = _plain('resnext50_32x4d', Bottleneck, [3, 4, 6, 3], 'resnet.py:787-792', **_X4)
+resnext50d_32x4d = _plain('resnext50d_32x4d', Bottleneck, [3, 4, 6, 3], 'resnet.py:795-802', **_X4, **_D)
+resnext101_32x4d = _plain('resnext101_32x4d', Bottleneck, [3, 4, 23, 3], 'resnet.py:805-810', **_X4)
+resnext101_32x8d = _plain('resnext101_32x8d', Bottleneck, [3, 4, 23, 3], 'resnet.py:813-818', **_X8)
+resnext101_64x4d = _plain('resnext101_64x4d', Bottleneck, [3, 4, 23, 3], 'resnet.py:821-826', cardinality=64, base_width=4)
+tv_resnext50_32x4d = _plain('tv_resnext50_32x4d', Bottleneck, [3, 4, 6, 3], 'resnet.py:829-834', **_X4)
+ig_resnext101_32x8d = _plain('ig_resnext101_32x8d', Bottleneck, [3, 4, 23, 3], 'resnet.py:837-845', default_pretrained=True, **_X8)
+ssl_resnext50_32x4d = _plain('ssl_resnext50_32x4d', Bottleneck, [3, 4, 6, 3], 'resnet.py:901-908', default_pretrained=True, **_X4)
+ssl_resnext101_32x4d = _plain('ssl_resnext101_32x4d', Bottleneck, [3, 4, 23, 3], 'resnet.py:911-918', default_pretrained=True, **_X4)
+ssl_resnext101_32x8d = _plain('ssl_resnext101_32x8d', Bottleneck, [3, 4, 23, 3], 'resnet.py:921-928', default_pretrained=True, **_X8)
+swsl_resnext50_32x4d = _plain('swsl_resnext50_32x4d', Bottleneck, [3, 4, 6, 3], 'resnet.py:963-971', default_pretrained=True, **_X4)
+swsl_resnext101_32x4d = _plain('swsl_resnext101_32x4d', Bottleneck, [3, 4, 23, 3], 'resnet.py:974-982', default_pretrained=True, **_X4)
+swsl_resnext101_32x8d = _plain('swsl_resnext101_32x8d', Bottleneck, [3, 4, 23, 3], 'resnet.py:985-993', default_pretrained=True, **_X8)
