@@ -292,6 +292,18 @@ int tok_bn_hswish_bwd_reduce(const void* dout, const void* y, const float* scale
                              const float* rstd, int64_t m, int c, float* partial, void* stream);
 int tok_bn_hswish_bwd_apply(const void* dout, const void* y, const float* scale, const float* shift, const float* coef,
                             void* dy, int64_t m, int c, void* stream);
+/* BatchNorm + ReLU6 without a mask (EfficientNet-Lite): the hard-swish trio's kernels, launch geometry and partial-row layout
+ * with the other activation.  z = fmaf(y, scale, shift) in fp32, recomputed from the stored bf16 y in every pass.
+ * out = min(max(z, 0), 6), rounded once to bf16;  dz = dout * [0 < z < 6]: the interval is open, both kinks give 0, what
+ * torch.nn.ReLU6 (aten::hardtanh_backward) differentiates to.
+ * tok_bn_relu6_bwd_reduce: partial[2][tok_bn_bwd_rows(m, c)][c] = sum(dz), sum(dz * xhat) -> tok_bn_bwd_finalize, dzy_form = 0.
+ * tok_bn_relu6_bwd_apply: dy = a1*dz + a2*y + a3 from coef[3][c] (eval-mode BatchNorm: coef = (scale, 0, 0)).
+ * No shortcut, no mask; m > 0, c % 8 == 0; a null pointer or a bad size is refused (TOK_ERR_INVALID) before any launch. */
+int tok_bn_relu6_fwd(const void* y, const float* scale, const float* shift, void* out, int64_t m, int c, void* stream);
+int tok_bn_relu6_bwd_reduce(const void* dout, const void* y, const float* scale, const float* shift, const float* mean,
+                            const float* rstd, int64_t m, int c, float* partial, void* stream);
+int tok_bn_relu6_bwd_apply(const void* dout, const void* y, const float* scale, const float* shift, const float* coef,
+                           void* dy, int64_t m, int c, void* stream);
 
 
 /* ---- pooling ----------------------------------------------------------------------------

@@ -76,6 +76,9 @@ PROTOTYPES = {
     'tok_bn_hswish_fwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, _P]),
     'tok_bn_hswish_bwd_reduce': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P]),
     'tok_bn_hswish_bwd_apply': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
+    'tok_bn_relu6_fwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, _P]),
+    'tok_bn_relu6_bwd_reduce': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P]),
+    'tok_bn_relu6_bwd_apply': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
     'tok_maxpool3x3s2_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     'tok_maxpool3x3s2_bwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     'tok_avgpool2x2_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),

@@ -1,10 +1,10 @@
-// BatchNorm (training, batch statistics) + ReLU / hard-swish + residual add, NHWC bf16, fp32 statistics.
+// BatchNorm (training, batch statistics) + ReLU / hard-swish / ReLU6 + residual add, NHWC bf16, fp32 statistics.
 // All passes are HBM-bound streaming kernels on the row skeleton of row_stream.h: 16-byte (8 x bf16) accesses per lane, a
 // thread keeps ONE 8-channel group for a whole pass so scale/shift/coefficients live in registers.
 //
-// Forward :  conv epilogue partial sums -> tok_bn_finalize -> tok_bn_act_fwd | tok_bn_hswish_fwd
-// Backward:  tok_bn_bwd_reduce (partials) -> tok_bn_bwd_finalize -> tok_bn_bwd_apply      (tok_bn_hswish_bwd_*: the same two
-//            kernels with the hard-swish derivative)
+// Forward :  conv epilogue partial sums -> tok_bn_finalize -> tok_bn_act_fwd | tok_bn_hswish_fwd | tok_bn_relu6_fwd
+// Backward:  tok_bn_bwd_reduce (partials) -> tok_bn_bwd_finalize -> tok_bn_bwd_apply      (tok_bn_hswish_bwd_*, tok_bn_relu6_bwd_*: the
+//            same two kernels with the hard-swish / ReLU6 derivative)
 //            dz = dout * act'(z) ;  dy = a1*dz + a2*y + a3   (a* per channel)
 // The reducing kernels leave partial[2][gridDim.x][C]; fixed summation order, no atomics: two runs give the same bits.
 // Under -ffp-contract=fast hipcc fuses a product into a following add or not depending on the surrounding code, so every
@@ -235,23 +235,33 @@ struct ReluD {
     for (int e = 0; e < 8; ++e) s1[e] += dz[e];
   }
 };
-// Hard-swish (MobileNetV3), the mask-less path: nothing is kept between the passes but y; forward, reduce and apply each
-// recompute z from the stored bf16 y, so all three see the same z and the same branch of the derivative.
+// The mask-less path (hard-swish: MobileNetV3; ReLU6: EfficientNet-Lite): nothing is kept between the passes but y; forward,
+// reduce and apply each recompute z from the stored bf16 y, so all three see the same z and the same branch of the derivative.
+// An activation is its two scalar functions, f(z) and d(z) = f'(z); the three kernels are written once over them.
 //   hswish(z) = z * min(max(z + 3, 0), 6) / 6      hswish'(z) = 0 (z < -3), z/3 + 0.5 (-3 <= z <= 3), 1 (z > 3)
-__device__ __forceinline__ float hswish_f(float z) {
-  return z * __builtin_amdgcn_fmed3f(z + 3.f, 0.f, 6.f) * (1.f / 6.f);
-}
-// what torch.nn.functional.hardswish differentiates to (the kinks belong to the middle branch)
-__device__ __forceinline__ float hswish_d(float z) {
-  const float mid = fmaf(z, 1.f / 3.f, 0.5f);
-  return z < -3.f ? 0.f : (z <= 3.f ? mid : 1.f);
-}
-struct HswishD {
+struct Hswish {
+  static __device__ __forceinline__ float f(float z) {
+    return z * __builtin_amdgcn_fmed3f(z + 3.f, 0.f, 6.f) * (1.f / 6.f);
+  }
+  // what torch.nn.functional.hardswish differentiates to (the kinks belong to the middle branch)
+  static __device__ __forceinline__ float d(float z) {
+    const float mid = fmaf(z, 1.f / 3.f, 0.5f);
+    return z < -3.f ? 0.f : (z <= 3.f ? mid : 1.f);
+  }
+};
+//   relu6(z) = min(max(z, 0), 6)                   relu6'(z) = 1 (0 < z < 6), else 0
+struct Relu6 {
+  static __device__ __forceinline__ float f(float z) { return fminf(fmaxf(z, 0.f), 6.f); }
+  // what torch.nn.ReLU6 (aten::hardtanh_backward) differentiates to: the interval is open, both kinks give 0
+  static __device__ __forceinline__ float d(float z) { return (z > 0.f && z < 6.f) ? 1.f : 0.f; }
+};
+template <class Act>
+struct MasklessD {
   __device__ __forceinline__ void operator()(int64_t, int, int, const bf16x8& g, const bf16x8& v, const float (&sc)[8],
                                              const float (&sh)[8], float (&dz)[8], float (&s1)[8]) const {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float gf = bf2f(g[e]), d = hswish_d(fmaf(bf2f(v[e]), sc[e], sh[e]));
+      const float gf = bf2f(g[e]), d = Act::d(fmaf(bf2f(v[e]), sc[e], sh[e]));
       dz[e] = gf * d;
       s1[e] = fmaf(gf, d, s1[e]);     // the product fused into the sum, dz rounded on its own
     }
@@ -366,10 +376,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
   });
 }
 
-// out = hswish(y*scale + shift)
-__global__ __launch_bounds__(256) void bn_hswish_fwd_kernel(const bf16* __restrict__ y, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, bf16* __restrict__ out,
-                                                            int64_t M, int C, int cge, int rpb) {
+// out = Act::f(y*scale + shift)
+template <class Act>
+__global__ __launch_bounds__(256) void bn_maskless_fwd_kernel(const bf16* __restrict__ y, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, bf16* __restrict__ out,
+                                                              int64_t M, int C, int cge, int rpb) {
   rows_map(grid_rows(M, rpb), C, C, cge, rpb, [&](int cg) TOK_ROW_INLINE {
     float sc[8], sh[8];
     load8f(scale + cg * 8, sc);
@@ -378,7 +389,7 @@ __global__ __launch_bounds__(256) void bn_hswish_fwd_kernel(const bf16* __restri
       const bf16x8 v = ldg16(y + off);
       bf16x8 o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = f2bf(hswish_f(fmaf(bf2f(v[e]), sc[e], sh[e])));
+      for (int e = 0; e < 8; ++e) o[e] = f2bf(Act::f(fmaf(bf2f(v[e]), sc[e], sh[e])));
       stg16(out + off, o);
     };
   });
@@ -748,40 +759,69 @@ extern "C" int tok_bn_bwd_apply(const void* dout, const void* y, const uint8_t* 
 }
 
 
-// ---- hard-swish units: the ReLU path's geometry, block caps and partial-row layout with the hard-swish rule ------------------
+// ---- mask-less units (hard-swish, ReLU6): the ReLU path's geometry, block caps and partial-row layout with the activation's rule
+template <class Act>
+static int maskless_fwd(const char* name, const void* y, const float* scale, const float* shift, void* out, int64_t m, int c,
+                        void* stream) {
+  TOK_CHECK_ARG(y && scale && shift && out && m > 0 && c > 0 && c % 8 == 0, "%s: bad args", name);
+  if (tok_dbg_skip(8)) return TOK_OK;
+  const Geo g = make_geo(c);
+  hipLaunchKernelGGL(bn_maskless_fwd_kernel<Act>, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)y, scale, shift, (bf16*)out, m, c, g.cge, g.rpb);
+  TOK_CHECK_LAUNCH(name);
+  return TOK_OK;
+}
+
+template <class Act>
+static int maskless_bwd_reduce(const char* name, const void* dout, const void* y, const float* scale, const float* shift,
+                               const float* mean, const float* rstd, int64_t m, int c, float* partial, void* stream) {
+  TOK_CHECK_ARG(dout && y && scale && shift && mean && rstd && partial, "%s: null pointer", name);
+  TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "%s: bad sizes", name);
+  const Geo g = make_geo(c);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<MasklessD<Act>>, dim3(row_blocks(m, g, kReduceCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)dout, (const bf16*)y, MasklessD<Act>{}, scale, shift, mean, rstd, m, c, g.cge, g.rpb, partial);
+  TOK_CHECK_LAUNCH(name);
+  return TOK_OK;
+}
+
+template <class Act>
+static int maskless_bwd_apply(const char* name, const void* dout, const void* y, const float* scale, const float* shift,
+                              const float* coef, void* dy, int64_t m, int c, void* stream) {
+  TOK_CHECK_ARG(dout && y && scale && shift && coef && dy, "%s: null pointer", name);
+  TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "%s: bad sizes", name);
+  if (tok_dbg_skip(8)) return TOK_OK;
+  const Geo g = make_geo(c);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel<MasklessD<Act>>, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)dout, (const bf16*)y, MasklessD<Act>{}, scale, shift, coef, (bf16*)dy, (bf16*)nullptr, 0, m, c,
+                     g.cge, g.rpb);
+  TOK_CHECK_LAUNCH(name);
+  return TOK_OK;
+}
+
 extern "C" int tok_bn_hswish_fwd(const void* y, const float* scale, const float* shift, void* out, int64_t m, int c,
                                  void* stream) {
-  TOK_CHECK_ARG(y && scale && shift && out && m > 0 && c > 0 && c % 8 == 0, "tok_bn_hswish_fwd: bad args");
-  if (tok_dbg_skip(8)) return TOK_OK;
-  const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_hswish_fwd_kernel, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)y, scale, shift, (bf16*)out, m, c, g.cge, g.rpb);
-  TOK_CHECK_LAUNCH("tok_bn_hswish_fwd");
-  return TOK_OK;
+  return maskless_fwd<Hswish>("tok_bn_hswish_fwd", y, scale, shift, out, m, c, stream);
 }
-
 extern "C" int tok_bn_hswish_bwd_reduce(const void* dout, const void* y, const float* scale, const float* shift,
                                         const float* mean, const float* rstd, int64_t m, int c, float* partial, void* stream) {
-  TOK_CHECK_ARG(dout && y && scale && shift && mean && rstd && partial, "tok_bn_hswish_bwd_reduce: null pointer");
-  TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "tok_bn_hswish_bwd_reduce: bad sizes");
-  const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel<HswishD>, dim3(row_blocks(m, g, kReduceCap)), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)dout, (const bf16*)y, HswishD{}, scale, shift, mean, rstd, m, c, g.cge, g.rpb, partial);
-  TOK_CHECK_LAUNCH("tok_bn_hswish_bwd_reduce");
-  return TOK_OK;
+  return maskless_bwd_reduce<Hswish>("tok_bn_hswish_bwd_reduce", dout, y, scale, shift, mean, rstd, m, c, partial, stream);
 }
-
 extern "C" int tok_bn_hswish_bwd_apply(const void* dout, const void* y, const float* scale, const float* shift,
                                        const float* coef, void* dy, int64_t m, int c, void* stream) {
-  TOK_CHECK_ARG(dout && y && scale && shift && coef && dy, "tok_bn_hswish_bwd_apply: null pointer");
-  TOK_CHECK_ARG(m > 0 && c > 0 && c % 8 == 0, "tok_bn_hswish_bwd_apply: bad sizes");
-  if (tok_dbg_skip(8)) return TOK_OK;
-  const Geo g = make_geo(c);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<HswishD>, dim3(row_blocks(m, g, kStreamCap)), dim3(256), 0, tok_stream(stream),
-                     (const bf16*)dout, (const bf16*)y, HswishD{}, scale, shift, coef, (bf16*)dy, (bf16*)nullptr, 0, m, c,
-                     g.cge, g.rpb);
-  TOK_CHECK_LAUNCH("tok_bn_hswish_bwd_apply");
-  return TOK_OK;
+  return maskless_bwd_apply<Hswish>("tok_bn_hswish_bwd_apply", dout, y, scale, shift, coef, dy, m, c, stream);
+}
+
+extern "C" int tok_bn_relu6_fwd(const void* y, const float* scale, const float* shift, void* out, int64_t m, int c,
+                                void* stream) {
+  return maskless_fwd<Relu6>("tok_bn_relu6_fwd", y, scale, shift, out, m, c, stream);
+}
+extern "C" int tok_bn_relu6_bwd_reduce(const void* dout, const void* y, const float* scale, const float* shift,
+                                       const float* mean, const float* rstd, int64_t m, int c, float* partial, void* stream) {
+  return maskless_bwd_reduce<Relu6>("tok_bn_relu6_bwd_reduce", dout, y, scale, shift, mean, rstd, m, c, partial, stream);
+}
+extern "C" int tok_bn_relu6_bwd_apply(const void* dout, const void* y, const float* scale, const float* shift,
+                                      const float* coef, void* dy, int64_t m, int c, void* stream) {
+  return maskless_bwd_apply<Relu6>("tok_bn_relu6_bwd_apply", dout, y, scale, shift, coef, dy, m, c, stream);
 }
 
 // ---- completion events carried by a launch (two-stream schedule without record packets) ------------------------------------

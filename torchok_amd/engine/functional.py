@@ -13,7 +13,8 @@ gconv_bn_act              grouped 3x3 conv -> batch_norm -> relu         ([timm]
 squeeze_excite            x * gate(expand(relu(reduce(mean(x)))))        ([timm] efficientnet_blocks.SqueezeExcite;
                           gate = sigmoid or hard sigmoid)
 
-conv_bn_act / dwconv_bn_act take act='hard_swish' (MobileNetV3): the mask-less activation path of csrc/bn.hip.
+conv_bn_act / dwconv_bn_act take act='hard_swish' (MobileNetV3) or act='relu6' (EfficientNet-Lite): the mask-less activation
+path of csrc/bn.hip.
 """
 import weakref
 from typing import Optional
@@ -235,19 +236,29 @@ def _check_conv(conv: nn.Conv2d):
 
 RELU = 'relu'
 HARD_SWISH = 'hard_swish'
+RELU6 = 'relu6'
+# the mask-less activations -> the entry-point family tok_bn_<family>_fwd / _bwd_reduce / _bwd_apply that serves them
+MASKLESS = {HARD_SWISH: 'hswish', RELU6: 'relu6'}
 
 
 def _check_act(relu, act, bn, shortcut=None, pool=False, defer_apply=False):
-    """The unit's one activation, None / RELU / HARD_SWISH, from the public keywords.  act=None: what `relu` says.
-    act='hard_swish' (`relu` is not looked at): BatchNorm + hard-swish on tok_bn_hswish_*, which keeps no mask and knows no
-    shortcut, pooled or deferred form (MobileNetV3 never activates after a residual add)."""
+    """The unit's one activation, None / RELU / HARD_SWISH / RELU6, from the public keywords.  act=None: what `relu` says.
+    act='hard_swish' or 'relu6' (`relu` is not looked at): BatchNorm + that activation on tok_bn_hswish_* / tok_bn_relu6_*,
+    which keep no mask and know no shortcut, pooled or deferred form (MobileNetV3 and EfficientNet-Lite never activate after
+    a residual add)."""
     if act is None:
         return RELU if relu else None
-    if act != HARD_SWISH:
-        raise NotImplementedError(f'torchok_amd activation {act!r}: None (ReLU / identity by `relu`) or {HARD_SWISH!r}')
+    if act not in MASKLESS:
+        raise NotImplementedError(f'torchok_amd activation {act!r}: None (ReLU / identity by `relu`), {HARD_SWISH!r} or {RELU6!r}')
     if bn is None or shortcut is not None or pool or defer_apply:
-        raise NotImplementedError(f"act={HARD_SWISH!r}: BatchNorm units without shortcut, pool or defer_apply only")
-    return HARD_SWISH
+        raise NotImplementedError(f"act={act!r}: BatchNorm units without shortcut, pool or defer_apply only")
+    return act
+
+
+def _maskless(lib, act, stage):
+    """(entry point, its name) of a mask-less activation's `stage`: 'fwd', 'bwd_reduce' or 'bwd_apply'."""
+    name = f'tok_bn_{MASKLESS[act]}_{stage}'
+    return getattr(lib, name), name
 
 
 # ---- the BatchNorm stage of a unit: every "producer -> BatchNorm -> activation" unit takes it from here ---------------
@@ -281,10 +292,11 @@ def bn_coeffs(lib, st, bn, stats, rows, m, kp, dev):
 
 def bn_apply(lib, st, y, scale, shift, act, shortcut, want_mask, m, kp):
     """The plain apply pass out = act(y * scale + shift (+ shortcut)) -> (out_data, mask).  `want_mask` is the caller's
-    rule for keeping the ReLU bits; hard-swish keeps none."""
+    rule for keeping the ReLU bits; hard-swish and ReLU6 keep none."""
     out_data = torch.empty_like(y)
-    if act == HARD_SWISH:
-        _C.check(lib.tok_bn_hswish_fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, kp, st), 'tok_bn_hswish_fwd')
+    if act in MASKLESS:
+        fwd, name = _maskless(lib, act, 'fwd')
+        _C.check(fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, kp, st), name)
         return out_data, None
     mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=y.device) if want_mask else None
     _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), ptr(shortcut.data) if shortcut is not None else None,
@@ -294,7 +306,7 @@ def bn_apply(lib, st, y, scale, shift, act, shortcut, want_mask, m, kp):
 
 class _ConvBnActNode(Node):
     needs_backward = True
-    act = None                      # None / RELU / HARD_SWISH (dz is recomputed from y in tok_bn_hswish_bwd_*: no mask)
+    act = None                      # None / RELU / HARD_SWISH / RELU6 (the last two: dz is recomputed from y, no mask)
     relu = property(lambda self: self.act == RELU)
 
     def __init__(self):
@@ -312,15 +324,15 @@ class _ConvBnActNode(Node):
 
     def wants_fused_bwd_stats(self) -> bool:
         """Can the kernel that completes d(out) also reduce sum(dz), sum(dz*y) for this unit?"""
-        # (the dgrad epilogues know the ReLU mask only: a hard-swish producer takes the stand-alone reduce)
+        # (the dgrad epilogues know the ReLU mask only: a hard-swish or ReLU6 producer takes the stand-alone reduce)
         return (self.bn is not None and self.batch_stats and self.pool is None
                 and (self.act is None or (self.act == RELU and self.mask is not None)))
 
     def _apply_bwd(self, lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp):
         """dy = c1*dz + c2*y + c3 (and the shortcut's dz) for the unit's activation."""
-        if self.act == HARD_SWISH:
-            _C.check(lib.tok_bn_hswish_bwd_apply(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(coef), ptr(dy), m, kp,
-                                                 st), 'tok_bn_hswish_bwd_apply')
+        if self.act in MASKLESS:
+            bwd_apply, name = _maskless(lib, self.act, 'bwd_apply')
+            _C.check(bwd_apply(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(coef), ptr(dy), m, kp, st), name)
         else:
             _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift), ptr(coef),
                                           int(self.relu), ptr(dy), ds_ptr, ds_acc, m, kp, st), 'tok_bn_bwd_apply')
@@ -348,10 +360,11 @@ class _ConvBnActNode(Node):
                 _C.check(lib.tok_bn_pool_bwd_reduce(ptr(g), ptr(self.pool), ptr(self.y), ptr(self.scale), ptr(self.shift),
                                                     ptr(self.mean), ptr(self.rstd), n_, h_, w_, kp, ptr(partial), st),
                          'tok_bn_pool_bwd_reduce')
-            elif self.act == HARD_SWISH:
+            elif self.act in MASKLESS:
                 partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
-                _C.check(lib.tok_bn_hswish_bwd_reduce(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(self.mean),
-                                                      ptr(self.rstd), m, kp, ptr(partial), st), 'tok_bn_hswish_bwd_reduce')
+                bwd_reduce, name = _maskless(lib, self.act, 'bwd_reduce')
+                _C.check(bwd_reduce(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.rstd), m, kp,
+                                    ptr(partial), st), name)
             else:
                 partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
                 _C.check(lib.tok_bn_bwd_reduce(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift),
@@ -409,7 +422,7 @@ class _ConvBnActNode(Node):
 
             def apply(mask, coef, dy):
                 nonlocal apply_event
-                if side and self.pool is None and self.act != HARD_SWISH:
+                if side and self.pool is None and self.act not in MASKLESS:
                     # the weight gradient will be forked to the side stream behind THIS apply pass: the pass carries the
                     # completion event itself (no event-record packet on the main queue)
                     apply_event = self.region.raw_event()     # armed right in front of the launch that carries it (below)
@@ -680,9 +693,9 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
                 act: Optional[str] = None) -> TTensor:
     """out = act(bn(conv(x)) (+ shortcut)).  `conv` is an nn.Conv2d or nn.Linear used purely as
     the parameter container (state_dict names stay those of the reference).
-    act=None: ReLU or no activation, as `relu` says.  act='hard_swish' (BatchNorm, no shortcut / pool / defer_apply): the
-    activation is hard-swish and `relu` is not looked at; the unit keeps y and no mask, its backward recomputes z from y, it never
-    becomes the fused unit 3 and its BatchNorm-backward sums are never taken by a consumer's data gradient.
+    act=None: ReLU or no activation, as `relu` says.  act='hard_swish' / 'relu6' (BatchNorm, no shortcut / pool / defer_apply):
+    the activation is hard-swish / ReLU6 and `relu` is not looked at; the unit keeps y and no mask, its backward recomputes z
+    from y, it never becomes the fused unit 3 and its BatchNorm-backward sums are never taken by a consumer's data gradient.
     pool=True (BatchNorm + ReLU, no shortcut): out = maxpool3x3/s2/p1(act(bn(conv(x)))) with the activated map never
     stored (the ResNet stem when only the pooled map is consumed).
     defer_apply=True (BatchNorm, no activation, no shortcut — the last unit of an HRNet fuse path): the apply pass is NOT run;
@@ -716,7 +729,7 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     kp = pad8(k_real)
     if bn is not None and bn.num_features != k_real:
         raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {k_real}')
-    if (FUSE_UNIT3 and bn is not None and act != HARD_SWISH and (relu == (shortcut is not None)) and not pool
+    if (FUSE_UNIT3 and bn is not None and act not in MASKLESS and (relu == (shortcut is not None)) and not pool
             and isinstance(conv, nn.Conv2d)
             and r == 1 and s == 1 and stride == 1 and pad == 0 and conv.bias is None and x.data.dim() == 4
             and x.c == x.cp and kp == k_real and x.cp <= 1024 and (shortcut is None or shortcut.cp == kp)
@@ -1138,7 +1151,7 @@ class _DwConvBnActNode(_SameWidthConvBnActNode):
 def dwconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True,
                   act: Optional[str] = None) -> TTensor:
     """out = act(bn(conv(x))) for a depthwise `conv` ([timm] create_conv2d(depthwise=True) + BatchNormAct2d of the MnasNet
-    and MobileNetV3 blocks).  act=None: `relu` decides; act='hard_swish': as in conv_bn_act.  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
+    and MobileNetV3 blocks).  act=None: `relu` decides; act='hard_swish' / 'relu6': as in conv_bn_act.  Training-mode BatchNorm takes its statistics from the convolution launch (tok_dwconv_fwd leaves the partial
     rows tok_bn_finalize folds); eval mode uses the running statistics; track_running_stats=False uses batch statistics."""
     act = _check_act(relu, act, bn)
     _check_dwconv(conv, x)
@@ -1212,7 +1225,7 @@ class _GConvBnActNode(_SameWidthConvBnActNode):
 def gconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool = True,
                  act: Optional[str] = None) -> TTensor:
     """out = act(bn(conv(x))) for a grouped 3x3 `conv` ([timm] Bottleneck.conv2 + bn2 + act2 of the ResNeXts).  act=None: `relu`
-    decides; act='hard_swish': as in conv_bn_act.  The kernels read the fp32 master itself (rounded to bf16 as a wave builds its
+    decides; act='hard_swish' / 'relu6': as in conv_bn_act.  The kernels read the fp32 master itself (rounded to bf16 as a wave builds its
     fragments): there is no packed copy that an optimizer step could leave stale.  The BatchNorm stage is dwconv_bn_act's.  The
     output carries no `colsum_part`: a fused residual unit that consumes it sums the columns itself (_unit3_forward)."""
     act = _check_act(relu, act, bn)

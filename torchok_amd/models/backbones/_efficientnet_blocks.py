@@ -60,13 +60,39 @@ def decode_block_str(block_str: str, unsupported, block_types=('ds', 'ir'), nre=
     return args, int(opts.get('r', 1))
 
 
-def decode_arch_def(arch_def, unsupported, block_types=('ds', 'ir'), nre=False) -> List[List[dict]]:
+def scale_stage_depth(repeats: List[int], depth_multiplier=1.0, depth_trunc='ceil') -> List[int]:
+    """[timm] _scale_stage_depth: the repeats of one stage's block definitions under a depth multiplier.  The scaled total of
+    the stage is ceil (or round) of sum(repeats) * multiplier; it is handed out from the last definition to the first, each
+    taking its share of what is left (at least 1), so the first definition is the least likely to grow."""
+    num_repeat = sum(repeats)
+    if depth_trunc == 'round':
+        num_repeat_scaled = max(1, round(num_repeat * depth_multiplier))
+    else:
+        num_repeat_scaled = int(math.ceil(num_repeat * depth_multiplier))
+    scaled = []
+    for r in reversed(repeats):
+        rs = max(1, round(r / num_repeat * num_repeat_scaled))
+        scaled.append(rs)
+        num_repeat -= r
+        num_repeat_scaled -= rs
+    return scaled[::-1]
+
+
+def decode_arch_def(arch_def, unsupported, block_types=('ds', 'ir'), nre=False, depth_multiplier=1.0, depth_trunc='ceil',
+                    fix_first_last=False) -> List[List[dict]]:
+    """[timm] decode_arch_def.  `depth_multiplier` scales every stage's repeats (scale_stage_depth), except the first and the
+    last stage under `fix_first_last`; at the default 1.0 a stage keeps the repeats its strings name."""
+    if depth_trunc not in ('ceil', 'round'):
+        unsupported(f'depth_trunc={depth_trunc!r}')
     stages = []
-    for stack in arch_def:
+    for stack_idx, stack in enumerate(arch_def):
+        decoded = [decode_block_str(block_str, unsupported, block_types, nre) for block_str in stack]
+        repeats = [r for _, r in decoded]
+        if depth_multiplier != 1.0 and not (fix_first_last and stack_idx in (0, len(arch_def) - 1)):
+            repeats = scale_stage_depth(repeats, depth_multiplier, depth_trunc)
         blocks = []
-        for block_str in stack:
-            args, repeats = decode_block_str(block_str, unsupported, block_types, nre)
-            blocks.extend(dict(args) for _ in range(repeats))
+        for (args, _), rep in zip(decoded, repeats):
+            blocks.extend(dict(args) for _ in range(rep))
         stages.append(blocks)
     return stages
 

@@ -1,14 +1,17 @@
-"""MnasNet backbones on the MI355X engine.
+"""MnasNet and EfficientNet-Lite backbones on the MI355X engine.
 
 Mirrors the reference wiring ``torchok/models/backbones/efficientnet.py``: ``EfficientNet`` (:506-575), ``_gen_mnasnet_a1`` /
-``_b1`` / ``_small`` (:583-681) and the MnasNet entry points (:1181-1254), with the [timm 0.6.13] ``decode_arch_def``,
+``_b1`` / ``_small`` (:583-681) and the MnasNet entry points (:1181-1254), ``_gen_efficientnet_lite`` (:890-928) and the five
+EfficientNet-Lite entry points (:1528-1569), with the [timm 0.6.13] ``decode_arch_def``,
 ``EfficientNetBuilder``, ``DepthwiseSeparableConv``, ``InvertedResidual``, ``SqueezeExcite``, ``round_channels`` and
 ``_init_weight_goog`` semantics restated in ``_efficientnet_blocks.py``.  Module / parameter names are those of timm, so reference checkpoints load.
 
 The blocks, the block-string decoder and the builder are those of ``_efficientnet_blocks.py``, shared with ``mobilenetv3.py``;
-this family takes them with their defaults: ReLU, the 'ds' / 'ir' block types without the 'nre' option, the sigmoid
-squeeze-excite on the block input's width (``se_from_exp=False``), no stem feature.  The SiLU / ReLU6 families (EfficientNet,
-MobileNetV2, FBNet) stay unregistered.
+MnasNet takes them with their defaults: ReLU, the 'ds' / 'ir' block types without the 'nre' option, the sigmoid
+squeeze-excite on the block input's width (``se_from_exp=False``), no stem feature.  EfficientNet-Lite has no squeeze-excite
+and runs the stem, every block and the head with ReLU6 (``act='relu6'``, the mask-less path of csrc/bn.hip); its stage depths
+follow the decoder's depth multiplier with the first and the last stage fixed.  The SiLU families and the other ReLU6 ones
+(EfficientNet B*, MobileNetV2, FBNet, the ``tf_*`` Lite variants with their asymmetric "same" padding) stay unregistered.
 """
 from typing import List
 
@@ -20,16 +23,28 @@ from ...constructor import BACKBONES
 from ...engine import functional as EF
 from ..base import BaseBackbone
 from ._efficientnet_blocks import DepthwiseSeparableConv, InvertedResidual, SqueezeExcite  # noqa: F401  (the family's blocks)
-from ._efficientnet_blocks import build_blocks, decode_arch_def, init_weight_goog, round_channels
+from ._efficientnet_blocks import _act_kw, build_blocks, decode_arch_def, init_weight_goog, round_channels
 
 
 def _unsupported(what: str):
-    raise NotImplementedError(f'torchok_amd MnasNet: {what} not built')
+    raise NotImplementedError(f'torchok_amd MnasNet / EfficientNet-Lite: {what} not built')
+
+
+_ACT_LAYERS = {None: None, nn.ReLU: None, 'relu': None, nn.ReLU6: EF.RELU6, 'relu6': EF.RELU6}
+
+
+def _resolve_act_layer(act_layer):
+    """The blocks' `act` of an `act_layer`: None (ReLU) or EF.RELU6; nothing else is built."""
+    try:
+        return _ACT_LAYERS[act_layer]
+    except (KeyError, TypeError):
+        _unsupported(f'act_layer={act_layer}')
 
 
 class EfficientNet(BaseBackbone):
-    """The MnasNet members of the reference's EfficientNet family: stem conv 3x3/s2 + bn + ReLU, the 'ds' / 'ir' stages,
-    1x1 head conv + bn + ReLU to `num_features` channels."""
+    """The MnasNet and EfficientNet-Lite members of the reference's EfficientNet family: stem conv 3x3/s2 + bn + act, the
+    'ds' / 'ir' stages, 1x1 head conv + bn + act to `num_features` channels; act is ReLU or ReLU6 (`act_layer`), one for the
+    stem, the blocks and the head."""
 
     def __init__(self, block_args, num_features=1280, in_channels=3, stem_size=32, fix_stem=False, output_stride=32,
                  pad_type='', round_chs_fn=round_channels, act_layer=None, norm_layer=None, se_layer=None,
@@ -39,8 +54,7 @@ class EfficientNet(BaseBackbone):
             _unsupported(f'drop_path_rate={drop_path_rate}')
         if output_stride != 32:
             _unsupported(f'output_stride={output_stride}')
-        if act_layer not in (None, nn.ReLU):
-            _unsupported(f'act_layer={act_layer}')
+        self.act = _resolve_act_layer(act_layer)
         if norm_layer is not None and not (norm_layer is nn.BatchNorm2d or getattr(norm_layer, 'func', None) is nn.BatchNorm2d):
             _unsupported(f'norm_layer={norm_layer}')
         if pad_type not in ('', None) or se_layer is not None:
@@ -50,7 +64,7 @@ class EfficientNet(BaseBackbone):
             stem_size = round_chs_fn(stem_size)
         self.conv_stem = nn.Conv2d(in_channels, stem_size, 3, stride=2, padding=1, bias=False)
         self.bn1 = nn.BatchNorm2d(stem_size)
-        stages, self.feature_info, head_chs = build_blocks(stem_size, block_args, round_chs_fn)
+        stages, self.feature_info, head_chs = build_blocks(stem_size, block_args, round_chs_fn, act=self.act)
         self.blocks = nn.Sequential(*stages)
         self.conv_head = nn.Conv2d(head_chs, self.num_features, 1, bias=False)
         self.bn2 = nn.BatchNorm2d(self.num_features)
@@ -64,7 +78,7 @@ class EfficientNet(BaseBackbone):
 
     def _run(self, r, x: torch.Tensor, all_features: bool):
         t = r.input(x, c_pad_to=4 if x.shape[1] <= 4 else 8)
-        t = EF.conv_bn_act(r, t, self.conv_stem, self.bn1, relu=True)
+        t = EF.conv_bn_act(r, t, self.conv_stem, self.bn1, **_act_kw(False, self.act))
         wanted = {f['module'] for f in self.feature_info}
         feats = []
         for si, stage in enumerate(self.blocks):
@@ -73,7 +87,7 @@ class EfficientNet(BaseBackbone):
                 if all_features and f'blocks.{si}.{bi}' in wanted:
                     feats.append(t)
         if not all_features:
-            feats.append(EF.conv_bn_act(r, t, self.conv_head, self.bn2, relu=True))
+            feats.append(EF.conv_bn_act(r, t, self.conv_head, self.bn2, **_act_kw(False, self.act)))
         return feats
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -137,3 +151,33 @@ semnasnet_100 = _entry('semnasnet_100', _MNASNET_A1, 32, 1.0, 'MNASNet A1 (w/ SE
 mnasnet_a1 = _entry('mnasnet_a1', _MNASNET_A1, 32, 1.0, 'MNASNet A1 (w/ SE), depth multiplier of 1.0 (= semnasnet_100)')
 semnasnet_140 = _entry('semnasnet_140', _MNASNET_A1, 32, 1.4, 'MNASNet A1 (w/ SE), depth multiplier of 1.4')
 mnasnet_small = _entry('mnasnet_small', _MNASNET_SMALL, 8, 1.0, 'MNASNet Small, depth multiplier of 1.0')
+
+
+# ---- EfficientNet-Lite: no squeeze-excite, ReLU6, fixed stem and head -----------------------------------------------------
+_EFFICIENTNET_LITE = [['ds_r1_k3_s1_e1_c16'], ['ir_r2_k3_s2_e6_c24'], ['ir_r2_k5_s2_e6_c40'], ['ir_r3_k3_s2_e6_c80'],
+                      ['ir_r3_k5_s1_e6_c112'], ['ir_r4_k5_s2_e6_c192'], ['ir_r1_k3_s1_e6_c320']]
+
+
+def _gen_efficientnet_lite(variant, channel_multiplier=1.0, depth_multiplier=1.0, pretrained=False, **kwargs):
+    def round_chs_fn(c):
+        return round_channels(c, multiplier=channel_multiplier)
+    kwargs.setdefault('act_layer', 'relu6')
+    block_args = decode_arch_def(_EFFICIENTNET_LITE, _unsupported, depth_multiplier=depth_multiplier, fix_first_last=True)
+    return _create_effnet(variant, pretrained, block_args=block_args, num_features=1280, stem_size=32, fix_stem=True,
+                          round_chs_fn=round_chs_fn, **kwargs)
+
+
+def _lite_entry(name, channel_multiplier, depth_multiplier):
+    def entry(pretrained=False, **kwargs):
+        return _gen_efficientnet_lite(name, channel_multiplier, depth_multiplier, pretrained, **kwargs)
+    entry.__name__ = entry.__qualname__ = name
+    entry.__doc__ = (f'EfficientNet-Lite{name[-1]}: channel multiplier {channel_multiplier}, depth multiplier {depth_multiplier} '
+                     f'(efficientnet.py:1528-1569)')
+    return BACKBONES.register_class(entry)
+
+
+efficientnet_lite0 = _lite_entry('efficientnet_lite0', 1.0, 1.0)
+efficientnet_lite1 = _lite_entry('efficientnet_lite1', 1.0, 1.1)
+efficientnet_lite2 = _lite_entry('efficientnet_lite2', 1.1, 1.2)
+efficientnet_lite3 = _lite_entry('efficientnet_lite3', 1.2, 1.4)
+efficientnet_lite4 = _lite_entry('efficientnet_lite4', 1.4, 1.8)
