@@ -309,6 +309,10 @@ int tok_bn_relu6_bwd_apply(const void* dout, const void* y, const float* scale, 
 /* ---- pooling ----------------------------------------------------------------------------
  * aten::max_pool2d(3, stride 2, pad 1) at resnet.py:510; adaptive avg pool + flatten at
  * poolings/classification/pooling.py:7-12 ([timm] SelectAdaptivePool2d).                   */
+/* NHWC bf16, c % 8 == 0, every extent > 0 (else TOK_ERR_INVALID before any launch).  argmax uint8 [n][P][Q][c] = tap r * 3 + s of
+ * the first maximum in (r, s) order over the in-bounds taps; a NaN beats every number and a later NaN an earlier one (ATen's
+ * `val > max || isnan(val)`), so with NaN in a window the LAST NaN is recorded; a window of -inf alone records its first
+ * in-bounds tap.  The backward routes each dy to the recorded tap (<= 4 terms per pixel, fp32) and adds dx when accumulate.  */
 int tok_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* argmax, int n, int h, int w, int c,
                          void* stream);
 int tok_maxpool3x3s2_bwd(const void* dy, const uint8_t* argmax, void* dx, int accumulate,
@@ -321,13 +325,16 @@ int tok_gap_fwd(const void* x, void* y, int n, int hw, int c, void* stream);
 int tok_gap_bwd(const void* dy, void* dx, int accumulate, int n, int hw, int c, void* stream);
 /* SelectAdaptivePool2d(1, pool_type) beyond 'avg' ([timm] adaptive_avgmax_pool; reference
  * poolings/classification/pooling.py:7-12): mode 1 'max', 2 'avgmax' = 0.5 * (avg + max), 3 'catavgmax' = cat(avg, max)
- * (y row = [avg(c) | max(c)], needs ldy >= 2c).  argmax [n][c] int32 = first maximal pixel per (image, channel), the
- * index-exact route of the max gradient (ATen adaptive_max_pool2d_backward).                                            */
+ * (y row = [avg(c) | max(c)], needs ldy >= 2c; ldy % 8 == 0 always; columns past those written are left alone).  argmax [n][c]
+ * int32 = first maximal pixel per (image, channel), the index-exact route of the max gradient (ATen
+ * adaptive_max_pool2d_backward); with NaN in a channel the LAST NaN pixel (`val > max || isnan(val)`), pixel 0 for a channel of
+ * -inf alone.  avgmax follows the bf16 chain of autocast: 0.5 * bf16(bf16(avg) + bf16(max)).                              */
 int tok_global_pool_fwd(const void* x, void* y, int* argmax, int n, int hw, int c, int ldy, int mode, void* stream);
 int tok_global_pool_bwd(const void* dy, const int* argmax, void* dx, int accumulate, int n, int hw, int c, int ldy,
                         int mode, void* stream);
 
-/* column sums of a bf16 [m][n] matrix -> fp32 (bias gradients of Linear / biased conv)     */
+/* column sums of a bf16 [m][n_pad] matrix -> fp32 (bias gradients of Linear / biased conv): out[0 .. n_real) written (added to when
+ * accumulate), the rest of out left alone; m > 0, n_pad % 8 == 0, 0 < n_real <= n_pad, else TOK_ERR_INVALID                 */
 int tok_colsum(const void* dy, int64_t m, int n_pad, int n_real, float* out, int accumulate,
                void* stream);
 
@@ -831,7 +838,11 @@ int tok_retrieval_eval(int kind, const int64_t* idx, int kk, const uint8_t* drop
 /* ---- optimizers (flat arenas) -------------------------------------------------------------
  * torch.optim.SGD / Adam / AdamW registered at optim/optimizers/__init__.py:11,13,18 and
  * built by Constructor.create_optimizer (constructor/constructor.py:151-158).  One launch
- * updates `count` contiguous fp32 parameters and rewrites their bf16 shadow.               */
+ * updates `count` contiguous fp32 parameters and rewrites their bf16 shadow (shadow_bf16 may be NULL: no shadow is kept).
+ * Hyper-parameters are floats and are used as given: 1 - beta2 is formed from float(beta2).  Refused with TOK_ERR_INVALID before
+ * any launch: a NULL param / grad / state array that the configuration uses (momentum != 0 needs momentum_buf, Adam both
+ * moments, RMSprop square_avg, momentum > 0 momentum_buf, centered grad_avg), count == 0, tok_adam_step with step < 1.
+ * tok_sgd_step: first_step != 0 sets the momentum buffer to the gradient (torch's buffer initialisation).                  */
 int tok_sgd_step(float* param, const float* grad, float* momentum_buf, void* shadow_bf16,
                  size_t count, float lr, float momentum, float dampening, float weight_decay,
                  int nesterov, int first_step, int maximize, void* stream);

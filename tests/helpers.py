@@ -135,10 +135,13 @@ def assert_bounded(mine, ref, mag, a, b, what='', test=None):
     return worst
 
 
-_INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8}
-SENTINEL = {torch.bfloat16: 0x5A5B, torch.float32: 0x5A5B5C5D, torch.uint8: 0x5A}   # finite, ~1e16: no kernel here produces these bits
+_INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8,
+           torch.int32: torch.int32, torch.int64: torch.int64}
+SENTINEL = {torch.bfloat16: 0x5A5B, torch.float32: 0x5A5B5C5D, torch.uint8: 0x5A,   # finite, ~1e16: no kernel here produces these bits
+            torch.float16: 0x5A5B, torch.int32: 0x5A5B5C5D, torch.int64: 0x5A5B5C5D5E5F6061}
 BF16_NAN = 0x7FC1
-NAN_BITS = {torch.bfloat16: BF16_NAN, torch.float32: 0x7FC00001, torch.uint8: 0xFF}   # (bytes: every mask bit set)
+NAN_BITS = {torch.bfloat16: BF16_NAN, torch.float32: 0x7FC00001, torch.uint8: 0xFF,   # (bytes: every mask bit set)
+            torch.float16: 0x7E01, torch.int32: 0x7FC00001, torch.int64: 0x7FC000017FC00001}   # (integers: an index far outside)
 
 
 class Guarded:

@@ -5,7 +5,8 @@
 namespace {
 
 // One thread = one output pixel x 8 channels.  argmax = tap index r*3+s of the FIRST maximum in
-// (r, s) scan order over the in-bounds taps; NaN wins (aten max_pool2d: `val > max || isnan(val)`).
+// (r, s) scan order over the in-bounds taps; NaN wins, and among several the LAST one (aten max_pool2d:
+// `val > max || isnan(val)`); a window of -inf alone reports its first in-bounds tap.
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const bf16* __restrict__ x, bf16* __restrict__ y,
                                                           uint8_t* __restrict__ argmax, int N, int H,
                                                           int W, int C, int P, int Q) {
@@ -475,7 +476,7 @@ extern "C" int tok_global_pool_bwd(const void* dy, const int* argmax, void* dx, 
 
 extern "C" int tok_colsum(const void* dy, int64_t m, int n_pad, int n_real, float* out, int accumulate,
                           void* stream) {
-  TOK_CHECK_ARG(dy && out && m > 0 && n_pad > 0 && n_pad % 8 == 0 && n_real <= n_pad, "tok_colsum: bad args");
+  TOK_CHECK_ARG(dy && out && m > 0 && n_pad > 0 && n_pad % 8 == 0 && n_real > 0 && n_real <= n_pad, "tok_colsum: bad args");
   hipLaunchKernelGGL(colsum_kernel, dim3(n_pad / 8), dim3(256), 0, tok_stream(stream), (const bf16*)dy, m,
                      n_pad, n_real, out, accumulate);
   TOK_CHECK_LAUNCH("tok_colsum");
