@@ -1,4 +1,4 @@
-"""fp64 references of the loss and metric-count entries of csrc/loss.hip (include/tok.h) on the same bf16-rounded inputs, the
+"""fp64 references of the loss entries of csrc/loss_*.hip and the metric-count entries of csrc/metric.hip (include/tok.h) on the same bf16-rounded inputs, the
 bounds of their contracts, the input makers, and plain fp32 runs of the same formulas (tests/test_loss_ref.py: an fp32 run
 stays inside half of every bound, deliberately wrong variants do not pass).  Everything is plain torch and runs on the device of
 its inputs (the GPU module keeps the large cases on the device in float64).

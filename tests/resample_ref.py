@@ -1,4 +1,4 @@
-"""fp64 reference of the multi-resolution glue (csrc/resample.hip): bilinear interpolation with align_corners=False, its exact
+"""fp64 reference of the multi-resolution glue (csrc/resample.hip, fuse_sum.hip, neck_resample.hip): bilinear interpolation with align_corners=False, its exact
 transpose, and the HRNet fuse sum with its backward.  Plain torch, no GPU needed (every function follows the device of its
 operand, so the past-2^31 cases evaluate it on the device from slices).  NHWC throughout: x is [n][h][w][c].
 

@@ -841,7 +841,7 @@ def test_bce_logits_ignore(libs, rows, classes, ld, mean):
     assert ld == classes or float(dv[id(dz)][:, classes:].abs().max()) == 0.0
 
 
-# ---- multi-resolution glue (resample.hip) ------------------------------------------------------------------
+# ---- multi-resolution glue (resample.hip, fuse_sum.hip, neck_resample.hip) ---------------------------------
 @pytest.mark.parametrize('n,h,w,c,shifts,relu', [(2, 16, 16, 16, (0, 1, 2, 3), 1), (2, 8, 24, 48, (0, 0, 1), 1),
                                                (1, 32, 32, 32, (0, 0), 1), (3, 8, 8, 64, (0, 2), 0)])
 def test_fuse_sum_relu(libs, n, h, w, c, shifts, relu):

@@ -1,4 +1,4 @@
-"""The loss and metric-count entries of csrc/loss.hip element by element against fp64 of the same bf16 inputs; references, bounds
+"""The loss entries of csrc/loss_*.hip and the metric-count entries of csrc/metric.hip element by element against fp64 of the same bf16 inputs; references, bounds
 and input makers are in tests/loss_ref.py (tests/test_loss_ref.py: an fp32 run stays inside half of every bound).
 
 Every case states which kernel or reduction class it is meant to run, and asserts it against a restatement of the launcher's

@@ -1,4 +1,4 @@
-"""Kernel contract of tok_nearest_fwd/_bwd (csrc/nearest.hip), element by element.  The forward is a copy: bit for bit
+"""Kernel contract of tok_nearest_fwd/_bwd (csrc/resample.hip), element by element.  The forward is a copy: bit for bit
 F.interpolate(mode='nearest') of the source, placed at ch_off, every other element of dst untouched.  The backward is its
 transpose: bit for bit the fp64 transpose on small-integer gradients (the sums are exact), within one bf16 rounding of the
 result plus the fp32 accumulation on reals, with and without `accumulate`; sources no destination maps to get exact zeros;

@@ -1,4 +1,4 @@
-"""Kernel contract of the bilinear gather pair and the HRNet fuse pair (csrc/resample.hip), element by element against the fp64
+"""Kernel contract of the bilinear gather pair and the HRNet fuse pair (csrc/resample.hip, csrc/fuse_sum.hip), element by element against the fp64
 reference of tests/resample_ref.py.  Operands sit in helpers.Guarded buffers: input pads and guard rows hold NaN, output pads
 and guard rows hold sentinels that are checked after the call; the channels of dst outside [ch_off, ch_off + c) keep their
 sentinel, the channels of ddst outside it hold NaN and no NaN reaches dsrc.

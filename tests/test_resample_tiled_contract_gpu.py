@@ -1,4 +1,4 @@
-"""Kernel contract of tok_bilinear_sum_stats and tok_bilinear_bwd_multi (csrc/resample.hip: the tiled LDS kernels of the commuted
+"""Kernel contract of tok_bilinear_sum_stats and tok_bilinear_bwd_multi (csrc/neck_resample.hip: the tiled LDS kernels of the commuted
 HRNet neck and the generic kernels behind them), element by element against the fp64 reference of tests/resample_ref.py — not
 against tok_bilinear_bwd, which shares src_index with them.
 

@@ -1,4 +1,4 @@
-// Accuracy of the device math functions the loss kernels (torchok_amd/csrc/loss.hip) call, against fp64 on the host, over the
+// Accuracy of the device math functions the loss kernels (torchok_amd/csrc/loss_*.hip) call, against fp64 on the host, over the
 // argument ranges those kernels feed them: expf / __expf on v - max in [-104, 0], logf / __logf on a sum of exponentials in
 // [1, 1024], log1pf on exp(-|x|) in (0, 1]; expf also on [0, 88], the arguments of the sigmoids 1 / (1 + expf(-z)).
 // Prints one JSON line; tests/loss_ref.py carries the maxima with a 2x margin.

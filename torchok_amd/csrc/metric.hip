@@ -4,6 +4,7 @@
 //   ArcFace margin fwd/bwd on the cosine matrix                              arcface_head.py:95-108
 //   relevance matrix R[i][j] = (label_i == label_j)                          pairwise_task.py:87-107
 //   contrastive loss fwd/bwd over pairwise Euclidean distances               pairwise.py:126-136 (torch.cdist)
+//   classification counts / confusion matrix for the on-device metrics       (at the end of the file)
 // One wavefront per row, 64-lane butterflies, fp32 math.
 #include "tok_common.h"
 #include <math.h>
@@ -504,5 +505,73 @@ extern "C" int tok_triplet_bwd(const void* anchor, const void* positive, const v
                      (const bf16*)positive, (const bf16*)negative, dist, gscale, rows, d, ld, margin, eps, swap,
                      (bf16*)d_anchor, (bf16*)d_positive, (bf16*)d_negative);
   TOK_CHECK_LAUNCH("tok_triplet_bwd");
+  return TOK_OK;
+}
+
+namespace {
+// classification statistics for the on-device metrics: per class c: counts[0][c] += [argmax == c == target],
+// counts[1][c] += [argmax == c], counts[2][c] += [target == c]  (int64 atomics: exact, order-independent)
+__global__ __launch_bounds__(256) void cls_stats_kernel(const bf16* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                        const int64_t* __restrict__ target, int64_t rows, int classes,
+                                                        int ld, int64_t ignore_index, unsigned long long* counts,
+                                                        unsigned long long* confusion) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (int64_t)gridDim.x * 4) {
+    const int64_t t = target[row];
+    if (t == ignore_index || t < 0 || t >= classes) continue;
+    int pred;
+    if (labels != nullptr) {       // compared as int64: a label such as 2^40 must not wrap into a class index
+      const int64_t p64 = labels[row];
+      pred = (p64 >= 0 && p64 < (int64_t)classes) ? (int)p64 : -1;
+    } else {                       // first maximum, as torch.argmax
+      // a lane that owns a column starts from that column's index, so a row of -inf (a fully masked row) resolves to
+      // column 0 like any other row of equal logits; only a lane without a column keeps the index that cannot win
+      float best = -INFINITY;
+      int bi = lane < classes ? lane : 0x7fffffff;
+      for (int c = lane; c < classes; c += 64) {
+        const float v = bf2f(logits[row * ld + c]);
+        if (v > best) { best = v; bi = c; }
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+      }
+      pred = bi;
+    }
+    if (lane == 0 && confusion != nullptr) {        // confusion[target][prediction] += 1
+      if (pred >= 0 && pred < classes) atomicAdd(&confusion[(size_t)t * classes + pred], 1ull);
+    } else if (lane == 0) {
+      if (pred >= 0 && pred < classes) {
+        atomicAdd(&counts[classes + pred], 1ull);
+        if (pred == (int)t) atomicAdd(&counts[pred], 1ull);
+      }
+      atomicAdd(&counts[2 * classes + (int)t], 1ull);
+    }
+  }
+}
+}  // namespace
+
+extern "C" int tok_cls_stats_update(const void* logits, const int64_t* labels, const int64_t* target, int64_t rows,
+                                    int classes, int ld, int64_t ignore_index, int64_t* counts, void* stream) {
+  TOK_CHECK_ARG((logits != nullptr) != (labels != nullptr), "tok_cls_stats_update: give logits OR predicted labels");
+  TOK_CHECK_ARG(target && counts && rows > 0 && classes > 0 && (labels || ld >= classes), "tok_cls_stats_update: bad args");
+  const int64_t b = (rows + 3) / 4;
+  hipLaunchKernelGGL(cls_stats_kernel, dim3((unsigned)(b > 2048 ? 2048 : b)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)logits, labels, target, rows, classes, ld, ignore_index, (unsigned long long*)counts,
+                     (unsigned long long*)nullptr);
+  TOK_CHECK_LAUNCH("tok_cls_stats_update");
+  return TOK_OK;
+}
+
+extern "C" int tok_confusion_update(const void* logits, const int64_t* labels, const int64_t* target, int64_t rows,
+                                    int classes, int ld, int64_t ignore_index, int64_t* confusion, void* stream) {
+  TOK_CHECK_ARG((logits != nullptr) != (labels != nullptr), "tok_confusion_update: give logits OR predicted labels");
+  TOK_CHECK_ARG(target && confusion && rows > 0 && classes > 0 && (labels || ld >= classes), "tok_confusion_update: bad args");
+  const int64_t b = (rows + 3) / 4;
+  hipLaunchKernelGGL(cls_stats_kernel, dim3((unsigned)(b > 2048 ? 2048 : b)), dim3(256), 0, tok_stream(stream),
+                     (const bf16*)logits, labels, target, rows, classes, ld, ignore_index, (unsigned long long*)nullptr,
+                     (unsigned long long*)confusion);
+  TOK_CHECK_LAUNCH("tok_confusion_update");
   return TOK_OK;
 }

@@ -1,12 +1,11 @@
 // The per-channel row-streaming skeleton (bn.hip, layer_scale.hip, se.hip, relu_mask_reduce in unit3.hip, bilinear_sum_stats in
-// resample.hip): a [rows][ld] bf16 matrix, CGE = min(C/8, 256) channel groups across the 256-thread block, RPB = 256 / CGE
+// neck_resample.hip): a [rows][ld] bf16 matrix, CGE = min(C/8, 256) channel groups across the 256-thread block, RPB = 256 / CGE
 // rows per block iteration; a lane keeps ONE 8-channel group (16 bytes of bf16) for a whole pass over its rows, so its
 // per-channel coefficients live in registers.  A kernel is a `setup` lambda: setup(cg) loads the lane's coefficients of channel
-// group cg and returns the per-row body.  Everything is force-inlined: no call and no dispatch inside the row loop.
+// group cg and returns the per-row body (TOK_ROW_INLINE behind both parameter lists).  Everything is force-inlined: no call
+// and no dispatch inside the row loop.
 #pragma once
 #include "tok_common.h"
-
-#define TOK_ROW_INLINE __attribute__((always_inline))   // behind the parameter list of a setup / row lambda
 
 struct Geo {
   int cg_total, cge, rpb;

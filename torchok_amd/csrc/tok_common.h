@@ -76,6 +76,9 @@ void tok_launch_lds(int max_bytes, dim3 grid, dim3 block, size_t bytes, hipStrea
 }
 
 // ---- device helpers -----------------------------------------------------------------------
+// behind the parameter list of a lambda handed to a force-inlined skeleton (row_stream.h, resample.h)
+#define TOK_ROW_INLINE __attribute__((always_inline))
+
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 __device__ __forceinline__ bf16 f2bf(float v) { return (bf16)v; }  // RNE (v_cvt_pk_bf16_f32)
 
@@ -174,6 +177,11 @@ __device__ __forceinline__ int tok_xcd_remap(int b, int nwg) {
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
 

@@ -164,7 +164,7 @@ def materialized(x):
 
 
 class _UpsampleCE(torch.autograd.Function):
-    """CrossEntropyLoss(F.interpolate(low, size, 'bilinear'), target) from the low-resolution logits (csrc/loss.hip)."""
+    """CrossEntropyLoss(F.interpolate(low, size, 'bilinear'), target) from the low-resolution logits (csrc/loss_upsample_ce.hip)."""
 
     @staticmethod
     def forward(ctx, low: Tensor, target: Tensor, size, ignore_index: int):
