@@ -740,6 +740,44 @@ int tok_se_gate_fwd(const void* x, int n, int hw, int c, int ld, int rd, int gat
 int tok_se_gate_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, const float* w1,
                     const float* w2, const float* mean, const float* hid, const float* gate, float* dw1, float* db1, float* dw2,
                     float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
+/* ... and with the inner activation and the biases as arguments (GCViT: [timm 0.6.13] SEModule with GELU between two bias-free
+ * 1x1 layers): act_kind 0 = ReLU (the entry points above, bit for bit), 1 = erf-GELU (the gelu_f of tok_act_fwd).  b1 and b2 are
+ * both given or both NULL (layers without bias); db1 / db2 may be NULL as above.  With act_kind 1 `hid` holds the hidden
+ * PRE-activation (the backward differentiates GELU there).  ws: tok_se_act_ws_floats(...) floats for both calls.          */
+size_t tok_se_act_ws_floats(int n, int hw, int c, int rd);
+int tok_se_act_fwd(const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, int act_kind, const float* w1,
+                   const float* b1, const float* w2, const float* b2, float* mean, float* hid, float* gate, float* ws,
+                   void* stream);
+int tok_se_act_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, int act_kind,
+                   const float* w1, const float* w2, const float* mean, const float* hid, const float* gate, float* dw1,
+                   float* db1, float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
+
+/* ---- Global Context ViT: biased window attention with an optional shared query ([timm 0.6.13]
+ * gcvit.WindowAttentionGlobal.forward between qkv and proj; csrc/gc_attn.hip) ---------------------------------------------------
+ * Per (window, head) O = softmax(Q K^T * 32^-0.5 + bias[h]) V over the N = ws * ws tokens of a window of a [batch][h][w] token
+ * map.  Windows are numbered image-major, u = img * nW + wy * (w / ws) + wx; partition and reverse are index arithmetic, rows
+ * stay in token order.
+ *   q_global == NULL (local):  qkv bf16 [batch*h*w][ld], columns (3, heads, 32).
+ *   q_global != NULL (global): qkv columns (2, heads, 32) = k | v; q_global bf16 [batch*N][ldg], columns (heads, 32); window u
+ *     uses the rows of image u % batch (the reference's `repeat` tiles image-minor), NOT u / nW.
+ *   bias fp32 [heads][N][ldb] (tok_relpos_bias_fwd), 16-byte aligned, ldb >= N, ldb % 4 == 0; out bf16 [batch*h*w][ldo] at column
+ *   head*32 + d; lse fp32 [batch*nW][heads][N], natural log, of the biased logits.
+ * Served: c == heads * 32 (head_dim 32), h % ws == 0, w % ws == 0, N <= 256, pitches multiples of 8 and wide enough; anything
+ * else, or a NULL qkv / bias / out / lse, is TOK_ERR_INVALID before any launch.
+ * tok_gc_attn_bwd: P recomputed from q, k, bias and lse; delta = rowsum(dO o O) is formed as rowsum(P o dP) in fp32 (`out` is
+ *   checked but not read: the stored bf16 O would put its rounding into a difference that cancels).  dqkv bf16 [batch*h*w][ldd] in the layout of qkv (global mode: dk | dv;
+ *   columns past those never written); global mode: dq_global[img] bf16 [batch*N][lddg] = sum over the windows u % batch == img, in
+ *   ascending u, of that window's dq (fp32 sum, rounded once).  dbias (nullable: a frozen table costs nothing) fp32
+ *   [heads][N][ldb] (= | += with dbias_accumulate) sum over all windows, ascending u, of dS; columns >= N not written.  The
+ *   windows are split into at most 128 chunks whose partial tables are folded in chunk order.  No float atomics: bit-reproducible.
+ *   ws_buf: tok_gc_attn_bwd_ws_bytes(...) bytes (0 for a geometry that is not served).                                       */
+int tok_gc_attn_fwd(const void* qkv, int ld, const void* q_global, int ldg, const float* bias, int ldb, int batch, int h, int w,
+                    int c, int heads, int ws, void* out, int ldo, float* lse, void* stream);
+size_t tok_gc_attn_bwd_ws_bytes(int batch, int h, int w, int heads, int ws, int global, int want_dbias);
+int tok_gc_attn_bwd(const void* qkv, int ld, const void* q_global, int ldg, const float* bias, int ldb, const void* out,
+                    const void* dout, int ldo, const float* lse, int batch, int h, int w, int c, int heads, int ws, void* dqkv,
+                    int ldd, void* dq_global, int lddg, float* dbias, int dbias_accumulate, void* ws_buf, size_t ws_bytes,
+                    void* stream);
 
 /* ---- Vision Transformer: global self-attention and token embedding ([timm 0.6.13] vision_transformer.Attention.forward,
  * PatchEmbed, VisionTransformer._pos_embed; reached from torchok/models/backbones/vit.py:202-357) -------------------------------

@@ -199,6 +199,14 @@ PROTOTYPES = {
     'tok_se_gate_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tok_se_gate_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P,
                                 c_int, _P, _P]),
+    'tok_se_act_ws_floats': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'tok_se_act_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'tok_se_act_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int,
+                               _P, c_int, _P, _P]),
+    'tok_gc_attn_fwd': (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
+    'tok_gc_attn_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'tok_gc_attn_bwd': (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P,
+                                c_int, _P, c_int, _P, c_int, _P, c_size_t, _P]),
     'tok_global_attn_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     'tok_global_attn_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int]),
     'tok_global_attn_bwd': (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),

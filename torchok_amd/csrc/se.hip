@@ -3,6 +3,9 @@
 //   s[n][c] = gate(b2 + W2 relu(b1 + W1 mean_hw(x[n])))      out = x * s   (the product: tok_channel_scale)
 //   gate 0: sigmoid(a), s' = s (1 - s);  gate 1: hard sigmoid min(max(a + 3, 0), 6) / 6, s' = 1/6 where 0 < s < 1, else 0
 // The gate is a compile-time parameter of the two per-image kernels: the sigmoid instantiation is the MnasNet code.
+// So are the activation between the two layers (ReLU, or erf-GELU for [timm 0.6.13] SEModule as GCViT's MbConvBlock builds it) and
+// "the layers have biases": tok_se_act_fwd / _bwd reach the new instantiations, the four older entry points launch the
+// <gate, ReLU, biases> ones, whose instruction streams are what they were (profiles/gcvit_se_isa.txt).
 // x / dout / dx bf16 [n][hw][ld] (c % 8 == 0), W1 fp32 [rd][c] (conv_reduce), W2 fp32 [c][rd] (conv_expand), 1 <= rd <= 256.
 //
 // Forward : per-(image, chunk) channel sums -> one block per image folds them in chunk order and runs the two 1x1 layers.
@@ -59,8 +62,10 @@ __global__ __launch_bounds__(256) void se_sum_kernel(const bf16* __restrict__ a,
 __device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + __expf(-v)); }
 __device__ __forceinline__ float hard_sigmoid_f(float v) { return fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f; }
 
-// one block per image: mean, hidden = relu(W1 mean + b1), gate = GATE(W2 hidden + b2)
-template <int GATE>
+// one block per image: mean, hidden = act(W1 mean + b1), gate = GATE(W2 hidden + b2).  ACT 0: ReLU, `hid` keeps the hidden
+// activation.  ACT 1: erf-GELU (gelu_f), `hid` keeps the PRE-activation, which is what the backward differentiates at.
+// BIAS false: b1 and b2 are not read (the layers have none).  <GATE, 0, true> is the code the kernel had before ACT and BIAS.
+template <int GATE, int ACT, bool BIAS>
 __global__ __launch_bounds__(256) void se_fwd_image_kernel(const float* __restrict__ part, int chunks, int hw, int C, int rd,
                                                            const float* __restrict__ w1, const float* __restrict__ b1,
                                                            const float* __restrict__ w2, const float* __restrict__ b2,
@@ -82,21 +87,29 @@ __global__ __launch_bounds__(256) void se_fwd_image_kernel(const float* __restri
     for (int c = lane; c < C; c += 64) a = fmaf(w1[(size_t)j * C + c], m[c], a);
     a = wave_sum(a);
     if (lane == 0) {
-      const float v = fmaxf(a + b1[j], 0.f);
-      h[j] = v;
-      hid[(size_t)img * rd + j] = v;
+      if constexpr (ACT == 0) {
+        const float v = fmaxf(BIAS ? a + b1[j] : a, 0.f);
+        h[j] = v;
+        hid[(size_t)img * rd + j] = v;
+      } else {
+        const float pre = BIAS ? a + b1[j] : a;
+        h[j] = gelu_f(pre);
+        hid[(size_t)img * rd + j] = pre;
+      }
     }
   }
   __syncthreads();
   for (int c = tid; c < C; c += 256) {
-    float a = b2[c];
+    float a = BIAS ? b2[c] : 0.f;
     for (int j = 0; j < rd; ++j) a = fmaf(w2[(size_t)c * rd + j], h[j], a);
     gate[(size_t)img * C + c] = GATE == 0 ? sigmoid_f(a) : hard_sigmoid_f(a);
   }
 }
 
-// one block per image: ds = g s' (s' from the stored gate, see the top), dh = relu'(hidden) W2^T ds, dmean = W1^T dh
-template <int GATE>
+// one block per image: ds = g s' (s' from the stored gate, see the top), dh = act'(hidden) W2^T ds, dmean = W1^T dh.
+// ACT 1: `hid` holds the pre-activation (see the forward), dh = gelu_d(pre) W2^T ds, and the hidden activation gelu_f(pre) that
+// the parameter gradients multiply with is written behind dh_out ([2][images][rd]: dh, then the activation).
+template <int GATE, int ACT>
 __global__ __launch_bounds__(256) void se_bwd_image_kernel(const float* __restrict__ part, int chunks, int C, int rd,
                                                            const float* __restrict__ w1, const float* __restrict__ w2,
                                                            const float* __restrict__ hid, const float* __restrict__ gate,
@@ -119,7 +132,14 @@ __global__ __launch_bounds__(256) void se_bwd_image_kernel(const float* __restri
     for (int c = lane; c < C; c += 64) a = fmaf(w2[(size_t)c * rd + j], ds[c], a);
     a = wave_sum(a);
     if (lane == 0) {
-      const float v = hid[(size_t)img * rd + j] > 0.f ? a : 0.f;
+      float v;
+      if constexpr (ACT == 0) {
+        v = hid[(size_t)img * rd + j] > 0.f ? a : 0.f;
+      } else {
+        const float pre = hid[(size_t)img * rd + j];
+        v = a * gelu_d(pre);
+        dh_out[((size_t)gridDim.x + img) * rd + j] = gelu_f(pre);
+      }
       dh[j] = v;
       dh_out[(size_t)img * rd + j] = v;
     }
@@ -212,6 +232,7 @@ extern "C" size_t tok_se_ws_floats(int n, int hw, int c, int rd) {
 
 namespace {
 
+template <int ACT, bool BIAS>
 int se_fwd_launch(const char* name, int gate_kind, const void* x, int n, int hw, int c, int ld, int rd, const float* w1,
                   const float* b1, const float* w2, const float* b2, float* mean, float* hid, float* gate, float* ws,
                   void* stream) {
@@ -220,15 +241,16 @@ int se_fwd_launch(const char* name, int gate_kind, const void* x, int n, int hw,
   hipLaunchKernelGGL(se_sum_kernel, dim3(g.chunks, n), dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, hw, c, ld, g.cge,
                      g.rpb, ws);
   if (gate_kind == 0)
-    hipLaunchKernelGGL(se_fwd_image_kernel<0>, dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid,
+    hipLaunchKernelGGL((se_fwd_image_kernel<0, ACT, BIAS>), dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid,
                        gate);
   else
-    hipLaunchKernelGGL(se_fwd_image_kernel<1>, dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid,
+    hipLaunchKernelGGL((se_fwd_image_kernel<1, ACT, BIAS>), dim3(n), dim3(256), 0, st, ws, g.chunks, hw, c, rd, w1, b1, w2, b2, mean, hid,
                        gate);
   TOK_CHECK_LAUNCH(name);
   return TOK_OK;
 }
 
+template <int ACT>
 int se_bwd_launch(const char* name, int gate_kind, const void* dout, const void* x, int n, int hw, int c, int ld, int rd,
                   const float* w1, const float* w2, const float* mean, const float* hid, const float* gate, float* dw1,
                   float* db1, float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws,
@@ -242,14 +264,14 @@ int se_bwd_launch(const char* name, int gate_kind, const void* dout, const void*
   hipLaunchKernelGGL(se_sum_kernel, dim3(g.chunks, n), dim3(256), 0, st, (const bf16*)dout, (const bf16*)x, hw, c, ld, g.cge,
                      g.rpb, part);
   if (gate_kind == 0)
-    hipLaunchKernelGGL(se_bwd_image_kernel<0>, dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh,
+    hipLaunchKernelGGL((se_bwd_image_kernel<0, ACT>), dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh,
                        dmean);
   else
-    hipLaunchKernelGGL(se_bwd_image_kernel<1>, dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh,
+    hipLaunchKernelGGL((se_bwd_image_kernel<1, ACT>), dim3(n), dim3(256), 0, st, part, g.chunks, c, rd, w1, w2, hid, gate, ds, dh,
                        dmean);
   if (dw1 || db1 || dw2 || db2)
-    hipLaunchKernelGGL(se_param_grad_kernel, dim3(blocks_for(2 * (size_t)c * rd + c + rd)), dim3(256), 0, st, ds, dh, hid, mean,
-                       n, c, rd, dw1, db1, dw2, db2, param_accumulate);
+    hipLaunchKernelGGL(se_param_grad_kernel, dim3(blocks_for(2 * (size_t)c * rd + c + rd)), dim3(256), 0, st, ds, dh,
+                       ACT == 0 ? hid : dh + (size_t)n * rd, mean, n, c, rd, dw1, db1, dw2, db2, param_accumulate);
   if (dx != nullptr)
     hipLaunchKernelGGL(se_dx_kernel, dim3(blocks_for((size_t)n * hw * (c >> 3))), dim3(256), 0, st, (const bf16*)dout, gate,
                        dmean, n, hw, c, ld, (bf16*)dx, dx_accumulate);
@@ -263,7 +285,7 @@ extern "C" int tok_se_fwd(const void* x, int n, int hw, int c, int ld, int rd, c
                           const float* b2, float* mean, float* hid, float* gate, float* ws, void* stream) {
   TOK_CHECK_ARG(x && w1 && b1 && w2 && b2 && mean && hid && gate && ws, "tok_se_fwd: null pointer");
   TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_fwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
-  return se_fwd_launch("tok_se_fwd", 0, x, n, hw, c, ld, rd, w1, b1, w2, b2, mean, hid, gate, ws, stream);
+  return se_fwd_launch<0, true>("tok_se_fwd", 0, x, n, hw, c, ld, rd, w1, b1, w2, b2, mean, hid, gate, ws, stream);
 }
 
 extern "C" int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, const float* w1,
@@ -271,7 +293,7 @@ extern "C" int tok_se_bwd(const void* dout, const void* x, int n, int hw, int c,
                           float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream) {
   TOK_CHECK_ARG(dout && x && w1 && w2 && mean && hid && gate && ws, "tok_se_bwd: null pointer");
   TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_bwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
-  return se_bwd_launch("tok_se_bwd", 0, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2,
+  return se_bwd_launch<0>("tok_se_bwd", 0, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2,
                        param_accumulate, dx, dx_accumulate, ws, stream);
 }
 
@@ -281,7 +303,7 @@ extern "C" int tok_se_gate_fwd(const void* x, int n, int hw, int c, int ld, int 
   TOK_CHECK_ARG(x && w1 && b1 && w2 && b2 && mean && hid && gate && ws, "tok_se_gate_fwd: null pointer");
   TOK_CHECK_ARG(gate_kind == 0 || gate_kind == 1, "tok_se_gate_fwd: gate 0 (sigmoid) or 1 (hard sigmoid)");
   TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_gate_fwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
-  return se_fwd_launch("tok_se_gate_fwd", gate_kind, x, n, hw, c, ld, rd, w1, b1, w2, b2, mean, hid, gate, ws, stream);
+  return se_fwd_launch<0, true>("tok_se_gate_fwd", gate_kind, x, n, hw, c, ld, rd, w1, b1, w2, b2, mean, hid, gate, ws, stream);
 }
 
 extern "C" int tok_se_gate_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, int gate_kind,
@@ -291,6 +313,43 @@ extern "C" int tok_se_gate_bwd(const void* dout, const void* x, int n, int hw, i
   TOK_CHECK_ARG(dout && x && w1 && w2 && mean && hid && gate && ws, "tok_se_gate_bwd: null pointer");
   TOK_CHECK_ARG(gate_kind == 0 || gate_kind == 1, "tok_se_gate_bwd: gate 0 (sigmoid) or 1 (hard sigmoid)");
   TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "tok_se_gate_bwd: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)");
-  return se_bwd_launch("tok_se_gate_bwd", gate_kind, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2,
+  return se_bwd_launch<0>("tok_se_gate_bwd", gate_kind, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2,
                        param_accumulate, dx, dx_accumulate, ws, stream);
+}
+
+// The inner activation and the biases as arguments (GCViT's SEModule: GELU between two bias-free 1x1 layers).
+extern "C" size_t tok_se_act_ws_floats(int n, int hw, int c, int rd) {
+  const size_t base = tok_se_ws_floats(n, hw, c, rd);
+  return base ? base + (size_t)n * rd : 0;
+}
+
+extern "C" int tok_se_act_fwd(const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, int act_kind, const float* w1,
+                              const float* b1, const float* w2, const float* b2, float* mean, float* hid, float* gate, float* ws,
+                              void* stream) {
+  const char* who = "tok_se_act_fwd";
+  TOK_CHECK_ARG(x && w1 && w2 && mean && hid && gate && ws, "%s: null pointer", who);
+  TOK_CHECK_ARG((b1 == nullptr) == (b2 == nullptr), "%s: b1 and b2 are both given or both NULL", who);
+  TOK_CHECK_ARG(gate_kind == 0 || gate_kind == 1, "%s: gate 0 (sigmoid) or 1 (hard sigmoid)", who);
+  TOK_CHECK_ARG(act_kind == 0 || act_kind == 1, "%s: activation 0 (ReLU) or 1 (GELU)", who);
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "%s: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)", who);
+#define TOK_SE_FWD(A, B) se_fwd_launch<A, B>(who, gate_kind, x, n, hw, c, ld, rd, w1, b1, w2, b2, mean, hid, gate, ws, stream)
+  if (act_kind == 0) return b1 ? TOK_SE_FWD(0, true) : TOK_SE_FWD(0, false);
+  return b1 ? TOK_SE_FWD(1, true) : TOK_SE_FWD(1, false);
+#undef TOK_SE_FWD
+}
+
+extern "C" int tok_se_act_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, int act_kind,
+                              const float* w1, const float* w2, const float* mean, const float* hid, const float* gate, float* dw1,
+                              float* db1, float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws,
+                              void* stream) {
+  const char* who = "tok_se_act_bwd";
+  TOK_CHECK_ARG(dout && x && w1 && w2 && mean && hid && gate && ws, "%s: null pointer", who);
+  TOK_CHECK_ARG(gate_kind == 0 || gate_kind == 1, "%s: gate 0 (sigmoid) or 1 (hard sigmoid)", who);
+  TOK_CHECK_ARG(act_kind == 0 || act_kind == 1, "%s: activation 0 (ReLU) or 1 (GELU)", who);
+  TOK_CHECK_ARG(se_args_ok(n, hw, c, ld, rd), "%s: bad sizes (c %% 8 == 0, c <= 2048, 1 <= rd <= 256)", who);
+  if (act_kind == 0)
+    return se_bwd_launch<0>(who, gate_kind, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2,
+                            param_accumulate, dx, dx_accumulate, ws, stream);
+  return se_bwd_launch<1>(who, gate_kind, dout, x, n, hw, c, ld, rd, w1, w2, mean, hid, gate, dw1, db1, dw2, db2, param_accumulate,
+                          dx, dx_accumulate, ws, stream);
 }

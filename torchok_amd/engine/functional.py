@@ -17,7 +17,7 @@ conv_bn_act / dwconv_bn_act take act='hard_swish' (MobileNetV3) or act='relu6' (
 path of csrc/bn.hip.
 """
 import weakref
-from typing import Optional
+from typing import Optional, Tuple
 
 import os
 
@@ -1236,11 +1236,13 @@ def gconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d
 # ---- squeeze-excite (MnasNet-A1) -----------------------------------------------------------------------------------------
 
 SE_GATES = {'sigmoid': 0, 'hard_sigmoid': 1}      # gate_kind of tok_se_gate_fwd / _bwd
+SE_ACTS = {'relu': 0, 'gelu': 1}                  # act_kind of tok_se_act_fwd / _bwd
 
 
 class _SqueezeExciteNode(Node):
     needs_backward = True
     gate_kind = 0
+    act_kind = 0            # SE_ACTS: the activation between the two 1x1 layers
 
     def backward(self):
         g = self.out.grad
@@ -1250,13 +1252,21 @@ class _SqueezeExciteNode(Node):
         se, x = self.se, self.x
         lib = _C.lib()
         n, h, w, c = x.shape
-        rd = se.conv_reduce.out_channels
-        prm = (se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias)
-        targets = [(p, *(PG.sink(p) if p.requires_grad else (None, 0))) for p in prm]
+        red, exp = self.layers
+        rd = red.out_channels
+        prm = (red.weight, red.bias, exp.weight, exp.bias)
+        targets = [(p, *(PG.sink(p) if p is not None and p.requires_grad else (None, 0))) for p in prm]
         acc_bits = sum(acc << bit for bit, (_, _, acc) in enumerate(targets))
         dx, dx_acc = grad_target(x) if x.requires_grad else (None, 0)
-        ws = torch.empty(lib.tok_se_ws_floats(n, h * w, c, rd), dtype=F32, device=g.device)
-        if self.gate_kind:
+        general = self.act_kind != 0 or red.bias is None
+        ws = torch.empty((lib.tok_se_act_ws_floats if general else lib.tok_se_ws_floats)(n, h * w, c, rd), dtype=F32,
+                         device=g.device)
+        if general:
+            _C.check(lib.tok_se_act_bwd(ptr(g), ptr(x.data), n, h * w, c, c, rd, self.gate_kind, self.act_kind, ptr(prm[0]),
+                                        ptr(prm[2]), ptr(self.mean), ptr(self.hid), ptr(self.gate),
+                                        *(ptr(t[1]) for t in targets), acc_bits, ptr(dx), dx_acc, ptr(ws), stream_ptr()),
+                     'tok_se_act_bwd')
+        elif self.gate_kind:
             _C.check(lib.tok_se_gate_bwd(ptr(g), ptr(x.data), n, h * w, c, c, rd, self.gate_kind, ptr(prm[0]), ptr(prm[2]),
                                          ptr(self.mean), ptr(self.hid), ptr(self.gate), *(ptr(t[1]) for t in targets), acc_bits,
                                          ptr(dx), dx_acc, ptr(ws), stream_ptr()), 'tok_se_gate_bwd')
@@ -1271,20 +1281,26 @@ class _SqueezeExciteNode(Node):
             self.region.keep_until_join(ws)
 
     def release(self):
-        self.x = self.out = self.mean = self.hid = self.gate = None
+        self.x = self.out = self.mean = self.hid = self.gate = self.layers = None
 
 
-def squeeze_excite(region: Region, x: TTensor, se: nn.Module, gate: str = 'sigmoid') -> TTensor:
-    """x * gate(conv_expand(relu(conv_reduce(mean_hw(x)))))  ([timm] efficientnet_blocks.SqueezeExcite with ReLU inside and
+def squeeze_excite(region: Region, x: TTensor, se: nn.Module, gate: str = 'sigmoid', act: str = 'relu',
+                   names: Tuple[str, str] = ('conv_reduce', 'conv_expand')) -> TTensor:
+    """x * gate(conv_expand(act(conv_reduce(mean_hw(x)))))  ([timm] efficientnet_blocks.SqueezeExcite with ReLU inside and
     the 'sigmoid' (MnasNet) or 'hard_sigmoid' (MobileNetV3) gate).  `se` holds conv_reduce / conv_expand (1x1, with bias) as
-    parameter containers."""
+    parameter containers.  act='gelu' and / or two layers without bias ([timm 0.6.13] SEModule as GCViT's MbConvBlock builds it,
+    names=('fc1', 'fc2')) go through tok_se_act_fwd / _bwd; the defaults are the launches they have always been."""
     if gate not in SE_GATES:
         raise NotImplementedError(f'torchok_amd squeeze-excite gate {gate!r}: one of {sorted(SE_GATES)}')
-    gate_kind = SE_GATES[gate]
+    if act not in SE_ACTS:
+        raise NotImplementedError(f'torchok_amd squeeze-excite activation {act!r}: one of {sorted(SE_ACTS)}')
+    gate_kind, act_kind = SE_GATES[gate], SE_ACTS[act]
     await_ready(x)
-    red, exp = se.conv_reduce, se.conv_expand
+    red, exp = getattr(se, names[0]), getattr(se, names[1])
+    general = act_kind != 0 or (red.bias is None and exp.bias is None)
     if x.data.dim() != 4 or x.c != x.cp or red.in_channels != x.c or exp.out_channels != x.c \
-            or red.out_channels != exp.in_channels or red.bias is None or exp.bias is None:
+            or red.out_channels != exp.in_channels or (red.bias is None) != (exp.bias is None) \
+            or (red.bias is None and not general):
         raise NotImplementedError('torchok_amd squeeze-excite: 1x1 convs with bias around a 4-D input of 8k channels')
     lib, st = _C.lib(), stream_ptr()
     n, h, w, c = x.shape
@@ -1297,8 +1313,11 @@ def squeeze_excite(region: Region, x: TTensor, se: nn.Module, gate: str = 'sigmo
     mean = torch.empty((n, c), dtype=F32, device=dev)
     hid = torch.empty((n, rd), dtype=F32, device=dev)
     gate_v = torch.empty((n, c), dtype=F32, device=dev)
-    ws = torch.empty(lib.tok_se_ws_floats(n, h * w, c, rd), dtype=F32, device=dev)
-    if gate_kind:
+    ws = torch.empty((lib.tok_se_act_ws_floats if general else lib.tok_se_ws_floats)(n, h * w, c, rd), dtype=F32, device=dev)
+    if general:
+        _C.check(lib.tok_se_act_fwd(ptr(x.data), n, h * w, c, c, rd, gate_kind, act_kind, ptr(w1), ptr(red.bias), ptr(w2),
+                                    ptr(exp.bias), ptr(mean), ptr(hid), ptr(gate_v), ptr(ws), st), 'tok_se_act_fwd')
+    elif gate_kind:
         _C.check(lib.tok_se_gate_fwd(ptr(x.data), n, h * w, c, c, rd, gate_kind, ptr(w1), ptr(red.bias), ptr(w2), ptr(exp.bias),
                                      ptr(mean), ptr(hid), ptr(gate_v), ptr(ws), st), 'tok_se_gate_fwd')
     else:
@@ -1311,8 +1330,11 @@ def squeeze_excite(region: Region, x: TTensor, se: nn.Module, gate: str = 'sigmo
     if req:
         node = _SqueezeExciteNode()
         node.x, node.out, node.se, node.mean, node.hid, node.gate = x, out, se, mean, hid, gate_v
+        node.layers = (red, exp)
         if gate_kind:
             node.gate_kind = gate_kind
+        if act_kind:
+            node.act_kind = act_kind
         out.node = node
         if x.requires_grad:
             x.uses += 1

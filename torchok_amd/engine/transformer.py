@@ -14,6 +14,8 @@ reshape              .view between (B, H, W, C) maps and (B*H*W, C) token rows (
 global_attention     ViT Attention.forward between qkv and proj: softmax(q k^T / 8) v over all tokens of an image; with
                      `bias` BEiT's softmax(q k^T / 8 + relative_position_bias) v
 relpos_bias          BEiT relative_position_bias_table[relative_position_index] -> [heads][N][N] (gathered again in the backward)
+gc_window_attention  GCViT WindowAttentionGlobal.forward between qkv and proj: softmax(q k^T / sqrt(32) + bias) v per window, the
+                     query from the tokens or from the stage's shared q_global map
 layer_scale_add      BEiT Block's  x + drop_path(gamma * f(x))
 patch_embed          ViT PatchEmbed.proj (k = stride = patch): patch gather + 1x1 GEMM
 vit_embed            VisionTransformer._pos_embed: cls token + pos_embed, one rounding
@@ -826,6 +828,95 @@ def global_attention(region: Region, qkv: TTensor, batch: int, tokens: int, head
             node.bias_node = bias[1]
         out.node = node
         qkv.uses += 1
+        region.add(node)
+    return out
+
+
+# ---- GCViT: biased window attention with an optional shared query -------------------------------------------------------------
+class _GcWindowAttnNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        lib, st = _C.lib(), stream_ptr()
+        g = self.out.grad
+        if g is None:
+            return
+        b, h, w, c, heads, ws = self.geo
+        qkv, qg, o, bn = self.qkv, self.q_global, self.out, self.bias_node
+        if g.stride(0) != o.data.stride(0):
+            raise RuntimeError('gc_window_attention: d(out) and out do not share a row pitch')
+        tgt, acc = grad_target(qkv)
+        if acc:
+            raise RuntimeError('gc_window_attention: qkv has a single consumer')
+        bias = bn.gather()                 # gathered again: no block keeps its [heads][N][N] bias across the step
+        ldb = bias.shape[-1]
+        dbias = torch.empty_like(bias) if bn.table.requires_grad else None
+        dqg = qg_tgt = None
+        if qg is not None and not qg.requires_grad:
+            dqg = torch.empty_like(qg.data)            # the kernel writes it; nobody reads it
+        elif qg is not None:
+            # q_global has one consumer per global block of its stage: the kernel writes d(q_global) of THIS block, which is the
+            # gradient's first contribution or is added to it
+            qg_tgt, qg_acc = grad_target(qg)
+            dqg = torch.empty_like(qg_tgt) if qg_acc else qg_tgt
+        ws_bytes = int(lib.tok_gc_attn_bwd_ws_bytes(b, h, w, heads, ws, int(qg is not None), int(dbias is not None)))
+        wsb = torch.empty(max(ws_bytes // 4, 1), dtype=F32, device=g.device)
+        _C.check(lib.tok_gc_attn_bwd(ptr(qkv.data), qkv.cp, ptr(qg.data) if qg is not None else None, qg.cp if qg is not None else 0,
+                                     ptr(bias), ldb, ptr(o.data), ptr(g), o.cp, ptr(self.lse), b, h, w, c, heads, ws, ptr(tgt),
+                                     qkv.cp, ptr(dqg), qg.cp if qg is not None else 0, ptr(dbias), 0, ptr(wsb), ws_bytes, st),
+                 'tok_gc_attn_bwd')
+        if qg_tgt is not None and dqg is not qg_tgt:
+            _C.check(lib.tok_act_bwd(2, ptr(dqg), ptr(dqg), ptr(qg_tgt), 1, dqg.numel(), st), 'tok_act_bwd')
+        bn.dbias = dbias
+        self.out.grad = None
+
+    def release(self):
+        self.qkv = self.q_global = self.out = self.lse = self.bias_node = None
+
+
+def gc_window_attention(region: Region, qkv: TTensor, geo: Tuple[int, int, int, int, int, int], bias,
+                        q_global: Optional[TTensor] = None) -> TTensor:
+    """[timm 0.6.13] gcvit.WindowAttentionGlobal.forward between qkv and proj, window_partition / window_reverse included:
+    softmax(q k^T * 32^-0.5 + bias[h]) v over the windows of a token map; geo = (B, H, W, C, heads, window).
+    q_global None: qkv rows [B*H*W][3C].  q_global given (a (B, ws, ws, C) map): qkv rows [B*H*W][2C] hold k | v and window u
+    takes the query of image u mod B — the reference's `repeat`, see csrc/gc_attn.hip.  bias: the (bias, node) pair of
+    `relpos_bias`; the backward gathers the bias again and hands d(bias) to that node.  d(q_global) accumulates over its
+    consumers (one per global block of a stage)."""
+    b, h, w, c, heads, ws = geo
+    if c != heads * 32:
+        raise NotImplementedError(f'gc_window_attention: head_dim {c // max(heads, 1)} (32 only)')
+    if h % ws or w % ws:
+        raise NotImplementedError(f'gc_window_attention: a {h}x{w} token map is not a multiple of the window {ws}')
+    n = ws * ws
+    if n > 256:
+        raise NotImplementedError(f'gc_window_attention: {n} tokens per window (at most 256)')
+    parts = 3 if q_global is None else 2
+    if qkv.c != parts * c or qkv.rows() != b * h * w:
+        raise ValueError(f'gc_window_attention: qkv {tuple(qkv.shape)} for {b}x{h}x{w} tokens of {parts} x {c}')
+    if q_global is not None and (q_global.c != c or q_global.cp != c or q_global.rows() != b * n):
+        raise ValueError(f'gc_window_attention: q_global {tuple(q_global.shape)} for {b} images of {n} x {c}')
+    bias_data, bias_node = bias
+    if tuple(bias_data.shape[:2]) != (heads, n):
+        raise ValueError(f'gc_window_attention: bias {tuple(bias_data.shape)} for {heads} heads, {n} tokens')
+    await_ready(qkv, q_global)
+    lib, st = _C.lib(), stream_ptr()
+    dev = qkv.data.device
+    nw = (h // ws) * (w // ws)
+    out_data = torch.empty((b * h * w, c), dtype=BF16, device=dev)
+    lse = torch.empty((b * nw, heads, n), dtype=F32, device=dev)
+    _C.check(lib.tok_gc_attn_fwd(ptr(qkv.data), qkv.cp, ptr(q_global.data) if q_global is not None else None,
+                                 q_global.cp if q_global is not None else 0, ptr(bias_data), bias_data.shape[-1], b, h, w, c, heads,
+                                 ws, ptr(out_data), c, ptr(lse), st), 'tok_gc_attn_fwd')
+    req = region.grad_mode and bias_node is not None and (
+        qkv.requires_grad or bias_node.table.requires_grad or (q_global is not None and q_global.requires_grad))
+    out = TTensor(out_data, c, requires_grad=bool(req))
+    if req:
+        node = _GcWindowAttnNode()
+        node.qkv, node.q_global, node.out, node.lse, node.geo, node.bias_node = qkv, q_global, out, lse, geo, bias_node
+        out.node = node
+        qkv.uses += 1
+        if q_global is not None and q_global.requires_grad:
+            q_global.uses += 1
         region.add(node)
     return out
 

@@ -1,1 +1,1 @@
-from . import beit, davit, efficientnet, hrnet, mobilenetv3, resnet, swin, vit  # noqa: F401
+from . import beit, davit, efficientnet, gcvit, hrnet, mobilenetv3, resnet, swin, vit  # noqa: F401
