@@ -753,7 +753,7 @@ int tok_se_act_bwd(const void* dout, const void* x, int n, int hw, int c, int ld
                    float* db1, float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
 
 /* ---- Global Context ViT: biased window attention with an optional shared query ([timm 0.6.13]
- * gcvit.WindowAttentionGlobal.forward between qkv and proj; csrc/gc_attn.hip) ---------------------------------------------------
+ * gcvit.WindowAttentionGlobal.forward between qkv and proj; csrc/gc_attn.hip on csrc/attn_tile.h) ----------------------------
  * Per (window, head) O = softmax(Q K^T * 32^-0.5 + bias[h]) V over the N = ws * ws tokens of a window of a [batch][h][w] token
  * map.  Windows are numbered image-major, u = img * nW + wy * (w / ws) + wx; partition and reverse are index arithmetic, rows
  * stay in token order.
@@ -780,7 +780,8 @@ int tok_gc_attn_bwd(const void* qkv, int ld, const void* q_global, int ldg, cons
                     void* stream);
 
 /* ---- Vision Transformer: global self-attention and token embedding ([timm 0.6.13] vision_transformer.Attention.forward,
- * PatchEmbed, VisionTransformer._pos_embed; reached from torchok/models/backbones/vit.py:202-357) -------------------------------
+ * PatchEmbed, VisionTransformer._pos_embed; reached from torchok/models/backbones/vit.py:202-357; attention in
+ * csrc/attn_global.hip on csrc/attn_tile.h, the embedding entries in csrc/vit_embed.hip) ----------------------------------------
  * tok_global_attn_fwd: per (image, head) O = softmax(Q K^T * 64^-0.5) V over all n tokens.  qkv bf16 [batch*n][ldq], columns
  *   (3, heads, 64) as timm's qkv.reshape(B, N, 3, H, 64); out bf16 [batch*n][ldo] at column h*64 + d (timm's
  *   transpose(1, 2).reshape(B, N, C)); lse fp32 [batch][heads][n] = the natural-log row log-sum-exp of the scaled logits.

@@ -183,7 +183,7 @@ def step(name, batch, steps, warmup, share):
         whole = sum(t for _, t in rows)
         mine = {}
         for k, t in rows:
-            for tag in ('gc_fwd_kernel', 'gc_dkv_kernel', 'gc_dq_kernel', 'gc_dbias_kernel', 'gc_dbias_fold_kernel', 'gc_delta_kernel',
+            for tag in ('gc_fwd_kernel', 'gc_dkv_kernel', 'gc_dq_kernel', 'gc_dbias_kernel', 'attn_dbias_fold_kernel', 'gc_delta_kernel',
                         'se_fwd_image_kernel', 'se_bwd_image_kernel'):
                 if tag in k:
                     mine[tag] = mine.get(tag, 0) + t

@@ -38,6 +38,17 @@ void tok_set_error(const char* fmt, ...);
     }                                                                            \
   } while (0)
 
+// TOK_CHECK_LAUNCH for the launch "<who><stage>" of an entry point that issues several: returns the code instead of leaving
+static inline int launched(const char* who, const char* stage) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return TOK_OK;
+  tok_set_error("%s%s: launch failed: %s", who, stage, hipGetErrorString(e));
+  return TOK_ERR_LAUNCH;
+}
+
+// workgroups of 256 threads for n work items
+static inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+
 static inline hipStream_t tok_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // TOK_DBG_SKIP=<bitmask>: ablation probe for step-time budgeting (tools/ubench/runs/*): the named launches are NOT issued, results are
