@@ -419,27 +419,41 @@ int tok_confusion_update(const void* logits, const int64_t* labels, const int64_
 
 /* ---- metric-learning head and loss -----------------------------------------------------------
  * F.normalize (arcface_head.py:125-126, linear_head.py:33-34): y = x / max(||x||_2, eps) per row;
- * is_f32 selects fp32 rows (class-weight matrix) instead of bf16 activations.               */
+ * is_f32 selects fp32 rows (class-weight matrix) instead of bf16 activations.  Rows have pitch ld >= c; the forward
+ * writes 0 into the pad columns [c, ld) of y.  x and y must not overlap (no in-place form).  A row of norm 0 with
+ * eps = 0 is 0 * inf = NaN, as the division 0 / 0 it stands for.
+ * Backward: dx = (dy - y <y, dy>) * inv_norm of the saved y and inv_norm (the clamp branch ||x|| < eps has zero
+ * measure: there too).  accumulate = 0 writes dx and zeroes its pad columns; accumulate != 0 adds onto dx and leaves
+ * the pad columns holding what they held (they are re-stored as read).                       */
 int tok_l2norm_fwd(const void* x, void* y, float* inv_norm, int rows, int c, int ld, int is_f32,
                    float eps, void* stream);
 int tok_l2norm_bwd(const void* dy, const void* y, const float* inv_norm, void* dx, int accumulate,
                    int rows, int c, int ld, int is_f32, void* stream);
 /* ArcFaceHead.__add_margin (arcface_head.py:95-108) on the bf16 cosine matrix [rows][ld]:
- * the target column becomes phi (or its easy/hard fallback), everything is scaled.          */
+ * the target column becomes phi (or its easy/hard fallback), everything is scaled.  phi is rounded to bf16 once
+ * (the reference's .type(cosine.dtype)) before the fallback select and the scale.  A target outside [0, classes)
+ * changes no column; pad columns [classes, ld) of out / dcos are written 0.
+ * Backward: d phi / d cos = cos_m + cos / sqrt(1 - cos^2) * sin_m where the fp32 value of 1 - cos^2 lies in (0, 1),
+ * and cos_m where it does not (cos = +-1, where autograd of the clamped square root is not finite, and |cos| so small
+ * that 1 - cos^2 rounds to 1): the clamp kills the sine term's derivative outside (0, 1).        */
 int tok_arcface_margin_fwd(const void* cosine, const int64_t* target, int rows, int classes, int ld,
                            float cos_m, float sin_m, float th, float mm, int easy_margin, float scale,
                            void* out, void* stream);
 int tok_arcface_margin_bwd(const void* cosine, const int64_t* target, const void* dout, int rows,
                            int classes, int ld, float cos_m, float sin_m, float th, float mm,
                            int easy_margin, float scale, void* dcos, void* stream);
-/* PairwiseLearnTask.calc_relevance_matrix for 1-D labels (pairwise_task.py:87-107): exact.   */
+/* PairwiseLearnTask.calc_relevance_matrix for 1-D labels (pairwise_task.py:87-107): exact (int64 comparison).
+ * Both forms index R with an int: na * nb > 2^31 - 1 is refused with TOK_ERR_INVALID before any launch.   */
 int tok_relevance_matrix(const int64_t* labels_a, const int64_t* labels_b, int na, int nb, float* R,
                          void* stream);
 /* the same for multi-label matrices ya fp32 [na][classes], yb [nb][classes] (:103-105): R_ij = [sum_c ya_ic yb_jc > 0] */
 int tok_relevance_matrix_multilabel(const float* ya, const float* yb, int na, int nb, int classes, float* R,
                                     void* stream);
 /* ContrastiveLoss (losses/representation/pairwise.py:126-136, mean reduction, no regulariser):
- * S = cdist(e1, e2) [n1][n2] (saved), loss[0] = mean_i sum_j (1-R)relu(mu-S)^2 + R S^2.      */
+ * S = cdist(e1, e2) [n1][n2] (saved), loss[0] = mean_i sum_j (1-R)relu(mu-S)^2 + R S^2.
+ * Backward: de1 [n1][ld], de2 [n2][ld] (pad columns 0; a pair with S == 0 contributes 0).  same_tensor != 0 (emb1 is
+ * emb2): de2 is not used and the second operand's gradient is added onto de1, which is stored as bf16 in between;
+ * that needs n1 == n2, anything else is refused with TOK_ERR_INVALID before any launch.      */
 int tok_contrastive_fwd(const void* e1, const void* e2, const float* R, int n1, int n2, int d, int ld,
                         float margin, float* S, float* row_loss, float* loss, void* stream);
 int tok_contrastive_bwd(const void* e1, const void* e2, const float* R, const float* S,
@@ -856,8 +870,11 @@ int tok_rows_select(const void* src, int batch, int t, int first, int count, int
  * so that larger is closer), fp32 [nq][ldo] for fp32 rows q [nq][ldq], g [ng][ldg].                        */
 int tok_sim_matrix(const float* q, const float* g, int nq, int ng, int d, int ldq, int ldg, int metric,
                    float* out, int64_t ldo, void* stream);
-/* k best columns per row, larger value first, lower index on ties; k > cols is padded with (-inf, -1) as
- * faiss does.  vals fp32 [rows][k], idx int64 [rows][k].                                                  */
+/* k best columns per row, larger value first, lower index on ties (-0.0 == +0.0; -inf and +inf rank as values); k > cols
+ * is padded with (-inf, -1) as faiss does.  A NaN never ranks (every comparison of faiss's result heap is false for
+ * it): a row with fewer than k columns that are not NaN is padded the same way, so the all-NaN row of a zero vector
+ * under normalize_vectors (0 / 0, as in the reference) retrieves k times -1.  s has row pitch ld >= cols.
+ * vals fp32 [rows][k], idx int64 [rows][k].                                                               */
 int tok_topk_rows(const float* s, int rows, int cols, int64_t ld, int k, float* vals, int64_t* idx, void* stream);
 /* Number of relevant vectors per query.  labels != NULL (classification data, :379-418): vectors with the label
  * of row q_row[i], the query excluded.  Otherwise scores fp32 [n][n_cols] (representation data, :342-377): rows

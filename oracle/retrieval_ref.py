@@ -29,20 +29,29 @@ import numpy as np
 # ---- faiss IndexFlat{IP,L2}.search ------------------------------------------------------------------------------------
 def flat_search(gallery: np.ndarray, queries: np.ndarray, k: int, metric: str = 'IP'):
     """(scores [nq][k], indices [nq][k]) of the k best gallery rows per query; ties -> lower index first.  A label of
-    -1 then indexes `faiss_vector_idxs[-1]` in query_generator (:503), i.e. the LAST gallery row — kept as is."""
+    -1 then indexes `faiss_vector_idxs[-1]` in query_generator (:503), i.e. the LAST gallery row — kept as is.
+    A NaN score is never a result: faiss collects the k best in a heap that starts as k times (-inf, -1) for IP
+    (+inf for L2) and replaces its root only where `score > root` (IP) resp. `distance < root` (L2) holds, which is
+    false for a NaN on either side; what the heap never replaced comes back as label -1.  So a vector that
+    `normalize_vectors` turned into 0 / 0 = NaN is retrieved by nobody, and as a query it retrieves k times -1
+    (a plain argsort would rank the NaN entries last and hand back gallery rows 0 .. k - 1 for such a query)."""
     g = gallery.astype(np.float32)
     q = queries.astype(np.float32)
-    if metric == 'IP':
-        s = q @ g.T
-        order = np.argsort(-s, axis=1, kind='stable')[:, :k]
-    else:
-        s = ((q[:, None, :] - g[None, :, :]) ** 2).sum(-1)
-        order = np.argsort(s, axis=1, kind='stable')[:, :k]
-    val = np.take_along_axis(s, order, axis=1)
-    if k > g.shape[0]:      # faiss pads missing results with label -1 (score -inf for IP, +inf for L2)
-        pad = k - g.shape[0]
-        order = np.concatenate([order, np.full((len(q), pad), -1, dtype=order.dtype)], axis=1)
-        val = np.concatenate([val, np.full((len(q), pad), -np.inf if metric == 'IP' else np.inf, np.float32)], axis=1)
+    with np.errstate(invalid='ignore'):
+        if metric == 'IP':
+            s = q @ g.T
+            key = -s
+        else:
+            s = ((q[:, None, :] - g[None, :, :]) ** 2).sum(-1)
+            key = s
+    pad_val = -np.inf if metric == 'IP' else np.inf
+    order = np.full((len(q), k), -1, dtype=np.int64)
+    val = np.full((len(q), k), pad_val, np.float32)
+    for i in range(len(q)):
+        live = np.where(~np.isnan(key[i]))[0]
+        best = live[np.argsort(key[i][live], kind='stable')][:k]
+        order[i, :len(best)] = best           # fewer than k (k > gallery size, or NaN scores): label -1, score -inf / +inf
+        val[i, :len(best)] = s[i][best]
     return val, order
 
 
@@ -159,7 +168,8 @@ def meter_compute(metric: str, vectors, dataset_type: str, k=None, group_labels=
     search_k = k + 1                                                      # :107
     vectors = np.array(vectors, dtype=np.float32)
     if normalize_vectors:
-        vectors = vectors / np.linalg.norm(vectors, axis=1, keepdims=True)   # :189-190, see the header note
+        with np.errstate(invalid='ignore', divide='ignore'):            # a zero vector becomes 0 / 0 = NaN, as in the reference
+            vectors = vectors / np.linalg.norm(vectors, axis=1, keepdims=True)   # :189-190, see the header note
     group_labels = np.asarray(group_labels)
     if dataset_type == 'classification':
         relevant, gallery, q_rows, q_as_rel = prepare_classification(group_labels, raise_empty_query)

@@ -934,13 +934,14 @@ class FakeTok:
 
     def tok_topk_rows(self, s, rows, cols, ld, k, vals, idx, st):
         sv = _t(s, (rows, ld), torch.float32)[:, :cols]
-        order = torch.argsort(-sv, dim=1, stable=True)[:, :k]
+        order = torch.argsort(-sv, dim=1, stable=True)[:, :k]            # (a NaN sorts behind every value, -inf included)
         v = torch.gather(sv, 1, order)
         vo, io = _t(vals, (rows, k), torch.float32), _t(idx, (rows, k), torch.int64)
         vo.fill_(float('-inf'))
         io.fill_(-1)
-        vo[:, :order.shape[1]] = v
-        io[:, :order.shape[1]] = order
+        live = ~torch.isnan(v)                                            # NaN never ranks: padded like k > cols (include/tok.h)
+        vo[:, :order.shape[1]] = torch.where(live, v, torch.full_like(v, float('-inf')))
+        io[:, :order.shape[1]] = torch.where(live, order, torch.full_like(order, -1))
         return 0
 
     def tok_retrieval_nrel(self, labels, scores, n, n_cols, q_row, q_col, nq, n_rel, st):
@@ -1174,11 +1175,15 @@ class FakeTok:
         return 0
 
     def tok_relevance_matrix(self, la, lb, na, nb, R, st):
+        if na * nb > 0x7fffffff:
+            return -1
         a, b = _t(la, (na,), torch.int64), _t(lb, (nb,), torch.int64)
         _t(R, (na, nb), torch.float32).copy_((a[:, None] == b[None, :]).float())
         return 0
 
     def tok_relevance_matrix_multilabel(self, ya, yb, na, nb, classes, R, st):
+        if na * nb > 0x7fffffff:
+            return -1
         a, b = _t(ya, (na, classes), torch.float32), _t(yb, (nb, classes), torch.float32)
         _t(R, (na, nb), torch.float32).copy_((a @ b.t() > 0).float())
         return 0
@@ -1213,6 +1218,8 @@ class FakeTok:
         return 0
 
     def tok_contrastive_bwd(self, e1, e2, R, S, gscale, n1, n2, d, ld, margin, de1, de2, same, st):
+        if same and n1 != n2:
+            return -1
         a = _t(e1, (n1, ld), BF16)[:, :d].float()
         b = _t(e2, (n2, ld), BF16)[:, :d].float()
         r, s = _t(R, (n1, n2), torch.float32), _t(S, (n1, n2), torch.float32)

@@ -225,6 +225,42 @@ A_BF = 2.0 ** -8            # one bf16 rounding
 ERR_INVALID, ERR_WORKSPACE = -1, -3
 
 
+class Mat:
+    """[rows][cols] of pitch ld inside a GuardedSpan, `off` elements past its 16-byte aligned start.  Inputs: NaN in pads, lead
+    and guards; outputs: sentinels.  done(zero_pads) asserts every owned element written, and the pads zero or untouched."""
+
+    def __init__(self, rows, cols, ld=None, dtype=BF, init=None, nan=False, off=0):
+        ld = cols if ld is None else ld
+        self.rows, self.cols, self.ld, self.dtype, self.off = rows, cols, ld, dtype, off
+        self.span = GuardedSpan(rows * ld + off, dtype, 4 * ld + 64, nan_guard=nan)
+        self.bits = self.span.bits
+        self.full = self.span.view[off:].view(rows, ld)
+        self.view = self.full[:, :cols]
+        if init is not None:
+            self.view.copy_(init.reshape(rows, cols))
+        self.ptr = self.span.ptr + off * self.span.view.element_size()
+
+    def value(self):
+        return self.view.detach().cpu()
+
+    def done(self, what, zero_pads=False, finite=True):
+        self.span.check(what)
+        iv = self.full.view(_INT_OF[self.dtype])
+        assert bool((self.span.view[:self.off].view(_INT_OF[self.dtype]) == self.bits).all()), f'{what}: elements in front overwritten'
+        assert int((iv[:, :self.cols] == self.bits).sum()) == 0, f'{what}: owned elements never written'
+        if finite:
+            assert bool(torch.isfinite(self.view.float()).all()), f'{what}: not finite'
+        if zero_pads:
+            assert bool((self.full[:, self.cols:] == 0).all()), f'{what}: pad columns are not zero'
+        else:
+            assert bool((iv[:, self.cols:] == self.bits).all()), f'{what}: pad columns overwritten'
+
+    def intact(self, what):
+        self.span.check(what)
+        if self.bits == SENTINEL[self.dtype]:
+            assert self.span.untouched(), f'{what}: written by a refused call'
+
+
 def cdiv(a, b):
     return -(-a // b)
 

@@ -416,6 +416,8 @@ extern "C" int tok_embed_reg_bwd(const void* e, const float* row_reg, const floa
 extern "C" int tok_relevance_matrix(const int64_t* labels_a, const int64_t* labels_b, int na, int nb, float* R,
                                     void* stream) {
   TOK_CHECK_ARG(labels_a && labels_b && R && na > 0 && nb > 0, "tok_relevance_matrix: bad args");
+  TOK_CHECK_ARG((int64_t)na * nb <= 0x7fffffffLL, "tok_relevance_matrix: na * nb = %lld elements, at most 2^31 - 1 (int indices)",
+                (long long)na * nb);
   hipLaunchKernelGGL(relevance_kernel, dim3((na * nb + 255) / 256), dim3(256), 0, tok_stream(stream), labels_a,
                      labels_b, na, nb, R);
   TOK_CHECK_LAUNCH("tok_relevance_matrix");
@@ -425,6 +427,8 @@ extern "C" int tok_relevance_matrix(const int64_t* labels_a, const int64_t* labe
 extern "C" int tok_relevance_matrix_multilabel(const float* ya, const float* yb, int na, int nb, int classes, float* R,
                                                void* stream) {
   TOK_CHECK_ARG(ya && yb && R && na > 0 && nb > 0 && classes > 0, "tok_relevance_matrix_multilabel: bad args");
+  TOK_CHECK_ARG((int64_t)na * nb <= 0x7fffffffLL,
+                "tok_relevance_matrix_multilabel: na * nb = %lld elements, at most 2^31 - 1 (int indices)", (long long)na * nb);
   hipLaunchKernelGGL(relevance_ml_kernel, dim3((na * nb + 255) / 256), dim3(256), 0, tok_stream(stream), ya, yb, na, nb,
                      classes, R);
   TOK_CHECK_LAUNCH("tok_relevance_matrix_multilabel");
@@ -449,6 +453,8 @@ extern "C" int tok_contrastive_bwd(const void* e1, const void* e2, const float* 
                                    void* de2, int same_tensor, void* stream) {
   TOK_CHECK_ARG(e1 && e2 && R && S && de1 && n1 > 0 && n2 > 0 && d > 0 && ld >= d, "tok_contrastive_bwd: bad args");
   TOK_CHECK_ARG(same_tensor || de2, "tok_contrastive_bwd: de2 missing");
+  // the second launch below adds the n2 rows of the second operand onto de1, which holds n1 rows
+  TOK_CHECK_ARG(!same_tensor || n1 == n2, "tok_contrastive_bwd: same_tensor needs n1 == n2 (%d, %d)", n1, n2);
   hipStream_t st = tok_stream(stream);
   hipLaunchKernelGGL(contrastive_bwd_kernel, dim3((n1 + 3) / 4), dim3(256), 0, st, (const bf16*)e1, (const bf16*)e2,
                      R, S, gscale, n1, n2, d, ld, margin, 0, (bf16*)de1, 0);
