@@ -765,6 +765,22 @@ int tok_se_act_fwd(const void* x, int n, int hw, int c, int ld, int rd, int gate
 int tok_se_act_bwd(const void* dout, const void* x, int n, int hw, int c, int ld, int rd, int gate_kind, int act_kind,
                    const float* w1, const float* w2, const float* mean, const float* hid, const float* gate, float* dw1,
                    float* db1, float* dw2, float* db2, int param_accumulate, void* dx, int dx_accumulate, float* ws, void* stream);
+/* Efficient channel attention and the residual behind it ([timm 0.6.13] EcaModule as the `se` of a ResNet block; csrc/eca.hip):
+ *   mean[n][c] = mean_hw z[n],  gate = sigmoid(sum_{j<k} w[j] mean[n][c + j - k/2]) (zero outside 0..c-1),
+ *   out = relu(z * gate + shortcut).
+ * z / shortcut / out / dout / dz / dshort bf16 [n][hw][ld]; w fp32 [k]; mean, gate fp32 [n][c], written by tok_eca_fwd and read by
+ * tok_eca_bwd.  Served: c % 8 == 0, c <= 2048, ld >= c, ld % 8 == 0, k odd with 1 <= k <= 15, 1 <= n <= 65535; anything else
+ * returns TOK_ERR_INVALID with nothing launched or written.  ws: fp32 scratch of tok_eca_ws_floats(...) floats (both directions).
+ * tok_eca_bwd: dm = dout where the stored out > 0, else 0;  dw[j] (=|+=) sum_n sum_c da[n][c] mean[n][c + j - k/2] with
+ * da = (sum_hw dm * z) gate (1 - gate);  dz (=|+=) dm * gate + dmean / hw, dmean[n][c] = sum_j w[j] da[n][c - j + k/2];
+ * dshort (=|+=) dm.  dw, dz and dshort are each nullable: a NULL output is neither computed nor written.  Every sum folds in a
+ * fixed order (no float atomics): bit-reproducible run to run.                                                            */
+size_t tok_eca_ws_floats(int n, int hw, int c);
+int tok_eca_fwd(const void* z, const void* shortcut, int n, int hw, int c, int ld, const float* w, int k, float* mean,
+                float* gate, void* out, float* ws, void* stream);
+int tok_eca_bwd(const void* dout, const void* out, const void* z, int n, int hw, int c, int ld, const float* w, int k,
+                const float* mean, const float* gate, float* dw, int dw_accumulate, void* dz, int dz_accumulate, void* dshort,
+                int dshort_accumulate, float* ws, void* stream);
 
 /* ---- Global Context ViT: biased window attention with an optional shared query ([timm 0.6.13]
  * gcvit.WindowAttentionGlobal.forward between qkv and proj; csrc/gc_attn.hip on csrc/attn_tile.h) ----------------------------

@@ -203,6 +203,9 @@ PROTOTYPES = {
     'tok_se_act_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tok_se_act_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int,
                                _P, c_int, _P, _P]),
+    'tok_eca_ws_floats': (c_size_t, [c_int, c_int, c_int]),
+    'tok_eca_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P]),
+    'tok_eca_bwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P]),
     'tok_gc_attn_fwd': (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     'tok_gc_attn_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'tok_gc_attn_bwd': (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P,

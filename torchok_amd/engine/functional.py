@@ -1340,3 +1340,68 @@ def squeeze_excite(region: Region, x: TTensor, se: nn.Module, gate: str = 'sigmo
             x.uses += 1
         region.add(node)
     return out
+
+
+# ---- efficient channel attention + residual (ECA-ResNet) ----------------------------------------------------------------
+
+class _EcaResidualNode(Node):
+    needs_backward = True
+
+    def backward(self):
+        g = self.out.grad
+        if g is None:
+            return
+        self.out.grad = None
+        z, sc, w = self.z, self.shortcut, self.se.conv.weight
+        lib = _C.lib()
+        n, h, wd, c = z.shape
+        dw, dw_acc = PG.sink(w) if w.requires_grad else (None, 0)
+        dz, dz_acc = grad_target(z) if z.requires_grad else (None, 0)
+        ds, ds_acc = grad_target(sc) if sc.requires_grad else (None, 0)
+        ws = torch.empty(lib.tok_eca_ws_floats(n, h * wd, c), dtype=F32, device=g.device)
+        _C.check(lib.tok_eca_bwd(ptr(g), ptr(self.out.data), ptr(z.data), n, h * wd, c, c, ptr(w), w.shape[-1], ptr(self.mean),
+                                 ptr(self.gate), ptr(dw), dw_acc, ptr(dz), dz_acc, ptr(ds), ds_acc, ptr(ws), stream_ptr()),
+                 'tok_eca_bwd')
+        if dw is not None:
+            PG.commit(w, dw, dw_acc)
+        if self.region is not None:
+            self.region.keep_until_join(ws)
+
+    def release(self):
+        self.z = self.shortcut = self.out = self.se = self.mean = self.gate = None
+
+
+def eca_residual(region: Region, z: TTensor, se: nn.Module, shortcut: TTensor) -> TTensor:
+    """relu(z * sigmoid(conv1d_k(mean_hw(z))) + shortcut)  ([timm 0.6.13] EcaModule as the `se` of a ResNet block, then the
+    block's residual add and last activation).  `se.conv` is the nn.Conv1d(1, 1, k, padding=k // 2, bias=False) over the channel
+    axis, a parameter container; z is the block's last BatchNorm output (conv_bn_act(..., relu=False))."""
+    await_ready(z, shortcut)
+    conv = se.conv
+    k = conv.kernel_size[0] if isinstance(conv, nn.Conv1d) else 0
+    if k == 0 or conv.in_channels != 1 or conv.out_channels != 1 or conv.bias is not None \
+            or k % 2 != 1 or conv.padding[0] != k // 2 or conv.stride[0] != 1 or conv.dilation[0] != 1:
+        raise NotImplementedError('torchok_amd ECA: nn.Conv1d(1, 1, k, padding=k // 2, bias=False) with odd k')
+    if z.data.dim() != 4 or z.c != z.cp or shortcut.data.shape != z.data.shape or shortcut.c != z.c:
+        raise NotImplementedError('torchok_amd ECA: a 4-D input of 8k channels and a shortcut of the same shape')
+    lib, st = _C.lib(), stream_ptr()
+    n, h, wd, c = z.shape
+    dev = z.data.device
+    w = conv.weight
+    mean = torch.empty((n, c), dtype=F32, device=dev)
+    gate = torch.empty((n, c), dtype=F32, device=dev)
+    out_data = torch.empty_like(z.data)
+    ws = torch.empty(lib.tok_eca_ws_floats(n, h * wd, c), dtype=F32, device=dev)
+    _C.check(lib.tok_eca_fwd(ptr(z.data), ptr(shortcut.data), n, h * wd, c, c, ptr(w), k, ptr(mean), ptr(gate), ptr(out_data),
+                             ptr(ws), st), 'tok_eca_fwd')
+    req = bool(region.grad_mode and (z.requires_grad or shortcut.requires_grad or w.requires_grad))
+    out = TTensor(out_data, c, requires_grad=req)
+    if req:
+        node = _EcaResidualNode()
+        node.z, node.shortcut, node.out, node.se, node.mean, node.gate = z, shortcut, out, se, mean, gate
+        out.node = node
+        if z.requires_grad:
+            z.uses += 1
+        if shortcut.requires_grad:
+            shortcut.uses += 1
+        region.add(node)
+    return out

@@ -12,9 +12,9 @@ pass), activations stay NHWC bf16 in HBM between units, and the whole backbone i
 autograd node.  The nn.Conv2d / nn.BatchNorm2d children are parameter containers only.
 
 Only the plain (v1.5) family is built: no SE / anti-aliasing / drop-block
-(plus the other plain-architecture entrypoints at the end of the file, the d / t stems and the ResNeXts of group width
-4 ... 64 on the grouped 3x3 unit; the s-stem, SE/ECA, blur-pool and RS variants of the reference are outside the hot-path
-scope).
+(plus the other plain-architecture entrypoints at the end of the file, the d / t stems, the ResNeXts of group width
+4 ... 64 on the grouped 3x3 unit and the ECA-ResNets on the channel-attention residual unit, EF.eca_residual; the s-stem, SE,
+blur-pool and RS variants of the reference are outside the hot-path scope).
 """
 import math
 from typing import List
@@ -32,6 +32,27 @@ def get_padding(kernel_size: int, stride: int, dilation: int = 1) -> int:
     return ((stride - 1) + dilation * (kernel_size - 1)) // 2
 
 
+def eca_kernel_size(channels: int, gamma: int = 2, beta: int = 1) -> int:
+    """[timm 0.6.13] EcaModule: the window grows with log2 of the channel count (256 ... 1024 -> 5, 2048 -> 7), at least 3."""
+    t = int(abs(math.log(channels, 2) + beta) / gamma)
+    return max(t if t % 2 else t + 1, 3)
+
+
+class EcaModule(nn.Module):
+    """Efficient channel attention ([timm 0.6.13] layers/eca.py): a k-tap convolution over the channel axis of the pooled map,
+    sigmoid, and a per-channel product.  A parameter container: EF.eca_residual runs it together with the block's residual."""
+
+    def __init__(self, channels: int):
+        super().__init__()
+        k = eca_kernel_size(channels)
+        self.conv = nn.Conv1d(1, 1, kernel_size=k, padding=k // 2, bias=False)
+
+
+def _attn(attn_layer, channels):
+    """The block's `se` child: the ECA module or None (the block has refused every other attention layer, SE among them)."""
+    return EcaModule(channels) if attn_layer == 'eca' else None
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
@@ -40,8 +61,8 @@ class BasicBlock(nn.Module):
                  attn_layer=None, aa_layer=None, drop_block=None, drop_path=None):
         super().__init__()
         assert cardinality == 1 and base_width == 64, 'BasicBlock only supports cardinality=1, base_width=64'
-        _unsupported(dilation=dilation != 1, attn_layer=attn_layer, aa_layer=aa_layer, drop_block=drop_block,
-                     drop_path=drop_path)
+        _unsupported(dilation=dilation != 1, attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer,
+                     drop_block=drop_block, drop_path=drop_path)
         first_planes = planes // reduce_first
         outplanes = planes * self.expansion
         self.conv1 = nn.Conv2d(inplanes, first_planes, kernel_size=3, stride=stride, padding=1, bias=False)
@@ -49,6 +70,7 @@ class BasicBlock(nn.Module):
         self.act1 = act_layer(inplace=True)
         self.conv2 = nn.Conv2d(first_planes, outplanes, kernel_size=3, padding=1, bias=False)
         self.bn2 = norm_layer(outplanes)
+        self.se = _attn(attn_layer, outplanes)
         self.act2 = act_layer(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -60,6 +82,8 @@ class BasicBlock(nn.Module):
         r = engine.current_region()
         shortcut = self._shortcut(r, x)
         y = EF.conv_bn_act(r, x, self.conv1, self.bn1, relu=True)
+        if self.se is not None:
+            return EF.eca_residual(r, EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=False), self.se, shortcut)
         return EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True, shortcut=shortcut)
 
     def _shortcut(self, r, x):
@@ -73,8 +97,8 @@ class Bottleneck(nn.Module):
                  reduce_first=1, dilation=1, first_dilation=None, act_layer=nn.ReLU, norm_layer=nn.BatchNorm2d,
                  attn_layer=None, aa_layer=None, drop_block=None, drop_path=None):
         super().__init__()
-        _unsupported(dilation=dilation != 1, attn_layer=attn_layer, aa_layer=aa_layer, drop_block=drop_block,
-                     drop_path=drop_path)
+        _unsupported(dilation=dilation != 1, attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer,
+                     drop_block=drop_block, drop_path=drop_path)
         width = int(math.floor(planes * (base_width / 64)) * cardinality)
         first_planes = width // reduce_first
         outplanes = planes * self.expansion
@@ -87,6 +111,7 @@ class Bottleneck(nn.Module):
         self.act2 = act_layer(inplace=True)
         self.conv3 = nn.Conv2d(width, outplanes, kernel_size=1, bias=False)
         self.bn3 = norm_layer(outplanes)
+        self.se = _attn(attn_layer, outplanes)
         self.act3 = act_layer(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -103,6 +128,8 @@ class Bottleneck(nn.Module):
         # whole tensor runs in the ring kernel's staged epilogue instead of the parity-class kernel's read-modify-write of
         # untouched pixels
         shortcut = _shortcut(r, x, self.downsample)
+        if self.se is not None:
+            return EF.eca_residual(r, EF.conv_bn_act(r, y, self.conv3, self.bn3, relu=False), self.se, shortcut)
         return EF.conv_bn_act(r, y, self.conv3, self.bn3, relu=True, shortcut=shortcut)
 
 
@@ -355,3 +382,15 @@ ssl_resnext101_32x8d = _plain('ssl_resnext101_32x8d', Bottleneck, [3, 4, 23, 3],
 swsl_resnext50_32x4d = _plain('swsl_resnext50_32x4d', Bottleneck, [3, 4, 6, 3], 'resnet.py:963-971', default_pretrained=True, **_X4)
 swsl_resnext101_32x4d = _plain('swsl_resnext101_32x4d', Bottleneck, [3, 4, 23, 3], 'resnet.py:974-982', default_pretrained=True, **_X4)
 swsl_resnext101_32x8d = _plain('swsl_resnext101_32x8d', Bottleneck, [3, 4, 23, 3], 'resnet.py:985-993', default_pretrained=True, **_X8)
+# ECA: efficient channel attention behind the last BatchNorm of every block (csrc/eca.hip, EF.eca_residual)
+_ECA = dict(block_args=dict(attn_layer='eca'))
+ecaresnet26t = _plain('ecaresnet26t', Bottleneck, [2, 2, 2, 2], 'resnet.py:1008-1017', **_T, **_ECA)
+ecaresnet50d = _plain('ecaresnet50d', Bottleneck, [3, 4, 6, 3], 'resnet.py:1020-1027', **_D, **_ECA)
+ecaresnet50t = _plain('ecaresnet50t', Bottleneck, [3, 4, 6, 3], 'resnet.py:1030-1038', **_T, **_ECA)
+ecaresnetlight = _plain('ecaresnetlight', Bottleneck, [1, 1, 11, 3], 'resnet.py:1041-1048', stem_width=32, avg_down=True, **_ECA)
+ecaresnet101d = _plain('ecaresnet101d', Bottleneck, [3, 4, 23, 3], 'resnet.py:1051-1058', **_D, **_ECA)
+ecaresnet200d = _plain('ecaresnet200d', Bottleneck, [3, 24, 36, 3], 'resnet.py:1061-1068', **_D, **_ECA)
+ecaresnet269d = _plain('ecaresnet269d', Bottleneck, [3, 30, 48, 8], 'resnet.py:1071-1078', **_D, **_ECA)
+ecaresnext26t_32x4d = _plain('ecaresnext26t_32x4d', Bottleneck, [2, 2, 2, 2], 'resnet.py:1081-1090', **_X4, **_T, **_ECA)
+ecaresnext50t_32x4d = _plain('ecaresnext50t_32x4d', Bottleneck, [2, 2, 2, 2], 'resnet.py:1093-1101 (the reference builds it with the layers of the 26t)',
+                             **_X4, **_T, **_ECA)
