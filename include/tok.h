@@ -648,13 +648,18 @@ int tok_mlp_bwd_dx(const void* dy, const void* w2_dgrad, const void* pre, const 
  * image, out = q A^T.  tok_chan_gram: out[u] = f(scale * X_u^T Y_u), u = image * heads + head, X / Y the 32-wide head
  * slices of bf16 token matrices (row pitches ldx / ldy, pointers already offset to the q / k / v block), fp32
  * [images*heads][32][32]; mode 0: f = id, 1: row softmax, 2: softmax backward A o (G - rowsum(G o A)) with A = a_in.
- * tok_chan_apply: out[n][h*32+i] = scale * sum_j M[u][i][j] x[n][h*32+j] (transposed != 0: M[u][j][i]).           */
+ * tok_chan_apply: out[n][h*32+i] = scale * sum_j M[u][i][j] x[n][h*32+j] (transposed != 0: M[u][j][i]).
+ * Both read and write nothing outside the heads * 32 columns they are pointed at (tok_chan_apply writes a q / k / v third of
+ * a wider gradient matrix in place).  x, y, out: 16-byte aligned, pitches multiples of 8 (TOK_ERR_INVALID otherwise: the
+ * kernels move 8 bf16 per access); images * heads <= 65535 for tok_chan_apply.  Fixed summation order: the same call
+ * gives the same bits.                                                                                              */
 int tok_chan_gram(const void* x, int ldx, const void* y, int ldy, int rows_per_image, int images, int heads,
                   float scale, int mode, const float* a_in, float* out, void* stream);
 int tok_chan_apply(const void* x, int ldx, const float* m, int transposed, float scale, int rows_per_image,
                    int images, int heads, void* out, int ldo, void* stream);
 /* out (+)= a + row_scale[row / rows_per_sample] * b on bf16 [rows][ld]; a and row_scale may be NULL.  The pre-norm
- * residual x + drop_path(f(norm(x))) of davit.py:262-271,330-366 and its backward (db = row_scale * dout).         */
+ * residual x + drop_path(f(norm(x))) of davit.py:262-271,330-366 and its backward (db = row_scale * dout).  The whole
+ * pitch is data (ld % 8 == 0); a, b, out 16-byte aligned; row_scale needs rows_per_sample > 0 (TOK_ERR_INVALID otherwise). */
 int tok_scale_rows_add(const void* a, const void* b, const float* row_scale, int rows_per_sample, void* out,
                        int accumulate, int64_t rows, int ld, void* stream);
 
@@ -669,7 +674,19 @@ int tok_scale_rows_add(const void* a, const void* b, const float* row_scale, int
  *                         [images][tok_weighted_pool_chunks(n)][k][c], fixed-order fold)
  *   tok_softmax_rows_f32 / _bwd_f32   softmax over the k entries of a row and its backward p o (dp - <p, dp>)
  *   tok_softmax_cols_fwd / _bwd       softmax over the n pixels of every (image, class) of bf16 logits * scale
- *   tok_channel_scale     out (+)= x * s[b][c]   (Dropout2d of SpatialOCR, :121-124, and its backward)            */
+ *   tok_channel_scale     out (+)= x * s[b][c]   (Dropout2d of SpatialOCR, :121-124, and its backward)
+ * Pad columns (the pad columns of an INPUT never enter a result, whatever they hold):
+ *   tok_pix_class_matmul  any ldx, ldm >= c; out is dense [images][n][k].
+ *   tok_class_pix_expand  ldo % 8 == 0, ldo >= round8(c), out 16-byte aligned; columns c .. round8(c) are written 0 on a
+ *                         fresh call and re-stored as read under accumulate; columns round8(c) .. ldo are never touched.
+ *   tok_weighted_pool     any ldx, ldo >= c; the pad columns of out and every element of `partial` past
+ *                         images * chunks * k * c are never touched.  Fixed order: the same call gives the same bits.
+ *   tok_softmax_cols_bwd  writes the whole pitch: columns k .. ld are 0 on a fresh call and keep what they held under accumulate.
+ *   tok_channel_scale     ld % 8 == 0, x and out 16-byte aligned; columns c .. ld of out are written 0 on a fresh call and keep
+ *                         what they held under accumulate (a select, not a product with 0: a NaN in a pad of x stays there).
+ * Limits (TOK_ERR_INVALID otherwise): k <= 64 except for tok_softmax_rows_f32 / _bwd_f32; the class matrix in fp32
+ * (k * c, c rounded up to 8 for tok_class_pix_expand) fits 64 KB of LDS; tok_weighted_pool: k * c <= 10240 and
+ * 32 * (c + k) (c <= 256) or 16 * (c + k) floats fit 64 KB.                                                              */
 int tok_pix_class_matmul(const void* x, int ldx, const void* m, int ldm, int images, int n, int k, int c, float scale,
                          float* out, void* stream);
 int tok_class_pix_expand(const float* w, const void* m, int ldm, int images, int n, int k, int c, float scale, void* out,
@@ -688,7 +705,10 @@ int tok_channel_scale(const void* x, const float* s, void* out, int accumulate, 
 /* Depthwise 3x3 / stride 1 / pad 1 convolution with bias (ConvPosEnc.proj, davit.py:101-106; only reached with
  * cpe_act=True).  x / out bf16 NHWC [n][h][w][ld], w fp32 [c][3][3] (the master), bias fp32 [c] or NULL.  flip = 1 applies
  * the tap-flipped filter (the data gradient).  tok_dwconv3x3_wgrad: dw fp32 [c][3][3], db fp32 [c]; partial fp32
- * [tok_dwconv3x3_wgrad_blocks(n, h)][c][10], fixed-order fold.                                                        */
+ * [tok_dwconv3x3_wgrad_blocks(n, h)][c][10], fixed-order fold (the same call gives the same bits; the call may use fewer
+ * blocks than it is sized for and then leaves the tail of `partial` untouched).  tok_dwconv3x3: ld % 8 == 0, x and out
+ * 16-byte aligned (TOK_ERR_INVALID otherwise); the pad columns c .. ld of x are never used, those of out are written 0 on a fresh
+ * call and keep what they held under accumulate.  tok_dwconv3x3_wgrad: any ld >= c; dw or db may be NULL, not both.          */
 int tok_dwconv3x3(const void* x, const float* w, const float* bias, void* out, int accumulate, int flip, int n, int h, int wd,
                   int c, int ld, void* stream);
 int tok_dwconv3x3_wgrad_blocks(int n, int h);

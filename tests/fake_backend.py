@@ -886,11 +886,14 @@ class FakeTok:
         return 0
 
     def tok_channel_scale(self, x, s, out, accumulate, images, n, c, ld, st):
-        xv = _t(x, (images, n, ld), BF16).float()
-        sv = torch.zeros(images, 1, ld)
-        sv[:, 0, :c] = _t(s, (images, c), torch.float32)
+        xv = _t(x, (images, n, ld), BF16)[..., :c].float()               # the pad columns of x never enter a result
+        sv = _t(s, (images, c), torch.float32)[:, None, :]
         o = _t(out, (images, n, ld), BF16)
-        o.copy_(_bf(xv * sv + (o.float() if accumulate else 0)))
+        if accumulate:
+            o[..., :c] = _bf(xv * sv + o[..., :c].float())                # pad columns keep what they held
+        else:
+            o.zero_()
+            o[..., :c] = _bf(xv * sv)
         return 0
 
     # ---- depthwise 3x3 (DaViT ConvPosEnc with activation) -----------------------------------------------------------

@@ -13,6 +13,9 @@ namespace {
 
 constexpr int HD = 32;
 
+// the 16-byte loads and stores (ldg16 / stg16) need a 16-byte aligned base as well as a pitch of 8 elements
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // out[u][i][j] = epilogue( scale * sum_n x[n][h*32+i] * y[n][h*32+j] ),  u = image * heads + h
 // mode 0: identity   1: row softmax   2: softmax backward with the saved A: A o (G - rowsum(G o A))
 __global__ __launch_bounds__(256) void chan_gram_kernel(const bf16* __restrict__ x, int ldx, const bf16* __restrict__ y,
@@ -149,6 +152,7 @@ extern "C" int tok_chan_gram(const void* x, int ldx, const void* y, int ldy, int
   TOK_CHECK_ARG(x && y && out && rows_per_image > 0 && images > 0 && heads > 0 && ldx >= heads * HD && ldy >= heads * HD &&
                 (ldx & 7) == 0 && (ldy & 7) == 0, "tok_chan_gram: bad args (head_dim is 32)");
   TOK_CHECK_ARG(mode >= 0 && mode <= 2 && (mode != 2 || a_in), "tok_chan_gram: mode 0..2 (2 needs the saved attention)");
+  TOK_CHECK_ARG(al16(x) && al16(y), "tok_chan_gram: x / y must be 16-byte aligned");
   hipLaunchKernelGGL(chan_gram_kernel, dim3(images * heads), dim3(256), 0, tok_stream(stream), (const bf16*)x, ldx,
                      (const bf16*)y, ldy, rows_per_image, heads, scale, mode, a_in, out);
   TOK_CHECK_LAUNCH("tok_chan_gram");
@@ -160,6 +164,7 @@ extern "C" int tok_chan_apply(const void* x, int ldx, const float* m, int transp
   TOK_CHECK_ARG(x && m && out && rows_per_image > 0 && images > 0 && heads > 0 && ldx >= heads * HD && ldo >= heads * HD &&
                 (ldx & 7) == 0 && (ldo & 7) == 0, "tok_chan_apply: bad args (head_dim is 32)");
   TOK_CHECK_ARG((long long)images * heads <= 65535, "tok_chan_apply: images * heads exceeds 65535");
+  TOK_CHECK_ARG(al16(x) && al16(out), "tok_chan_apply: x / out must be 16-byte aligned");
   hipLaunchKernelGGL(chan_apply_kernel, dim3(tok_cdiv(rows_per_image, 128), images * heads), dim3(256), 0,
                      tok_stream(stream), (const bf16*)x, ldx, m, transposed, scale, rows_per_image, heads, (bf16*)out, ldo);
   TOK_CHECK_LAUNCH("tok_chan_apply");
@@ -170,6 +175,7 @@ extern "C" int tok_scale_rows_add(const void* a, const void* b, const float* row
                                   int accumulate, int64_t rows, int ld, void* stream) {
   TOK_CHECK_ARG(b && out && rows > 0 && ld > 0 && (ld & 7) == 0 && (!row_scale || rows_per_sample > 0),
                 "tok_scale_rows_add: bad args");
+  TOK_CHECK_ARG(al16(a) && al16(b) && al16(out), "tok_scale_rows_add: a / b / out must be 16-byte aligned");
   const size_t n8 = (size_t)rows * (ld >> 3);
   size_t blocks = (n8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -299,6 +305,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_fold_kernel(const float* 
 extern "C" int tok_dwconv3x3(const void* x, const float* w, const float* bias, void* out, int accumulate, int flip, int n, int h,
                              int wd, int c, int ld, void* stream) {
   TOK_CHECK_ARG(x && w && out && n > 0 && h > 0 && wd > 0 && c > 0 && ld >= c && (ld & 7) == 0, "tok_dwconv3x3: bad args");
+  TOK_CHECK_ARG(al16(x) && al16(out), "tok_dwconv3x3: x / out must be 16-byte aligned");
   const size_t total = (size_t)n * h * wd * (ld >> 3);
   size_t blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;

@@ -233,11 +233,16 @@ __global__ __launch_bounds__(256) void channel_scale_kernel(const bf16* __restri
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int c = cg * 8 + e;
-      o[e] = f2bf(bf2f(v[e]) * (c < C ? s[(size_t)b * C + c] : 0.f) + bf2f(old[e]));
+      // a select, not a product with 0: a pad column of x (NaN, Inf) never enters out; out's pad is 0 fresh, kept under accumulate
+      const float r = bf2f(v[e]) * s[(size_t)b * C + (c < C ? c : C - 1)] + bf2f(old[e]);
+      o[e] = c < C ? f2bf(r) : old[e];
     }
     stg16(out + off, o);
   }
 }
+
+// the 16-byte loads and stores (ldg16 / stg16) need a 16-byte aligned base as well as a pitch of 8 elements
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline unsigned blocks_for(size_t n, unsigned cap = 2048) {
   size_t b = (n + 255) / 256;
@@ -262,6 +267,7 @@ extern "C" int tok_class_pix_expand(const float* w, const void* m, int ldm, int 
                                     void* out, int ldo, int accumulate, void* stream) {
   TOK_CHECK_ARG(w && m && out && images > 0 && n > 0 && k > 0 && k <= KMAX && c > 0 && ldm >= c && ldo >= ((c + 7) & ~7) &&
                 (ldo & 7) == 0, "tok_class_pix_expand: bad args (at most 64 classes)");
+  TOK_CHECK_ARG(al16(out), "tok_class_pix_expand: out must be 16-byte aligned");
   const size_t smem = (size_t)k * ((c + 7) & ~7) * sizeof(float);
   TOK_CHECK_ARG(smem <= 64 * 1024 && images <= 65535, "tok_class_pix_expand: class matrix of %d x %d does not fit LDS", k, c);
   hipLaunchKernelGGL(class_pix_expand_kernel, dim3(blocks_for((size_t)n * ((c + 7) >> 3), 1024), images), dim3(256), smem,
@@ -329,6 +335,7 @@ extern "C" int tok_channel_scale(const void* x, const float* s, void* out, int a
                                  void* stream) {
   TOK_CHECK_ARG(x && s && out && images > 0 && images <= 65535 && n > 0 && c > 0 && ld >= c && (ld & 7) == 0,
                 "tok_channel_scale: bad args");
+  TOK_CHECK_ARG(al16(x) && al16(out), "tok_channel_scale: x / out must be 16-byte aligned");
   hipLaunchKernelGGL(channel_scale_kernel, dim3(blocks_for((size_t)n * (ld >> 3), 1024), images), dim3(256), 0,
                      tok_stream(stream), (const bf16*)x, s, (bf16*)out, accumulate, n, c, ld);
   TOK_CHECK_LAUNCH("tok_channel_scale");
