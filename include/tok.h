@@ -801,6 +801,18 @@ int tok_eca_fwd(const void* z, const void* shortcut, int n, int hw, int c, int l
 int tok_eca_bwd(const void* dout, const void* out, const void* z, int n, int hw, int c, int ld, const float* w, int k,
                 const float* mean, const float* gate, float* dw, int dw_accumulate, void* dz, int dz_accumulate, void* dshort,
                 int dshort_accumulate, float* ws, void* stream);
+/* Phase split / merge by d (space-to-batch; csrc/phase.hip): the layout a dilated ResNet stage runs in, where a 3x3 convolution
+ * of dilation d and padding d is the plain padding-1 one on every phase image.
+ *   x / merged out: bf16 [n][h][w][ld];  phased: bf16 [n][d][d][h/d][w/d][ld], i.e. n*d*d images of h/d x w/d.
+ *   tok_phase_split: out[i][a][b][y][x][k] = x[i][y*d + a][x*d + b][k], k < c;  tok_phase_merge: the inverse.  h and w are
+ *   always the sizes of the MERGED tensor.
+ * Without `accumulate` a copy bit for bit (NaN payloads, infinities, -0); with it out = bf16(float(out) + float(v)), rounded
+ * once (the backward form: the gradient of a split is a merge and the reverse).  Channels [c, ld) are never read into a result
+ * and never written.  Served: d in {2, 4}, h % d == 0, w % d == 0, c % 8 == 0, c >= 8, ld >= c, ld % 8 == 0, n >= 1,
+ * n*h*w < 2^31 pixels (64-bit element offsets), distinct non-null 16-byte-aligned pointers; anything else returns
+ * TOK_ERR_INVALID with nothing launched or written.                                                                       */
+int tok_phase_split(const void* x, int n, int h, int w, int c, int ld, int d, void* out, int accumulate, void* stream);
+int tok_phase_merge(const void* xs, int n, int h, int w, int c, int ld, int d, void* out, int accumulate, void* stream);
 
 /* ---- Global Context ViT: biased window attention with an optional shared query ([timm 0.6.13]
  * gcvit.WindowAttentionGlobal.forward between qkv and proj; csrc/gc_attn.hip on csrc/attn_tile.h) ----------------------------

@@ -206,6 +206,8 @@ PROTOTYPES = {
     'tok_eca_ws_floats': (c_size_t, [c_int, c_int, c_int]),
     'tok_eca_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P]),
     'tok_eca_bwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P]),
+    'tok_phase_split': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    'tok_phase_merge': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     'tok_gc_attn_fwd': (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
     'tok_gc_attn_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'tok_gc_attn_bwd': (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P,

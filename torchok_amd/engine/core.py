@@ -103,9 +103,11 @@ def ptr(t: Optional[torch.Tensor]):
 class TTensor:
     """Engine tensor: bf16, channel-last, channels padded to a multiple of 8.
 
-    data: (N, H, W, Cp) or (N, Cp);  c: logical channel count (<= Cp)."""
+    data: (N, H, W, Cp) or (N, Cp);  c: logical channel count (<= Cp).
+    phase: 1, or 2 / 4 inside a dilated stage: `data` is then physically (N * phase^2, H / phase, W / phase, Cp), the phase
+    images of functional.phase_split (`phase_steps`: the split factors that led there, outermost first)."""
     __slots__ = ('data', 'c', 'node', 'grad', 'grad_owned', 'requires_grad', 'uses', 'arrived', 'ready', 'gevents',
-                 'sub_closers', 'grad_sub', 'colsum_part', 'affine', '__weakref__')
+                 'sub_closers', 'grad_sub', 'colsum_part', 'affine', 'phase', 'phase_steps', '__weakref__')
 
     def __init__(self, data: torch.Tensor, c: int, requires_grad: bool = False, node=None):
         self.data = data
@@ -122,6 +124,8 @@ class TTensor:
         self.grad_sub = None  # pending contribution: gradient of the stride-2 pixel subsample of this tensor (backward)
         self.colsum_part = None  # (partial [rows][C] fp32, rows): per-block column sums left by the pass that produced `data`
         self.affine = None  # (scale, shift) fp32 [Cp]: `data` is a RAW conv output whose BatchNorm apply is left to the consumer (conv_bn_act defer_apply)
+        self.phase = 1      # > 1: `data` holds phase images (space-to-batch by `phase`), see functional.phase_split
+        self.phase_steps = ()   # the split factors behind `phase`, outermost first: (2,), (4,) or (2, 2)
 
     @property
     def cp(self) -> int:
@@ -156,7 +160,15 @@ def _await(events):
             cur.wait_event(ev)
 
 
-def await_ready(*tensors, affine_ok: bool = False):
+def refuse_phased(t, who: str = 'a consumer'):
+    """A tensor in phase layout (functional.phase_split) is only for the units that say they take it (phase_ok)."""
+    if getattr(t, 'phase', 1) != 1:
+        raise RuntimeError(f'torchok_amd: a tensor in phase layout (phase {t.phase}, functional.phase_split) reached {who} '
+                           f'that does not take it; only 1x1 / stride-1 convolutions, 3x3 / stride-1 convolutions whose '
+                           f'dilation and padding equal the phase, and the fused residual unit do (merge it first)')
+
+
+def await_ready(*tensors, affine_ok: bool = False, phase_ok: bool = False):
     """Forward: make the current stream wait for tensors that were produced on a branch stream, and tell the caching
     allocator about the new reader: the buffers belong to the branch stream's pool, and without `record_stream` a buffer
     whose last reference dies on the launch thread (no-grad mode; operands no unit keeps for its backward, like a bias
@@ -167,7 +179,8 @@ def await_ready(*tensors, affine_ok: bool = False):
     the branch's kernels are still queued.  So it is `record_stream`ed on the branch stream (a no-op for a buffer the branch
     allocated itself).
     Arguments: TTensors, or objects with `ready` and a `tensors` tuple (Region.branch's publish).  A TTensor that carries
-    `.affine` (a raw conv output whose BatchNorm apply is deferred) is refused unless the consumer applies it (affine_ok)."""
+    `.affine` (a raw conv output whose BatchNorm apply is deferred) is refused unless the consumer applies it (affine_ok), and
+    one in phase layout (`.phase` != 1) unless the consumer runs on phase images (phase_ok)."""
     cur = None
     branch = getattr(_tls, 'branch', None)
     for t in tensors:
@@ -176,6 +189,8 @@ def await_ready(*tensors, affine_ok: bool = False):
         if not affine_ok and getattr(t, 'affine', None) is not None:
             raise RuntimeError('torchok_amd: a tensor with a deferred BatchNorm apply (conv_bn_act defer_apply) reached a '
                                'consumer that does not apply it; only resample.fuse_sum_relu does')
+        if not phase_ok:
+            refuse_phased(t)
         if t.ready is not None:
             _await((t.ready,))
             if cur is None:
@@ -588,6 +603,8 @@ class Region:
         self._join_forward()
         if any(o.affine is not None for o in outs):
             raise RuntimeError('torchok_amd: a region output with a deferred BatchNorm apply (conv_bn_act defer_apply)')
+        for o in outs:
+            refuse_phased(o, 'Region.output')
         need = self.grad_mode and any(o.requires_grad for o in outs)
         if not need:
             for n in self.nodes:

@@ -12,6 +12,8 @@ dwconv_bn_act             depthwise conv -> batch_norm -> relu           ([timm]
 gconv_bn_act              grouped 3x3 conv -> batch_norm -> relu         ([timm] Bottleneck.conv2 with groups = cardinality: ResNeXt)
 squeeze_excite            x * gate(expand(relu(reduce(mean(x)))))        ([timm] efficientnet_blocks.SqueezeExcite;
                           gate = sigmoid or hard sigmoid)
+phase_split / phase_merge the layout a dilated ResNet stage runs in: conv2d(dilation=d, padding=d) as the plain 3x3 on the d x d
+                          phase images (resnet.py:363-405 with output_stride 8 / 16)
 
 conv_bn_act / dwconv_bn_act take act='hard_swish' (MobileNetV3) or act='relu6' (EfficientNet-Lite): the mask-less activation
 path of csrc/bn.hip.
@@ -27,7 +29,8 @@ from torch import nn
 from .. import _C
 from .core import _ms as _core_ms
 from . import paramgrad as PG
-from .core import BF16, Node, Region, TTensor, await_ready, donate_grad, grad_target, is_last_contribution, pad8, ptr, stream_ptr
+from .core import (BF16, Node, Region, TTensor, await_ready, donate_grad, grad_target, is_last_contribution, pad8, ptr,
+                   refuse_phased, stream_ptr)
 
 F32 = torch.float32
 
@@ -220,8 +223,20 @@ def _conv_desc(x: TTensor, k_pad: int, r: int, s: int, stride: int, pad: int) ->
     return _C.ConvDesc(n, h, w, cp, k_pad, r, s, p, q, stride, pad, 8 if cp == 4 else s)
 
 
-def _check_conv(conv: nn.Conv2d):
-    if conv.groups != 1 or tuple(conv.dilation) != (1, 1):
+def _phased_conv_ok(conv: nn.Module, phase: int) -> bool:
+    """Does this layer commute with the phase layout of its input?  A 1x1 / stride-1 convolution does; a 3x3 / stride-1 one
+    whose dilation and padding both equal the phase IS the plain padding-1 convolution on every phase image."""
+    if not isinstance(conv, nn.Conv2d) or isinstance(conv.padding, str):
+        return False
+    ks, st, pd, dl = tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation)
+    if ks == (1, 1):
+        return st == (1, 1) and pd == (0, 0) and dl == (1, 1)
+    return ks == (3, 3) and st == (1, 1) and dl == (phase, phase) and pd == (phase, phase)
+
+
+def _check_conv(conv: nn.Conv2d, phase: int = 1):
+    """`phase` != 1: the caller has checked the layer with _phased_conv_ok (its dilation is then the phase, and served)."""
+    if conv.groups != 1 or (phase == 1 and tuple(conv.dilation) != (1, 1)):
         raise NotImplementedError('torchok_amd conv: dilation == 1 and groups == 1 (dense, conv_bn_act), groups == channels '
                                   '(depthwise 3x3 / 5x5, dwconv_bn_act) or a grouped 3x3 of group width 4, 8, 16, 32 or 64 '
                                   '(gconv_bn_act) only')
@@ -684,6 +699,13 @@ def _unit3_forward(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm
     return out
 
 
+def _inherit_phase(out: TTensor, x: TTensor) -> TTensor:
+    """The output of a unit that ran on phase images is in the phase layout of its input."""
+    if x.phase != 1:
+        out.phase, out.phase_steps = x.phase, x.phase_steps
+    return out
+
+
 FUSE_STEM_POOL = os.environ.get('TOK_FUSE_STEM_POOL', '1') != '0'
 STEM_POOLED_STATS = os.environ.get('TOK_STEM_POOLED_STATS', '1') != '0'   # BatchNorm-backward sums of the fused stem in the pooled domain
 
@@ -701,7 +723,12 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     defer_apply=True (BatchNorm, no activation, no shortcut — the last unit of an HRNet fuse path): the apply pass is NOT run;
     the returned tensor holds the RAW convolution output and carries `.affine = (scale, shift)` for a consumer that applies
     them itself (resample.fuse_sum_relu: the write and the read of the normalised term are one fma there).  Its backward is
-    the unit's usual one (it never reads the normalised values of a unit without activation)."""
+    the unit's usual one (it never reads the normalised values of a unit without activation).
+    An input in phase layout (phase_split; `bn=None` too): a 1x1 / stride-1 convolution on any phase, or a 3x3 / stride-1
+    nn.Conv2d whose dilation == padding == (x.phase, x.phase), which runs as the padding-1 convolution on x.data (descriptor
+    pad = 1; packs and every backward route are the plain ones).  The output inherits the phase; a shortcut must be in the same
+    phase layout.  A dilation that is not the tensor's phase is refused as it always was; every other layer refuses a phased
+    tensor through await_ready."""
     if pool and (bn is None or not relu or shortcut is not None or x.data.dim() != 4):
         raise ValueError('conv_bn_act(pool=True): BatchNorm + ReLU on a 4-D input, no shortcut')
     if (isinstance(conv, nn.Conv2d) and _is_grouped(conv) and bn is not None and shortcut is None and not pool
@@ -709,17 +736,31 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
         return gconv_bn_act(region, x, conv, bn, relu=relu, act=act)       # (anything else grouped: _check_conv refuses below)
     act = _check_act(relu, act, bn, shortcut, pool, defer_apply)
     relu = act == RELU
-    await_ready(x, shortcut)
+    phase = x.phase
+    if phase != 1:
+        # a dilated stage in phase layout (phase_split): pointwise layers as they are, the dilated 3x3 as the padding-1 one
+        # on the phase images; everything else is refused by await_ready (a dilation that is not the phase: by _check_conv)
+        phased = _phased_conv_ok(conv, phase) and not pool and not defer_apply and x.data.dim() == 4
+        if not phased and isinstance(conv, nn.Conv2d) and tuple(conv.dilation) != (1, 1):
+            _check_conv(conv)
+        await_ready(x, shortcut, phase_ok=phased)
+        if shortcut is not None and shortcut.phase_steps != x.phase_steps:
+            raise ValueError(f'conv_bn_act: the shortcut is in phase layout {shortcut.phase_steps or (1,)}, the unit in '
+                             f'{x.phase_steps}: bring it there with phase_split / to_phase')
+    else:
+        await_ready(x, shortcut)
     lib, st = _C.lib(), stream_ptr()
     if isinstance(conv, nn.Linear):
         r = s = 1
         stride, pad = 1, 0
         k_real = conv.out_features
     else:
-        _check_conv(conv)
+        _check_conv(conv, phase)
         r, s = conv.kernel_size
         stride, pad = conv.stride[0], conv.padding[0]
         k_real = conv.out_channels
+        if phase != 1 and r == 3:
+            pad = 1     # dilation == padding == phase on the merged map is padding 1 on every phase image
     if (SUBSAMPLE_S2 and r == 1 and s == 1 and stride == 2 and pad == 0 and x.data.dim() == 4 and not pool
             and x.rows() >= SUBSAMPLE_MIN_ROWS):
         # conv1x1/stride2(x) == conv1x1(x[:, ::2, ::2]): one strided copy, then a pointwise layer in all three passes
@@ -737,7 +778,7 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
             and batch_stats(bn) and conv.weight.permute(0, 2, 3, 1).is_contiguous()):
         # the residual unit of a bottleneck (conv3 + bn3 + shortcut + ReLU) and its stride-1 projection shortcut (conv + bn):
         # normalise (add, activate) in the GEMM epilogue — the wide pre-BatchNorm tensor is never stored
-        return _unit3_forward(region, x, conv, bn, shortcut, kp, relu)
+        return _inherit_phase(_unit3_forward(region, x, conv, bn, shortcut, kp, relu), x)
     d = _conv_desc(x4, kp, r, s, stride, pad)
     training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or
                                      (bn is not None and bn.weight.requires_grad))
@@ -793,7 +834,7 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
         out_data = out_data.view(d.n, kp)
 
     req = bool(training or (shortcut is not None and shortcut.requires_grad and region.grad_mode))
-    out = TTensor(out_data, k_real, requires_grad=req)
+    out = _inherit_phase(TTensor(out_data, k_real, requires_grad=req), x)
     if bn is not None and deferred:
         out.affine = (scale, shift)
     if bn is not None and cs_part is not None:
@@ -841,6 +882,7 @@ class _MaxPoolNode(Node):
 
 
 def max_pool_3x3_s2(region: Region, x: TTensor) -> TTensor:
+    refuse_phased(x, 'max_pool_3x3_s2')
     n, h, w, c = x.shape
     p, q = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
     y = torch.empty((n, p, q, c), dtype=BF16, device=x.data.device)
@@ -895,6 +937,7 @@ SUBSAMPLE_MIN_ROWS = int(os.environ.get('TOK_SUBSAMPLE_MIN_ROWS', '40000'))
 
 
 def subsample2(region: Region, x: TTensor) -> TTensor:
+    refuse_phased(x, 'subsample2')
     n, h, w, c = x.shape
     y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=BF16, device=x.data.device)
     _C.check(_C.lib().tok_subsample2_fwd(ptr(x.data), n, h, w, c, ptr(y), stream_ptr()), 'tok_subsample2_fwd')
@@ -907,6 +950,98 @@ def subsample2(region: Region, x: TTensor) -> TTensor:
         x.uses += 1
         region.add(node)
     return out
+
+
+# ---- phase layout (space-to-batch): how a dilated stage runs on the plain kernels -----------------------------------------
+# A 3x3 / stride-1 convolution with dilation d and padding d is the plain 3x3 / padding-1 convolution on each of the d x d
+# phase images x[:, a::d, b::d, :] (zero padding by d in the image is zero padding by 1 in every phase image), and 1x1
+# convolutions, BatchNorm, ReLU and the residual add do not care which pixel is where.  phase_split turns an (N, H, W, C)
+# tensor into the N * d * d phase images (N * d * d, H / d, W / d, C), image (i, a, b) at index (i * d + a) * d + b, and a whole
+# dilated stage runs on them; phase_merge is the inverse (csrc/phase.hip).
+# Nested splits: a split sees the tensor it is given as a batch of images, so splitting a phase-2 tensor by 2 gives phase 4 with
+# image index ((i * 2 + a1) * 2 + b1) * 4 + a2 * 2 + b2 for the pixels Y = 4y + 2 * a2 + a1, X = 4x + 2 * b2 + b1: the INNER
+# split holds the higher bit.  Each of those images is a phase image of dilation 4, but their order is not that of one split
+# by 4 — TTensor.phase_steps, (2, 2) against (4,), keeps the two apart, and a merge undoes the LAST split only.
+
+class _PhaseNode(Node):
+    """A split or a merge; its backward is the other kernel on the output gradient, into grad_target(x) (= or +=)."""
+    needs_backward = True
+
+    def backward(self):
+        g = self.out.grad
+        if g is None or not self.x.requires_grad:
+            return
+        self.out.grad = None
+        tgt, acc = grad_target(self.x)
+        n, h, w, c, d = self.geo
+        fn, name = (_C.lib().tok_phase_merge, 'tok_phase_merge') if self.split else (_C.lib().tok_phase_split, 'tok_phase_split')
+        _C.check(fn(ptr(g), n, h, w, c, c, d, ptr(tgt), acc, stream_ptr()), name)
+
+    def release(self):
+        self.x = self.out = None
+
+
+def _phase_move(region: Region, x: TTensor, d: int, split: bool) -> TTensor:
+    if d not in (2, 4):
+        raise NotImplementedError(f'phase_{"split" if split else "merge"}: d = {d}, 2 or 4 are served')
+    await_ready(x, phase_ok=True)
+    if x.data.dim() != 4 or x.affine is not None:
+        raise NotImplementedError('phase_split / phase_merge: a 4-D tensor without a deferred BatchNorm apply')
+    nb, hb, wb, c = x.shape
+    if split:
+        n, h, w = nb, hb, wb                         # the sizes of the MERGED tensor of this call
+        if h % d or w % d:
+            raise NotImplementedError(f'phase_split: a map of h = {h}, w = {w} is not divisible by d = {d} (a dilated stage '
+                                      f'needs an input whose map at that stage is a multiple of its dilation)')
+        shape, steps = (n * d * d, h // d, w // d, c), x.phase_steps + (d,)
+    else:
+        if not x.phase_steps or x.phase_steps[-1] != d:
+            raise ValueError(f'phase_merge by {d}: the last split of this tensor is {x.phase_steps[-1:] or None} '
+                             f'(phase_steps {x.phase_steps})')
+        n, h, w = nb // (d * d), hb * d, wb * d
+        shape, steps = (n, h, w, c), x.phase_steps[:-1]
+    y = torch.empty(shape, dtype=BF16, device=x.data.device)
+    fn, name = (_C.lib().tok_phase_split, 'tok_phase_split') if split else (_C.lib().tok_phase_merge, 'tok_phase_merge')
+    _C.check(fn(ptr(x.data), n, h, w, c, c, d, ptr(y), 0, stream_ptr()), name)
+    req = region.grad_mode and x.requires_grad
+    out = TTensor(y, x.c, requires_grad=req)
+    out.phase_steps = steps
+    for f in steps:
+        out.phase *= f
+    if req:
+        node = _PhaseNode()
+        node.x, node.out, node.split, node.geo = x, out, split, (n, h, w, c, d)
+        out.node = node
+        x.uses += 1
+        region.add(node)
+    return out
+
+
+def phase_split(region: Region, x: TTensor, d: int) -> TTensor:
+    """x -> its d x d phase images (see above); a phase-2 tensor split by 2 gives phase 4.  h or w not divisible by d:
+    NotImplementedError before anything is launched."""
+    return _phase_move(region, x, d, True)
+
+
+def phase_merge(region: Region, x: TTensor, d: int) -> TTensor:
+    """Undo the last split of x, which must have been by d: phase 4 = (2, 2) -> phase 2 -> phase 1."""
+    return _phase_move(region, x, d, False)
+
+
+def to_phase(region: Region, x: TTensor, d: int) -> TTensor:
+    """x in phase d: x itself when it is there already, split upward otherwise (never merged implicitly)."""
+    if x.phase == d:
+        return x
+    if d % x.phase or d // x.phase not in (2, 4):
+        raise ValueError(f'to_phase: phase {x.phase} -> {d} is no split by 2 or 4 (merge explicitly with phase_merge)')
+    return phase_split(region, x, d // x.phase)
+
+
+def from_phase(region: Region, x: TTensor) -> TTensor:
+    """x in plain layout: every split undone, last one first (x itself when it is plain)."""
+    while x.phase != 1:
+        x = phase_merge(region, x, x.phase_steps[-1])
+    return x
 
 
 class _AvgPool2Node(Node):
@@ -961,6 +1096,7 @@ class _GapNode(Node):
 
 
 def global_avg_pool(region: Region, x: TTensor) -> TTensor:
+    refuse_phased(x, 'global_avg_pool')
     n, h, w, c = x.shape
     y = torch.empty((n, c), dtype=BF16, device=x.data.device)
     _C.check(_C.lib().tok_gap_fwd(ptr(x.data), ptr(y), n, h * w, c, stream_ptr()), 'tok_gap_fwd')
@@ -1003,6 +1139,7 @@ def global_pool(region: Region, x: TTensor, pool_type: str) -> TTensor:
     if pool_type == 'avg':
         return global_avg_pool(region, x)
     mode = POOL_MODES[pool_type]
+    refuse_phased(x, 'global_pool')
     n, h, w, c = x.shape
     if mode == 3 and x.c != c:
         raise NotImplementedError("torchok_amd Pooling 'catavgmax': channel counts that are multiples of 8")
@@ -1087,9 +1224,11 @@ class _SameWidthConvBnActNode(_ConvBnActNode):
             self.launch_dgrad(lib, conv, geo, dy, tgt, acc, st)
 
 
-def _same_width_conv_bn_act(node_cls, region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, act) -> TTensor:
-    """The forward of a _SameWidthConvBnActNode family (the caller has checked the layer and resolved `act`)."""
-    await_ready(x)
+def _same_width_conv_bn_act(node_cls, region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, act,
+                            phase_ok: bool = False) -> TTensor:
+    """The forward of a _SameWidthConvBnActNode family (the caller has checked the layer and resolved `act`; a family that
+    takes an input in phase layout has checked that too: the unit then runs on the phase images)."""
+    await_ready(x, phase_ok=phase_ok)
     if bn.num_features != conv.out_channels:
         raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {conv.out_channels}')
     lib, st = _C.lib(), stream_ptr()
@@ -1109,7 +1248,7 @@ def _same_width_conv_bn_act(node_cls, region: Region, x: TTensor, conv: nn.Conv2
     training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad
                                      or bn.bias.requires_grad)
     out_data, mask = bn_apply(lib, st, y, scale, shift, act, None, act == RELU and training, m, c)
-    out = TTensor(out_data, c, requires_grad=bool(training))
+    out = _inherit_phase(TTensor(out_data, c, requires_grad=bool(training)), x)
     if training:
         node = node_cls()
         node.x, node.out, node.y, node.mask = x, out, y, mask
@@ -1172,7 +1311,8 @@ def _check_gconv(conv: nn.Conv2d, x: TTensor):
     g = conv.groups
     if (g < 2 or conv.in_channels != conv.out_channels or conv.in_channels % g != 0 or conv.in_channels // g not in GCONV_WIDTHS
             or conv.bias is not None or conv.kernel_size != (3, 3) or tuple(conv.stride) not in ((1, 1), (2, 2))
-            or tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != 'zeros'):
+            or conv.padding_mode != 'zeros'
+            or (tuple(conv.padding) != (1, 1) or tuple(conv.dilation) != (1, 1) if x.phase == 1 else not _phased_conv_ok(conv, x.phase))):
         raise NotImplementedError(f'torchok_amd grouped conv: 3x3, groups >= 2, as many output as input channels, group width '
                                   f'in {GCONV_WIDTHS}, no bias, stride 1 or 2, padding 1, no dilation')
     if x.data.dim() != 4 or x.c != x.cp or x.c != conv.in_channels:
@@ -1226,11 +1366,13 @@ def gconv_bn_act(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm2d
                  act: Optional[str] = None) -> TTensor:
     """out = act(bn(conv(x))) for a grouped 3x3 `conv` ([timm] Bottleneck.conv2 + bn2 + act2 of the ResNeXts).  act=None: `relu`
     decides; act='hard_swish' / 'relu6': as in conv_bn_act.  The kernels read the fp32 master itself (rounded to bf16 as a wave builds its
-    fragments): there is no packed copy that an optimizer step could leave stale.  The BatchNorm stage is dwconv_bn_act's.  The
+    fragments): there is no packed copy that an optimizer step could leave stale.  The BatchNorm stage is dwconv_bn_act's.  An
+    input in phase layout (phase_split) is served when the layer's stride is 1 and its dilation and padding equal the phase: the
+    kernels then run on the phase images as the padding-1 convolution they always are.  The
     output carries no `colsum_part`: a fused residual unit that consumes it sums the columns itself (_unit3_forward)."""
     act = _check_act(relu, act, bn)
     _check_gconv(conv, x)
-    return _same_width_conv_bn_act(_GConvBnActNode, region, x, conv, bn, act)
+    return _same_width_conv_bn_act(_GConvBnActNode, region, x, conv, bn, act, phase_ok=True)
 
 
 # ---- squeeze-excite (MnasNet-A1) -----------------------------------------------------------------------------------------

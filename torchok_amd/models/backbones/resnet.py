@@ -11,6 +11,8 @@ Execution differs completely: each ``conv -> bn -> (+shortcut) -> relu`` group i
 pass), activations stay NHWC bf16 in HBM between units, and the whole backbone is a single
 autograd node.  The nn.Conv2d / nn.BatchNorm2d children are parameter containers only.
 
+output_stride 8 / 16 (every entry point with convolutional shortcuts): the dilated stages run in phase layout, EF.phase_split, on
+the same units as the plain network (csrc/phase.hip is the only device code of their own).
 Only the plain (v1.5) family is built: no SE / anti-aliasing / drop-block
 (plus the other plain-architecture entrypoints at the end of the file, the d / t stems, the ResNeXts of group width
 4 ... 64 on the grouped 3x3 unit and the ECA-ResNets on the channel-attention residual unit, EF.eca_residual; the s-stem, SE,
@@ -61,14 +63,16 @@ class BasicBlock(nn.Module):
                  attn_layer=None, aa_layer=None, drop_block=None, drop_path=None):
         super().__init__()
         assert cardinality == 1 and base_width == 64, 'BasicBlock only supports cardinality=1, base_width=64'
-        _unsupported(dilation=dilation != 1, attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer,
-                     drop_block=drop_block, drop_path=drop_path)
+        first_dilation = first_dilation or dilation
+        _unsupported(eca_dilated=attn_layer == 'eca' and (dilation != 1 or first_dilation != 1),
+                     attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer, drop_block=drop_block, drop_path=drop_path)
         first_planes = planes // reduce_first
         outplanes = planes * self.expansion
-        self.conv1 = nn.Conv2d(inplanes, first_planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.conv1 = nn.Conv2d(inplanes, first_planes, kernel_size=3, stride=stride, padding=first_dilation,
+                               dilation=first_dilation, bias=False)
         self.bn1 = norm_layer(first_planes)
         self.act1 = act_layer(inplace=True)
-        self.conv2 = nn.Conv2d(first_planes, outplanes, kernel_size=3, padding=1, bias=False)
+        self.conv2 = nn.Conv2d(first_planes, outplanes, kernel_size=3, padding=dilation, dilation=dilation, bias=False)
         self.bn2 = norm_layer(outplanes)
         self.se = _attn(attn_layer, outplanes)
         self.act2 = act_layer(inplace=True)
@@ -80,8 +84,14 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         r = engine.current_region()
-        shortcut = self._shortcut(r, x)
-        y = EF.conv_bn_act(r, x, self.conv1, self.bn1, relu=True)
+        # a dilated stage runs in phase layout (EF.phase_split): every 3x3 takes its operand in the phase that equals its
+        # dilation.  The stage's first block has conv1 at the previous dilation and conv2 at the stage's: the split sits
+        # between them, and the block input is split for the 1x1 projection (its narrower side), so that the shortcut arrives
+        # in the phase of the unit that adds it.  Without dilation every to_phase returns its argument.
+        d1, d2 = self.conv1.dilation[0], self.conv2.dilation[0]
+        x = EF.to_phase(r, x, d1)
+        shortcut = self._shortcut(r, EF.to_phase(r, x, d2))
+        y = EF.to_phase(r, EF.conv_bn_act(r, x, self.conv1, self.bn1, relu=True), d2)
         if self.se is not None:
             return EF.eca_residual(r, EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=False), self.se, shortcut)
         return EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True, shortcut=shortcut)
@@ -97,8 +107,9 @@ class Bottleneck(nn.Module):
                  reduce_first=1, dilation=1, first_dilation=None, act_layer=nn.ReLU, norm_layer=nn.BatchNorm2d,
                  attn_layer=None, aa_layer=None, drop_block=None, drop_path=None):
         super().__init__()
-        _unsupported(dilation=dilation != 1, attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer,
-                     drop_block=drop_block, drop_path=drop_path)
+        first_dilation = first_dilation or dilation
+        _unsupported(eca_dilated=attn_layer == 'eca' and (dilation != 1 or first_dilation != 1),
+                     attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer, drop_block=drop_block, drop_path=drop_path)
         width = int(math.floor(planes * (base_width / 64)) * cardinality)
         first_planes = width // reduce_first
         outplanes = planes * self.expansion
@@ -106,7 +117,8 @@ class Bottleneck(nn.Module):
         self.bn1 = norm_layer(first_planes)
         self.act1 = act_layer(inplace=True)
         # cardinality > 1 (ResNeXt): a grouped 3x3, which conv_bn_act hands to the grouped unit (EF.gconv_bn_act)
-        self.conv2 = nn.Conv2d(first_planes, width, kernel_size=3, stride=stride, padding=1, groups=cardinality, bias=False)
+        self.conv2 = nn.Conv2d(first_planes, width, kernel_size=3, stride=stride, padding=first_dilation, dilation=first_dilation,
+                               groups=cardinality, bias=False)
         self.bn2 = norm_layer(width)
         self.act2 = act_layer(inplace=True)
         self.conv3 = nn.Conv2d(width, outplanes, kernel_size=1, bias=False)
@@ -121,6 +133,9 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         r = engine.current_region()
+        # a dilated stage runs in phase layout (EF.phase_split), the whole block in the phase that equals conv2's dilation: the
+        # stage's first block still in the previous phase, the split in front of the second.  Without dilation: x itself.
+        x = EF.to_phase(r, x, self.conv2.dilation[0])
         y = EF.conv_bn_act(r, x, self.conv1, self.bn1, relu=True)
         y = EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True)
         # the projection is recorded LAST before the unit that adds it: in backward its (strided) data gradient then opens the
@@ -180,23 +195,37 @@ def downsample_avg(in_channels, out_channels, kernel_size, stride=1, dilation=1,
 
 def make_blocks(block_fn, channels, block_repeats, inplanes, reduce_first=1, output_stride=32,
                 down_kernel_size=1, avg_down=False, drop_block_rate=0., drop_path_rate=0., **kwargs):
-    _unsupported(drop_block_rate=drop_block_rate, drop_path_rate=drop_path_rate, output_stride=output_stride != 32)
+    # dilated stages (output_stride 8 / 16) run in phase layout on the plain kernels (EF.phase_split).  Not with avg_down: timm's
+    # AvgPool2dSame of a dilated 'd' / 't' shortcut is not built; not with ECA: its per-image mean is not phase-agnostic
+    _unsupported(drop_block_rate=drop_block_rate, drop_path_rate=drop_path_rate)
+    if output_stride != 32 and (avg_down or kwargs.get('attn_layer') == 'eca'):
+        raise NotImplementedError(f'torchok_amd ResNet: output_stride={output_stride} with '
+                                  f'{"avg_down" if avg_down else "attn_layer=eca"} is not built (dilated stages: convolutional '
+                                  f'shortcuts, no channel attention)')
     no_downsample_stages = kwargs.pop('no_downsample_stages', [0])
     stages, feature_info = [], []
     net_stride = 4
+    dilation = prev_dilation = 1
     for stage_idx, (planes, num_blocks) in enumerate(zip(channels, block_repeats)):
         stage_name = f'layer{stage_idx + 1}'
         stride = 1 if stage_idx in no_downsample_stages else 2
-        net_stride *= stride
+        if net_stride >= output_stride:          # resnet.py:376-380: the stage dilates instead of striding
+            dilation *= stride
+            stride = 1
+        else:
+            net_stride *= stride
         downsample = None
         if stride != 1 or inplanes != planes * block_fn.expansion:
             make = downsample_avg if avg_down else downsample_conv
             downsample = make(inplanes, planes * block_fn.expansion, kernel_size=down_kernel_size,
-                              stride=stride, norm_layer=kwargs.get('norm_layer'))
+                              stride=stride, dilation=dilation, first_dilation=prev_dilation,
+                              norm_layer=kwargs.get('norm_layer'))
         blocks = []
         for block_idx in range(num_blocks):
             blocks.append(block_fn(inplanes, planes, stride if block_idx == 0 else 1,
-                                   downsample if block_idx == 0 else None, reduce_first=reduce_first, **kwargs))
+                                   downsample if block_idx == 0 else None, reduce_first=reduce_first, dilation=dilation,
+                                   first_dilation=prev_dilation, **kwargs))
+            prev_dilation = dilation
             inplanes = planes * block_fn.expansion
         stages.append((stage_name, nn.Sequential(*blocks)))
         feature_info.append(dict(num_chs=inplanes, reduction=net_stride, module=stage_name))
@@ -277,7 +306,9 @@ class ResNet(BaseBackbone):
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             t = layer(t)
             feats.append(t)
-        return feats
+        # a dilated stage leaves its map in phase layout and the next stage continues from that tensor; what is RETURNED is
+        # merged: every feature (it then has two consumers), or the last map alone
+        return [EF.from_phase(r, f) for f in feats] if all_features else feats[:-1] + [EF.from_phase(r, feats[-1])]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         with engine.region() as r:
