@@ -304,6 +304,26 @@ int tok_bn_relu6_bwd_reduce(const void* dout, const void* y, const float* scale,
                             const float* rstd, int64_t m, int c, float* partial, void* stream);
 int tok_bn_relu6_bwd_apply(const void* dout, const void* y, const float* scale, const float* shift, const float* coef,
                            void* dy, int64_t m, int c, void* stream);
+/* Stochastic depth on a residual unit's BatchNorm ([timm] DropPath in front of the residual add; csrc/bn_droppath.hip):
+ *   out = relu(s[i] * (y*scale + shift) + shortcut),  s[i] = row_scale[row / rows_per_sample] (fp32 [m / rows_per_sample]: 0 for
+ *   a dropped sample, 1 / keep for a kept one; rows are 64-bit).  z = fmaf(y, scale, shift) in fp32, one rounding to bf16 per
+ *   output element.  Operand layouts, mask bits (= stored out > 0; nullable in the forward), launch geometry and fold order are
+ *   those of tok_bn_act_fwd / tok_bn_bwd_reduce / tok_bn_bwd_apply: with s == 1 the results are theirs bit for bit.
+ * Backward: dt = dout * mask, dshortcut (=|+=) dt (may alias dout), dz = s[i] * dt;
+ *   tok_bn_droppath_bwd_reduce: partial[2][tok_bn_bwd_rows(m, c)][c] = sum(dz), sum(dz * xhat) -> tok_bn_bwd_finalize, dzy_form = 0;
+ *   tok_bn_droppath_bwd_apply: dy = a1*dz + a2*y + a3 on EVERY row: a dropped sample still receives a2*y + a3.  It carries an
+ *   armed tok_next_launch_event as tok_bn_bwd_apply does.
+ * Refused (TOK_ERR_INVALID, nothing launched or written): c % 8 != 0, m <= 0, rows_per_sample <= 0, m % rows_per_sample != 0, a
+ * NULL operand (row_scale, shortcut and, in the two backward calls, mask included; only the forward's mask and dshortcut may
+ * be NULL).                                                                                                                 */
+int tok_bn_droppath_fwd(const void* y, const float* scale, const float* shift, const void* shortcut, const float* row_scale,
+                        int64_t rows_per_sample, void* out, uint8_t* mask, int64_t m, int c, void* stream);
+int tok_bn_droppath_bwd_reduce(const void* dout, const void* y, const uint8_t* mask, const float* row_scale,
+                               int64_t rows_per_sample, const float* mean, const float* rstd, int64_t m, int c, float* partial,
+                               void* stream);
+int tok_bn_droppath_bwd_apply(const void* dout, const void* y, const uint8_t* mask, const float* row_scale,
+                              int64_t rows_per_sample, const float* coef, void* dy, void* dshortcut, int dshortcut_accumulate,
+                              int64_t m, int c, void* stream);
 
 
 /* ---- pooling ----------------------------------------------------------------------------

@@ -79,6 +79,9 @@ PROTOTYPES = {
     'tok_bn_relu6_fwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, _P]),
     'tok_bn_relu6_bwd_reduce': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P]),
     'tok_bn_relu6_bwd_apply': (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
+    'tok_bn_droppath_fwd': (c_int, [_P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int, _P]),
+    'tok_bn_droppath_bwd_reduce': (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int, _P, _P]),
+    'tok_bn_droppath_bwd_apply': (c_int, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int, c_int64, c_int, _P]),
     'tok_maxpool3x3s2_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     'tok_maxpool3x3s2_bwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     'tok_avgpool2x2_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),

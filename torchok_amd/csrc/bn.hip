@@ -608,13 +608,14 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_pooled_kernel(const bf
 
 }  // namespace
 
-static int stream_cap() {   // blocks of the elementwise kernels (TOK_BN_BLOCKS overrides).  1024 = 4 per CU = half the wave slots: the
-                            // weight-gradient kernels of the side stream run beside them (2048 measured 1.7 % slower end to end)
-  static const int v = tok_env_int("TOK_BN_BLOCKS", 1024);
-  return v;
+#define kStreamCap row_stream_cap()            // blocks of the elementwise kernels (row_stream.h)
+static const int kReduceCap = kRowReduceCap;   // partial rows of the reducing kernels
+
+hipEvent_t tok_take_launch_event() {
+  hipEvent_t ev = t_done_event;
+  t_done_event = nullptr;
+  return ev;
 }
-#define kStreamCap stream_cap()
-static const int kReduceCap = 1024;   // partial rows of the reducing kernels
 
 extern "C" int tok_bn_finalize(const float* stats, int rows, int64_t count, int c, int c_real, const float* gamma,
                                const float* beta, float* running_mean, float* running_var,

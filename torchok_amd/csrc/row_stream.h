@@ -24,6 +24,16 @@ inline int row_blocks(int64_t m, const Geo& g, int cap) {
   if (b < 1) b = 1;
   return (int)b;
 }
+// Block caps of the BatchNorm passes (bn.hip, bn_droppath.hip).  Map passes: TOK_BN_BLOCKS overrides; 1024 = 4 per CU = half the
+// wave slots: the weight-gradient kernels of the side stream run beside them (2048 measured 1.7 % slower end to end)
+inline int row_stream_cap() {
+  static const int v = tok_env_int("TOK_BN_BLOCKS", 1024);
+  return v;
+}
+constexpr int kRowReduceCap = 1024;   // partial rows of the reducing kernels (tok_bn_bwd_rows)
+// The completion event armed by tok_next_launch_event for the calling thread's next apply launch, disarmed by the read (bn.hip)
+hipEvent_t tok_take_launch_event();
+
 // the lane's 8 per-channel fp32 coefficients
 __device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
   const float4 a = *reinterpret_cast<const float4*>(p);

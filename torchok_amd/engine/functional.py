@@ -305,15 +305,21 @@ def bn_coeffs(lib, st, bn, stats, rows, m, kp, dev):
     return scale, shift, mean, rstd
 
 
-def bn_apply(lib, st, y, scale, shift, act, shortcut, want_mask, m, kp):
+def bn_apply(lib, st, y, scale, shift, act, shortcut, want_mask, m, kp, row_scale=None):
     """The plain apply pass out = act(y * scale + shift (+ shortcut)) -> (out_data, mask).  `want_mask` is the caller's
-    rule for keeping the ReLU bits; hard-swish and ReLU6 keep none."""
+    rule for keeping the ReLU bits; hard-swish and ReLU6 keep none.
+    row_scale (stochastic depth, a ReLU unit with a shortcut): out = relu(s[sample] * (y * scale + shift) + shortcut), the sample
+    of a row being row // (m // len(row_scale))."""
     out_data = torch.empty_like(y)
     if act in MASKLESS:
         fwd, name = _maskless(lib, act, 'fwd')
         _C.check(fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, kp, st), name)
         return out_data, None
     mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=y.device) if want_mask else None
+    if row_scale is not None:
+        _C.check(lib.tok_bn_droppath_fwd(ptr(y), ptr(scale), ptr(shift), ptr(shortcut.data), ptr(row_scale),
+                                         m // row_scale.numel(), ptr(out_data), ptr(mask), m, kp, st), 'tok_bn_droppath_fwd')
+        return out_data, mask
     _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), ptr(shortcut.data) if shortcut is not None else None,
                                 int(act == RELU), ptr(out_data), ptr(mask), m, kp, st), 'tok_bn_act_fwd')
     return out_data, mask
@@ -331,16 +337,18 @@ class _ConvBnActNode(Node):
         self.fused_partial = None   # (partial, rows) when a consumer's dgrad epilogue did our BN-bwd reduce
         self.pool = None            # tap indices of the fused 3x3/s2 max-pool: `out` is the POOLED map, z was never stored
         self.ypool = None           # raw conv output at the winning taps (pooled-domain BatchNorm-backward sums)
+        self.row_scale = None       # per-sample fp32 factor of the BatchNorm output (stochastic depth): the tok_bn_droppath_* trio
 
     def release(self):
         self.x = self.out = self.shortcut = None
         self.y = self.pk = self.mask = self.fused_partial = self.pool = self.ypool = None
-        self.mean = self.rstd = self.scale = self.shift = None
+        self.mean = self.rstd = self.scale = self.shift = self.row_scale = None
 
     def wants_fused_bwd_stats(self) -> bool:
         """Can the kernel that completes d(out) also reduce sum(dz), sum(dz*y) for this unit?"""
-        # (the dgrad epilogues know the ReLU mask only: a hard-swish or ReLU6 producer takes the stand-alone reduce)
-        return (self.bn is not None and self.batch_stats and self.pool is None
+        # (the dgrad epilogues know the ReLU mask only: a hard-swish or ReLU6 producer takes the stand-alone reduce, and so does
+        # a unit with a row scale, whose dz is not mask * d(out))
+        return (self.bn is not None and self.batch_stats and self.pool is None and self.row_scale is None
                 and (self.act is None or (self.act == RELU and self.mask is not None)))
 
     def _apply_bwd(self, lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp):
@@ -348,6 +356,9 @@ class _ConvBnActNode(Node):
         if self.act in MASKLESS:
             bwd_apply, name = _maskless(lib, self.act, 'bwd_apply')
             _C.check(bwd_apply(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(coef), ptr(dy), m, kp, st), name)
+        elif self.row_scale is not None:
+            _C.check(lib.tok_bn_droppath_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.row_scale), m // self.row_scale.numel(),
+                                                   ptr(coef), ptr(dy), ds_ptr, ds_acc, m, kp, st), 'tok_bn_droppath_bwd_apply')
         else:
             _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift), ptr(coef),
                                           int(self.relu), ptr(dy), ds_ptr, ds_acc, m, kp, st), 'tok_bn_bwd_apply')
@@ -380,6 +391,11 @@ class _ConvBnActNode(Node):
                 bwd_reduce, name = _maskless(lib, self.act, 'bwd_reduce')
                 _C.check(bwd_reduce(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.rstd), m, kp,
                                     ptr(partial), st), name)
+            elif self.row_scale is not None:
+                partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
+                _C.check(lib.tok_bn_droppath_bwd_reduce(ptr(g), ptr(self.y), ptr(mask), ptr(self.row_scale),
+                                                        m // self.row_scale.numel(), ptr(self.mean), ptr(self.rstd), m, kp,
+                                                        ptr(partial), st), 'tok_bn_droppath_bwd_reduce')
             else:
                 partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
                 _C.check(lib.tok_bn_bwd_reduce(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift),
@@ -712,7 +728,7 @@ STEM_POOLED_STATS = os.environ.get('TOK_STEM_POOLED_STATS', '1') != '0'   # Batc
 
 def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.BatchNorm2d] = None,
                 relu: bool = False, shortcut: Optional[TTensor] = None, pool: bool = False, defer_apply: bool = False,
-                act: Optional[str] = None) -> TTensor:
+                act: Optional[str] = None, row_scale: Optional[torch.Tensor] = None) -> TTensor:
     """out = act(bn(conv(x)) (+ shortcut)).  `conv` is an nn.Conv2d or nn.Linear used purely as
     the parameter container (state_dict names stay those of the reference).
     act=None: ReLU or no activation, as `relu` says.  act='hard_swish' / 'relu6' (BatchNorm, no shortcut / pool / defer_apply):
@@ -728,7 +744,22 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     nn.Conv2d whose dilation == padding == (x.phase, x.phase), which runs as the padding-1 convolution on x.data (descriptor
     pad = 1; packs and every backward route are the plain ones).  The output inherits the phase; a shortcut must be in the same
     phase layout.  A dilation that is not the tensor's phase is refused as it always was; every other layer refuses a phased
-    tensor through await_ready."""
+    tensor through await_ready.
+    row_scale (stochastic depth; BatchNorm + ReLU + shortcut on a 4-D input, no pool / defer_apply / act=): an fp32 vector with one
+    factor per SAMPLE, 0 for a dropped sample and 1 / keep for a kept one: out = relu(row_scale[i] * bn(conv(x)) + shortcut) on the
+    tok_bn_droppath_* trio (csrc/bn_droppath.hip).  BatchNorm sees the un-dropped convolution output, with batch or with
+    running statistics.  The unit never becomes the fused unit 3 and never hands its BatchNorm-backward sums to a consumer's
+    data gradient.  In phase layout the phase images of a sample are contiguous, so the rows of a sample are h * w of the merged
+    map.  row_scale=None: every launch is the one it always was."""
+    if row_scale is not None:
+        if pool or defer_apply or act is not None:
+            raise NotImplementedError('conv_bn_act(row_scale=...): no pool, defer_apply or act= (a ReLU residual unit only)')
+        if bn is None or not relu or shortcut is None or x.data.dim() != 4:
+            raise ValueError('conv_bn_act(row_scale=...): BatchNorm + ReLU + shortcut on a 4-D input')
+        samples = x.shape[0] // (x.phase * x.phase)
+        if row_scale.dtype != F32 or row_scale.dim() != 1 or row_scale.numel() != samples or not row_scale.is_contiguous():
+            raise ValueError(f'conv_bn_act(row_scale=...): a contiguous fp32 vector of {samples} factors (one per sample), got '
+                             f'{row_scale.dtype} {tuple(row_scale.shape)}')
     if pool and (bn is None or not relu or shortcut is not None or x.data.dim() != 4):
         raise ValueError('conv_bn_act(pool=True): BatchNorm + ReLU on a 4-D input, no shortcut')
     if (isinstance(conv, nn.Conv2d) and _is_grouped(conv) and bn is not None and shortcut is None and not pool
@@ -771,7 +802,7 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
     if bn is not None and bn.num_features != k_real:
         raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {k_real}')
     if (FUSE_UNIT3 and bn is not None and act not in MASKLESS and (relu == (shortcut is not None)) and not pool
-            and isinstance(conv, nn.Conv2d)
+            and row_scale is None and isinstance(conv, nn.Conv2d)
             and r == 1 and s == 1 and stride == 1 and pad == 0 and conv.bias is None and x.data.dim() == 4
             and x.c == x.cp and kp == k_real and x.cp <= 1024 and (shortcut is None or shortcut.cp == kp)
             and x.rows() >= UNIT3_MIN_ROWS and kp >= 2 * x.cp
@@ -822,7 +853,8 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
         else:
             # ReLU bits for the backward pass whenever gradients are on, running statistics included: the apply kernel's
             # mask-less fallback recomputes the pattern from y alone and would leave out a shortcut added before the activation
-            out_data, mask = bn_apply(lib, st, y, scale, shift, act, shortcut, relu and region.grad_mode, m, kp)
+            out_data, mask = bn_apply(lib, st, y, scale, shift, act, shortcut, relu and region.grad_mode, m, kp, row_scale)
+            node.row_scale = row_scale
         node.mask = mask
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
     else:

@@ -13,6 +13,13 @@ autograd node.  The nn.Conv2d / nn.BatchNorm2d children are parameter containers
 
 output_stride 8 / 16 (every entry point with convolutional shortcuts): the dilated stages run in phase layout, EF.phase_split, on
 the same units as the plain network (csrc/phase.hip is the only device code of their own).
+drop_path_rate (stochastic depth, resnet.py:369-400): block i of the network's N gets DropPath(drop_path_rate * i / (N - 1)), none
+where that is 0; the per-sample keep / scale vector (swin.DropPath, all of a step's vectors drawn at once in ResNet._run) is the
+`row_scale` of the block's last unit, out = relu(s[sample] * bn(conv(.)) + shortcut) on csrc/bn_droppath.hip.  BatchNorm sees the
+un-dropped convolution output, as in [timm 0.6.13], and a dropped sample still receives the batch-statistics terms of the
+gradient.  A block with a rate takes the plain conv + BatchNorm apply for that unit, never the fused residual unit.  In eval mode or
+at rate 0 the network is launch for launch the one without the argument.  drop_block_rate stays refused (timm's DropBlock cannot
+be checked offline), and so does drop_path_rate with attn_layer='eca' (the channel-attention residual kernel has no row scale).
 Only the plain (v1.5) family is built: no SE / anti-aliasing / drop-block
 (plus the other plain-architecture entrypoints at the end of the file, the d / t stems, the ResNeXts of group width
 4 ... 64 on the grouped 3x3 unit and the ECA-ResNets on the channel-attention residual unit, EF.eca_residual; the s-stem, SE,
@@ -28,6 +35,7 @@ from ... import engine
 from ...constructor import BACKBONES
 from ...engine import functional as EF
 from ..base import BaseBackbone
+from .swin import DropPath, draw_drop_scales
 
 
 def get_padding(kernel_size: int, stride: int, dilation: int = 1) -> int:
@@ -65,7 +73,8 @@ class BasicBlock(nn.Module):
         assert cardinality == 1 and base_width == 64, 'BasicBlock only supports cardinality=1, base_width=64'
         first_dilation = first_dilation or dilation
         _unsupported(eca_dilated=attn_layer == 'eca' and (dilation != 1 or first_dilation != 1),
-                     attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer, drop_block=drop_block, drop_path=drop_path)
+                     attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer, drop_block=drop_block)
+        _refuse_eca_drop_path(attn_layer, drop_path)
         first_planes = planes // reduce_first
         outplanes = planes * self.expansion
         self.conv1 = nn.Conv2d(inplanes, first_planes, kernel_size=3, stride=stride, padding=first_dilation,
@@ -78,6 +87,7 @@ class BasicBlock(nn.Module):
         self.act2 = act_layer(inplace=True)
         self.downsample = downsample
         self.stride = stride
+        self.drop_path = drop_path        # DropPath or None; no parameters: the state_dict is that of the block without it
 
     def zero_init_last(self):
         nn.init.zeros_(self.bn2.weight)
@@ -94,7 +104,7 @@ class BasicBlock(nn.Module):
         y = EF.to_phase(r, EF.conv_bn_act(r, x, self.conv1, self.bn1, relu=True), d2)
         if self.se is not None:
             return EF.eca_residual(r, EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=False), self.se, shortcut)
-        return EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True, shortcut=shortcut)
+        return EF.conv_bn_act(r, y, self.conv2, self.bn2, relu=True, shortcut=shortcut, row_scale=_drop_scale(self.drop_path, y))
 
     def _shortcut(self, r, x):
         return _shortcut(r, x, self.downsample)
@@ -109,7 +119,8 @@ class Bottleneck(nn.Module):
         super().__init__()
         first_dilation = first_dilation or dilation
         _unsupported(eca_dilated=attn_layer == 'eca' and (dilation != 1 or first_dilation != 1),
-                     attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer, drop_block=drop_block, drop_path=drop_path)
+                     attn_layer=attn_layer != 'eca' and attn_layer, aa_layer=aa_layer, drop_block=drop_block)
+        _refuse_eca_drop_path(attn_layer, drop_path)
         width = int(math.floor(planes * (base_width / 64)) * cardinality)
         first_planes = width // reduce_first
         outplanes = planes * self.expansion
@@ -127,6 +138,7 @@ class Bottleneck(nn.Module):
         self.act3 = act_layer(inplace=True)
         self.downsample = downsample
         self.stride = stride
+        self.drop_path = drop_path        # DropPath or None; no parameters: the state_dict is that of the block without it
 
     def zero_init_last(self):
         nn.init.zeros_(self.bn3.weight)
@@ -145,7 +157,21 @@ class Bottleneck(nn.Module):
         shortcut = _shortcut(r, x, self.downsample)
         if self.se is not None:
             return EF.eca_residual(r, EF.conv_bn_act(r, y, self.conv3, self.bn3, relu=False), self.se, shortcut)
-        return EF.conv_bn_act(r, y, self.conv3, self.bn3, relu=True, shortcut=shortcut)
+        return EF.conv_bn_act(r, y, self.conv3, self.bn3, relu=True, shortcut=shortcut, row_scale=_drop_scale(self.drop_path, y))
+
+
+def _drop_scale(drop_path, t):
+    """The block's per-sample keep / scale vector for this step (None in eval mode or without a DropPath): `t` is the operand of
+    the block's last unit, in phase layout d * d images per sample."""
+    if drop_path is None:
+        return None
+    return drop_path.sample_scale(t.shape[0] // (t.phase * t.phase), t.data.device)
+
+
+def _refuse_eca_drop_path(attn_layer, drop_path):
+    if attn_layer == 'eca' and drop_path is not None:
+        raise NotImplementedError('torchok_amd ResNet: drop_path with attn_layer=eca is not built (the channel-attention residual '
+                                  'kernel, csrc/eca.hip, has no row scale)')
 
 
 def _shortcut(r, x, downsample):
@@ -197,13 +223,18 @@ def make_blocks(block_fn, channels, block_repeats, inplanes, reduce_first=1, out
                 down_kernel_size=1, avg_down=False, drop_block_rate=0., drop_path_rate=0., **kwargs):
     # dilated stages (output_stride 8 / 16) run in phase layout on the plain kernels (EF.phase_split).  Not with avg_down: timm's
     # AvgPool2dSame of a dilated 'd' / 't' shortcut is not built; not with ECA: its per-image mean is not phase-agnostic
-    _unsupported(drop_block_rate=drop_block_rate, drop_path_rate=drop_path_rate)
+    if drop_block_rate:
+        raise NotImplementedError(f'torchok_amd ResNet: drop_block_rate={drop_block_rate} is not built (DropBlock of [timm 0.6.13] '
+                                  f'cannot be checked offline); drop_path_rate is')
+    if drop_path_rate and kwargs.get('attn_layer') == 'eca':
+        _refuse_eca_drop_path('eca', drop_path_rate)
     if output_stride != 32 and (avg_down or kwargs.get('attn_layer') == 'eca'):
         raise NotImplementedError(f'torchok_amd ResNet: output_stride={output_stride} with '
                                   f'{"avg_down" if avg_down else "attn_layer=eca"} is not built (dilated stages: convolutional '
                                   f'shortcuts, no channel attention)')
     no_downsample_stages = kwargs.pop('no_downsample_stages', [0])
     stages, feature_info = [], []
+    net_num_blocks, net_block_idx = sum(block_repeats), 0
     net_stride = 4
     dilation = prev_dilation = 1
     for stage_idx, (planes, num_blocks) in enumerate(zip(channels, block_repeats)):
@@ -222,11 +253,14 @@ def make_blocks(block_fn, channels, block_repeats, inplanes, reduce_first=1, out
                               norm_layer=kwargs.get('norm_layer'))
         blocks = []
         for block_idx in range(num_blocks):
+            block_dpr = drop_path_rate * net_block_idx / (net_num_blocks - 1)      # stochastic depth linear decay rule
             blocks.append(block_fn(inplanes, planes, stride if block_idx == 0 else 1,
                                    downsample if block_idx == 0 else None, reduce_first=reduce_first, dilation=dilation,
-                                   first_dilation=prev_dilation, **kwargs))
+                                   first_dilation=prev_dilation, drop_path=DropPath(block_dpr) if block_dpr > 0. else None,
+                                   **kwargs))
             prev_dilation = dilation
             inplanes = planes * block_fn.expansion
+            net_block_idx += 1
         stages.append((stage_name, nn.Sequential(*blocks)))
         feature_info.append(dict(num_chs=inplanes, reduction=net_stride, module=stage_name))
     return stages, feature_info
@@ -289,6 +323,9 @@ class ResNet(BaseBackbone):
                     m.zero_init_last()
 
     def _run(self, r, x: torch.Tensor, all_features: bool = True):
+        if self.training:       # every block's keep / scale vector of this step in one draw
+            draw_drop_scales([blk.drop_path for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for blk in layer],
+                             x.shape[0], x.device)
         t = r.input(x, c_pad_to=4 if x.shape[1] <= 4 else 8)
         feats = []
         last = self.conv1
