@@ -569,7 +569,8 @@ int tok_colsum_f32(const float* src, int64_t rows, int cols, float* dst, int acc
 int tok_colsum_f32_pair(const float* src0, const float* src1, int64_t rows, int cols, float* dst0, int accumulate0,
                         float* dst1, int accumulate1, void* stream);
 /* kind 0: ReLU (cpb_mlp), 1: GELU erf (Mlp); count % 8 == 0.  tok_act_bwd also takes kind 2 = identity
- * (dx (+)= dout: the pass-through branch of a residual)                                                  */
+ * (dx (+)= dout: the pass-through branch of a residual).  Every pointer 16-byte aligned (TOK_ERR_INVALID
+ * otherwise, nothing is launched).  A quiet NaN input gives GELU = 0 (a signalling one -5.6 Phi(-5.6)).  */
 int tok_act_fwd(int kind, const void* x, void* out, size_t count, void* stream);
 int tok_act_bwd(int kind, const void* dout, const void* x, void* dx, int accumulate, size_t count, void* stream);
 /* WindowAttention.forward + the roll / window_partition / window_reverse of SwinTransformerBlock._attn:
@@ -593,7 +594,8 @@ int tok_cpb_bias_fwd(const void* table, int ld, const int64_t* index, int heads,
 int tok_cpb_bias_bwd(const float* dbias, int transposed, const void* table, int ld, const int64_t* index,
                      int heads, int n_tokens, int table_rows, void* dtable, void* stream);
 /* PatchMerging gather [B][H][W][c] -> [B][H/2][W/2][4c] (x0, x1, x2, x3 order); inverse != 0: the inverse
- * permutation (its backward)                                                                             */
+ * permutation (its backward).  H, W even, c % 8 == 0, src and dst 16-byte aligned (TOK_ERR_INVALID
+ * otherwise, nothing is launched).                                                                       */
 int tok_patch_merge(const void* src, void* dst, int batch, int h, int w, int c, int inverse, void* stream);
 
 /* ---- self-supervised / triplet losses ---------------------------------------------------
@@ -649,8 +651,11 @@ int tok_conv_dgrad_act(const tok_conv_desc* d, const void* dy, const void* w_dgr
  * while fc2 consumes them out of registers; with pre given and act = NULL only the pre-activation rows are written
  * (tok_mlp_bwd_dx reads nothing else).  Rounding points
  * (pre-activation and activation to bf16) and results are those of tok_conv_fwd_act + tok_conv_fwd, bit for bit.
- * tok_mlp_serves: 1 when the geometry has a kernel (c in {96, 192, 384}, hidden = 4c), else the caller stays on the two
- * GEMM launches.                                                                                                         */
+ * tok_mlp_serves: 1 when the geometry has a kernel (c in {96, 192, 384}, hidden = 4c, at least TOK_MLP_MIN_ROWS rows, and
+ * the hidden rows of every WHOLE tile below 2^32 bytes: ceil(rows / TILE) * TILE * hidden * 2 < 2^32 with TILE = 256 tokens
+ * at c = 96 and 192, 128 at c = 384 — the kernels form 32-bit byte offsets for every row of the last tile), else the caller
+ * stays on the two GEMM launches.  Every bf16 operand of tok_mlp_fwd / tok_mlp_bwd_dx (x, w1, w2, y, pre, act; dy, w2_dgrad,
+ * pre, w1_dgrad, dx, dpre) is 16-byte aligned: TOK_ERR_INVALID otherwise, nothing is launched.                            */
 int tok_mlp_serves(int64_t rows, int c, int hidden);
 int tok_mlp_fwd(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, void* pre,
                 void* act, int64_t rows, int c, int hidden, void* stream);
@@ -913,20 +918,23 @@ int tok_layer_scale_bwd(const void* dout, const void* a, const float* gamma, con
                         void* stream);
 /* Patch embedding as a GEMM: img NHWC bf16 [n][h][w][4] (3 channels zero-padded to 4) -> rows bf16 [n*(h/p)*(w/p)][p*p*4],
  * element (py, px, c) of a row at (py*p + px)*4 + c — the k = p, stride = p convolution is then a 1x1 layer against the
- * [D][p][p][4] weight pack.  h, w multiples of p.                                                                             */
+ * [D][p][p][4] weight pack.  h, w multiples of p; img and rows 8-byte aligned (one pixel per access; TOK_ERR_INVALID
+ * otherwise, nothing is launched).                                                                                            */
 int tok_patch_gather(const void* img, int n, int h, int w, int p, void* rows, void* stream);
 /* Token assembly, rounded once to bf16: out [batch*T][d] with T = patches + (cls != NULL);
  *   default:          out[b][0] = cls + pos[0],  out[b][1+i] = patch[b][i] + pos[1+i]
  *   no_embed_class:   out[b][0] = cls,           out[b][1+i] = patch[b][i] + pos[i]        (no cls: out[b][i] = patch + pos[i])
  * patch bf16 [batch*patches][d], pos / cls fp32.  tok_vit_embed_bwd: d(pos) / d(cls) (each nullable; =|+= per *_acc) as sums over
- * the images in image order (no float atomics); d(patch) is tok_rows_select of dout.                                          */
+ * the images in image order (no float atomics); d(patch) is tok_rows_select of dout.  d % 8 == 0; patch and out 16-byte
+ * aligned (TOK_ERR_INVALID otherwise, nothing is launched); d(cls) needs has_cls.                                             */
 int tok_vit_embed_fwd(const void* patch, const float* pos, const float* cls, int batch, int patches, int d, int no_embed_class,
                       void* out, void* stream);
 int tok_vit_embed_bwd(const void* dout, int batch, int patches, int d, int has_cls, int no_embed_class, float* dpos, int pos_acc,
                       float* dcls, int cls_acc, void* stream);
 /* Rows [first, first + count) of every image's t token rows (bf16, pitch d, d % 8 == 0).  dir 0: dst [batch*count][d] = those
  * rows of src [batch*t][d].  dir 1 (the transpose): dst [batch*t][d] receives src [batch*count][d] in those rows (+= with
- * accumulate) and 0 in the others (left as they are with accumulate).                                                         */
+ * accumulate) and 0 in the others (left as they are with accumulate).  src and dst 16-byte aligned (TOK_ERR_INVALID
+ * otherwise, nothing is launched).                                                                                            */
 int tok_rows_select(const void* src, int batch, int t, int first, int count, int d, void* dst, int dir, int accumulate,
                     void* stream);
 

@@ -154,7 +154,9 @@ class FakeTok:
 
     def tok_mlp_serves(self, rows, c, hidden):
         import os
-        return int(c in (96, 192, 384) and hidden == 4 * c and rows >= int(os.environ.get('TOK_MLP_MIN_ROWS', '32768')))
+        tile = 128 if c == 384 else 256      # 32-bit byte offsets over every row of the last tile (include/tok.h)
+        return int(c in (96, 192, 384) and hidden == 4 * c and rows >= int(os.environ.get('TOK_MLP_MIN_ROWS', '32768')) and
+                   rows > 0 and -(-rows // tile) * tile * hidden * 2 < 2 ** 32)
 
     # The fused Mlp entry points go through the SAME torch primitives, on the same shapes, as the launches they replace
     # (F.conv2d / conv2d_input on (rows, C, 1, 1) tensors, tok_act_fwd / tok_act_bwd's formulas): the host test compares the two

@@ -207,6 +207,25 @@ def test_relpos_gather_past_one_trip_of_the_capped_grid():
     assert torch.equal(tg.view.double(), want)            # small integers (|sum| < 2^24): bit-exact
 
 
+def test_relpos_gather_of_beit_large_512_takes_a_second_trip():
+    """16 heads on a 32 x 32 grid (n = 1025, beit_large_patch16_512), the case relpos_bias_fwd_kernel's comment names: 16 * 1025^2 is
+    just past the 2^24 elements one trip of the capped grid covers.  With the model's own index; exact."""
+    lib, st = _C.lib(), stream_ptr()
+    heads = 16
+    index = R.gen_relative_position_index((32, 32))
+    n, rows = index.shape[0], int(index.max()) + 1
+    assert n == 1025 and 2 ** 24 < heads * n * n < 2 ** 24 + 2 ** 16
+    ldb = _ldb(n)
+    table = torch.randn(rows, heads, generator=torch.Generator().manual_seed(5)).cuda()
+    idx = index.cuda()
+    bg = Guarded(heads * n, n, ldb, dtype=F32)
+    _C.check(lib.tok_relpos_bias_fwd(table.data_ptr(), idx.data_ptr(), heads, n, bg.ptr, ldb, st), 'relpos fwd')
+    torch.cuda.synchronize()
+    bg.check('bias')
+    want = table[idx.view(-1)].view(n, n, heads).permute(2, 0, 1)
+    assert torch.equal(bg.view.reshape(heads, n, n).view(torch.int32), want.contiguous().view(torch.int32))      # exact
+
+
 # ---- LayerScale residual ---------------------------------------------------------------------------------------------------------
 def _layer_scale(x, a, gamma, scale, rps, dout, da_prior=None, dg_prior=None):
     lib, st = _C.lib(), stream_ptr()

@@ -1480,12 +1480,16 @@ def test_gemm_activation_epilogues_equal_the_unfused_pair(libs, rows, c, k, kind
     assert lib.tok_conv_fwd_act(d3, P(x), P(w), None, P(y1), P(a1), kind, st) != 0         # 3x3: refused
 
 
-@pytest.mark.parametrize('rows,c', [(1000, 96), (77, 192), (4133, 384), (256, 96), (70000, 96), (33000, 192), (16500, 384)])
+@pytest.mark.parametrize('rows,c', [(1000, 96), (77, 192), (4133, 384), (256, 96), (70000, 96), (33000, 192), (16500, 384),
+                                    (65869, 192), (32973, 384)])
 @pytest.mark.parametrize('save', [False, True])
 def test_fused_mlp_equals_the_two_gemm_launches(libs, rows, c, save):
     """tok_mlp_fwd == tok_conv_fwd_act (fc1 + GELU) + tok_conv_fwd (fc2), bit for bit, ragged row counts included (tiles of
-    256 / 128 tokens, several tiles per workgroup at the larger counts); with pre / act given those rows are the unfused
-    launches' too.  Against the fp32 restatement (fake_backend: torch matmul + F.gelu on the same rounding points) <= 1e-2."""
+    256 / 128 tokens); with pre / act given those rows are the unfused launches' too.  The grid is capped at 256 workgroups, so
+    a workgroup walks several tiles only past 256 tiles: (70000, 96) has 274 (the prefetch form), (65869, 192) and (32973, 384)
+    have 258 (the forms that reload the token rows after the epilogue); (33000, 192) and (16500, 384) have 129 tiles, one per
+    workgroup.  Against the fp32 restatement (fake_backend: torch matmul + F.gelu on the same rounding points) <= 1e-2; against
+    fp64, element by element: tests/test_mlp_rows_contract_gpu.py."""
     lib, fake = libs
     st = torch.cuda.current_stream().cuda_stream
     P = lambda t_: t_.data_ptr() if t_ is not None else None   # noqa: E731
@@ -1526,7 +1530,8 @@ def test_fused_mlp_equals_the_two_gemm_launches(libs, rows, c, save):
     assert lib.tok_mlp_fwd(P(x), P(w1), P(b1), P(w2), P(b2), P(y1), None, P(act1), rows, c, h, st) != 0
 
 
-@pytest.mark.parametrize('rows,c', [(1000, 96), (77, 192), (4133, 384), (70000, 96), (33000, 192), (16500, 384)])
+@pytest.mark.parametrize('rows,c', [(1000, 96), (77, 192), (4133, 384), (70000, 96), (33000, 192), (16500, 384),
+                                    (65869, 192), (32973, 384)])
 @pytest.mark.parametrize('acc', [0, 1])
 def test_fused_mlp_backward_equals_the_two_dgrad_launches(libs, rows, c, acc):
     """tok_mlp_bwd_dx == tok_conv_dgrad_act (fc2, GELU') + tok_conv_dgrad (fc1), bit for bit: dx (fresh or accumulated onto

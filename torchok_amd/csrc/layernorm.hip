@@ -484,6 +484,7 @@ extern "C" int tok_colsum_f32_pair(const float* src0, const float* src1, int64_t
 
 extern "C" int tok_act_fwd(int kind, const void* x, void* out, size_t count, void* stream) {
   TOK_CHECK_ARG(x && out && count > 0 && count % 8 == 0 && (kind == 0 || kind == 1), "tok_act_fwd: bad args");
+  TOK_CHECK_ARG(tok_aligned(x, 16) && tok_aligned(out, 16), "tok_act_fwd: x / out must be 16-byte aligned");
   hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks_for(count / 8)), dim3(256), 0, tok_stream(stream), kind, (const bf16*)x,
                      (bf16*)out, count / 8);
   TOK_CHECK_LAUNCH("tok_act_fwd");
@@ -493,6 +494,7 @@ extern "C" int tok_act_fwd(int kind, const void* x, void* out, size_t count, voi
 extern "C" int tok_act_bwd(int kind, const void* dout, const void* x, void* dx, int accumulate, size_t count,
                            void* stream) {
   TOK_CHECK_ARG(dout && x && dx && count > 0 && count % 8 == 0 && kind >= 0 && kind <= 2, "tok_act_bwd: bad args");
+  TOK_CHECK_ARG(tok_aligned(dout, 16) && tok_aligned(x, 16) && tok_aligned(dx, 16), "tok_act_bwd: dout / x / dx must be 16-byte aligned");
   hipLaunchKernelGGL(act_bwd_kernel, dim3(blocks_for(count / 8)), dim3(256), 0, tok_stream(stream), kind,
                      (const bf16*)dout, (const bf16*)x, (bf16*)dx, accumulate, count / 8);
   TOK_CHECK_LAUNCH("tok_act_bwd");

@@ -501,7 +501,13 @@ int mlp_min_rows() {   // below this the serial chain of hidden chunks of one ti
 extern "C" int tok_mlp_serves(int64_t rows, int c, int hidden) {
   if (!(c == 96 || c == 192 || c == 384)) return 0;
   if (hidden != 4 * c) return 0;
-  if (rows < mlp_min_rows() || rows <= 0 || rows * (long long)hidden * 2 >= (1ll << 32)) return 0;
+  if (rows < mlp_min_rows() || rows <= 0) return 0;
+  // The kernels form the byte offsets of the hidden rows (pre / act / dpre) in 32 bits for EVERY row of the last tile, the rows
+  // past `rows` included, and rely on the buffer range check to drop those: an offset that wraps past 2^32 would come back as a
+  // small in-range one and the store would land in the first rows.  So the whole last tile has to stay below 2^32 bytes.
+  const long long tile = c == 384 ? 128 : 256;     // WAVES * NT * 16 of the forms launch_c picks
+  const long long padded = (rows + tile - 1) / tile * tile;
+  if (padded * (long long)hidden * 2 >= (1ll << 32)) return 0;
   return 1;
 }
 
@@ -509,6 +515,9 @@ extern "C" int tok_mlp_fwd(const void* x, const void* w1, const float* b1, const
                            void* act, int64_t rows, int c, int hidden, void* stream) {
   TOK_CHECK_ARG(x && w1 && b1 && w2 && b2 && y, "tok_mlp_fwd: null pointer");
   TOK_CHECK_ARG(pre != nullptr || act == nullptr, "tok_mlp_fwd: act rows are saved together with the pre rows only");
+  TOK_CHECK_ARG(tok_aligned(x, 16) && tok_aligned(w1, 16) && tok_aligned(w2, 16) && tok_aligned(y, 16) && tok_aligned(pre, 16) &&
+                    tok_aligned(act, 16),
+                "tok_mlp_fwd: x / w1 / w2 / y / pre / act must be 16-byte aligned");
   TOK_CHECK_ARG(tok_mlp_serves(rows, c, hidden), "tok_mlp_fwd: geometry (%lld, %d, %d) is not served (tok_mlp_serves)", (long long)rows, c,
                 hidden);
   MlpArgs a;
@@ -527,6 +536,9 @@ extern "C" int tok_mlp_fwd(const void* x, const void* w1, const float* b1, const
 extern "C" int tok_mlp_bwd_dx(const void* dy, const void* w2_dgrad, const void* pre, const void* w1_dgrad, void* dx, int accumulate,
                               void* dpre, int64_t rows, int c, int hidden, void* stream) {
   TOK_CHECK_ARG(dy && w2_dgrad && pre && w1_dgrad && dx, "tok_mlp_bwd_dx: null pointer");
+  TOK_CHECK_ARG(tok_aligned(dy, 16) && tok_aligned(w2_dgrad, 16) && tok_aligned(pre, 16) && tok_aligned(w1_dgrad, 16) &&
+                    tok_aligned(dx, 16) && tok_aligned(dpre, 16),
+                "tok_mlp_bwd_dx: dy / w2_dgrad / pre / w1_dgrad / dx / dpre must be 16-byte aligned");
   TOK_CHECK_ARG(tok_mlp_serves(rows, c, hidden), "tok_mlp_bwd_dx: geometry (%lld, %d, %d) is not served (tok_mlp_serves)",
                 (long long)rows, c, hidden);
   MlpArgs a;

@@ -46,6 +46,10 @@ static inline int launched(const char* who, const char* stage) {
   return TOK_ERR_LAUNCH;
 }
 
+// the vector loads and stores (ldg16 / stg16, 16-byte buffer accesses, 8-byte pixels) need a base aligned to the access size as well
+// as a pitch that is a multiple of it
+static inline bool tok_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 // workgroups of 256 threads for n work items
 static inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -104,7 +108,9 @@ __device__ __forceinline__ void stg16(bf16* p, bf16x8 v) { *reinterpret_cast<bf1
 // < 2e-8) and ONE v_exp_f32, then GELU(x) = max(x, 0) - a Phi(-a) for either sign.  8 VALU + 1 transcendental per element (the
 // Abramowitz-Stegun 7.1.26 form of round 3a cost 12 + 2, libm's erff + expf ~55): in the GEMM epilogues and in the fused MLP the
 // activation's VALU time is what competes with the MFMA pipe.  All of it is fma / med3, so the two-wide form (v_pk_fma_f32)
-// rounds identically.  A NaN input gives 0 (med3 / max drop it); the residual stream next to every GELU here keeps the NaN.
+// rounds identically.  A NaN input is dropped (med3 / max): a quiet NaN, the only kind arithmetic produces, gives 0; a signalling
+// one is clamped to 5.6 by v_med3_f32 and gives what every x < -5.6 gives, -5.6 Phi(-5.6) ~ -5e-8.  The residual stream next to
+// every GELU here keeps the NaN.
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 #define TOK_GELU_C0 (-1.0000008344650269f)
 #define TOK_GELU_C1 (-1.1510831117630005f)

@@ -179,6 +179,7 @@ extern "C" int tok_relpos_bias_bwd(const float* dbias, int ldb, const int64_t* i
 extern "C" int tok_patch_merge(const void* src, void* dst, int batch, int h, int w, int c, int inverse, void* stream) {
   TOK_CHECK_ARG(src && dst && batch > 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && c > 0 && c % 8 == 0,
                 "tok_patch_merge: bad args");
+  TOK_CHECK_ARG(tok_aligned(src, 16) && tok_aligned(dst, 16), "tok_patch_merge: src / dst must be 16-byte aligned");
   hipLaunchKernelGGL(patch_merge_kernel, dim3(blocks_for((size_t)batch * h * w * (c >> 3))), dim3(256), 0,
                      tok_stream(stream), (const bf16*)src, (bf16*)dst, batch, h, w, c, inverse);
   TOK_CHECK_LAUNCH("tok_patch_merge");

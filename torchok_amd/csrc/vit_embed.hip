@@ -108,6 +108,7 @@ __global__ __launch_bounds__(256) void rows_select_kernel(const bf16* __restrict
 extern "C" int tok_patch_gather(const void* img, int n, int h, int w, int p, void* rows, void* stream) {
   TOK_CHECK_ARG(img && rows && n > 0 && p > 0 && h >= p && w >= p && h % p == 0 && w % p == 0,
                 "tok_patch_gather: %dx%d image, patch %d (sides must be multiples of the patch)", h, w, p);
+  TOK_CHECK_ARG(tok_aligned(img, 8) && tok_aligned(rows, 8), "tok_patch_gather: img / rows must be 8-byte aligned");
   const int64_t px = (int64_t)n * h * w;
   hipLaunchKernelGGL(patch_gather_kernel, dim3(blocks_of(px)), dim3(256), 0, tok_stream(stream), (const uint2*)img, n, h, w, p,
                      (uint2*)rows);
@@ -118,6 +119,7 @@ extern "C" int tok_patch_gather(const void* img, int n, int h, int w, int p, voi
 extern "C" int tok_vit_embed_fwd(const void* patch, const float* pos, const float* cls, int batch, int patches, int d,
                                  int no_embed_class, void* out, void* stream) {
   TOK_CHECK_ARG(patch && pos && out && batch > 0 && patches > 0 && d > 0 && d % 8 == 0, "tok_vit_embed_fwd: bad args");
+  TOK_CHECK_ARG(tok_aligned(patch, 16) && tok_aligned(out, 16), "tok_vit_embed_fwd: patch / out must be 16-byte aligned");
   const int prefix = cls ? 1 : 0;
   hipLaunchKernelGGL(vit_embed_fwd_kernel, dim3(blocks_of((int64_t)batch * (patches + prefix) * (d / 8))), dim3(256), 0,
                      tok_stream(stream), (const bf16*)patch, pos, cls, batch, patches, d, prefix, no_embed_class ? 1 : 0,
@@ -142,6 +144,7 @@ extern "C" int tok_rows_select(const void* src, int batch, int t, int first, int
                                int accumulate, void* stream) {
   TOK_CHECK_ARG(src && dst && batch > 0 && t > 0 && first >= 0 && count > 0 && first + count <= t && d > 0 && d % 8 == 0 &&
                 (dir == 0 || dir == 1), "tok_rows_select: bad args");
+  TOK_CHECK_ARG(tok_aligned(src, 16) && tok_aligned(dst, 16), "tok_rows_select: src / dst must be 16-byte aligned");
   const int64_t work = (int64_t)batch * (dir == 0 ? count : t) * (d / 8);
   hipLaunchKernelGGL(rows_select_kernel, dim3(blocks_of(work)), dim3(256), 0, tok_stream(stream), (const bf16*)src, batch, t,
                      first, count, d, (bf16*)dst, dir, accumulate ? 1 : 0);
