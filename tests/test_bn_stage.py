@@ -1,5 +1,5 @@
-"""The BatchNorm stage every "producer -> BatchNorm -> activation" unit shares (engine/functional.py: batch_stats, bn_coeffs,
-bn_apply, _ConvBnActNode._bn_bwd), pinned per unit on the host stand-in: the refusals of the depthwise unit and of the neck
+"""The BatchNorm stage every "producer -> BatchNorm -> activation" unit shares (engine/bn_stage.py: batch_stats, bn_coeffs,
+choose_form, bn_backward), pinned per unit on the host stand-in: the refusals of the depthwise unit and of the neck
 (only the conv unit's tests pinned them before), when tok_bn_act_fwd is handed a ReLU mask pointer and when tok_bn_finalize is
 handed the running statistics.  The mask rules differ between the units and are pinned as they are:
   conv_bn_act:  ReLU and gradients on (whatever requires a gradient);

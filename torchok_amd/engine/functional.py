@@ -27,6 +27,8 @@ import torch
 from torch import nn
 
 from .. import _C
+from .bn_stage import (HARD_SWISH, MASKLESS, RELU, RELU6, batch_stats, bn_apply, bn_backward, bn_coeffs,  # noqa: F401  (re-exported)
+                       choose_form, running_stat_ptrs)
 from .core import _ms as _core_ms
 from . import paramgrad as PG
 from .core import (BF16, Node, Region, TTensor, await_ready, donate_grad, grad_target, is_last_contribution, pad8, ptr,
@@ -249,18 +251,10 @@ def _check_conv(conv: nn.Conv2d, phase: int = 1):
 
 # ---- conv + bn + (add) + relu ------------------------------------------------------------------------
 
-RELU = 'relu'
-HARD_SWISH = 'hard_swish'
-RELU6 = 'relu6'
-# the mask-less activations -> the entry-point family tok_bn_<family>_fwd / _bwd_reduce / _bwd_apply that serves them
-MASKLESS = {HARD_SWISH: 'hswish', RELU6: 'relu6'}
-
-
 def _check_act(relu, act, bn, shortcut=None, pool=False, defer_apply=False):
     """The unit's one activation, None / RELU / HARD_SWISH / RELU6, from the public keywords.  act=None: what `relu` says.
-    act='hard_swish' or 'relu6' (`relu` is not looked at): BatchNorm + that activation on tok_bn_hswish_* / tok_bn_relu6_*,
-    which keep no mask and know no shortcut, pooled or deferred form (MobileNetV3 and EfficientNet-Lite never activate after
-    a residual add)."""
+    act='hard_swish' or 'relu6' (`relu` is not looked at): bn_stage.Maskless, which knows no shortcut, pooled or deferred form
+    (MobileNetV3 and EfficientNet-Lite never activate after a residual add)."""
     if act is None:
         return RELU if relu else None
     if act not in MASKLESS:
@@ -270,166 +264,18 @@ def _check_act(relu, act, bn, shortcut=None, pool=False, defer_apply=False):
     return act
 
 
-def _maskless(lib, act, stage):
-    """(entry point, its name) of a mask-less activation's `stage`: 'fwd', 'bwd_reduce' or 'bwd_apply'."""
-    name = f'tok_bn_{MASKLESS[act]}_{stage}'
-    return getattr(lib, name), name
-
-
-# ---- the BatchNorm stage of a unit: every "producer -> BatchNorm -> activation" unit takes it from here ---------------
-
-def batch_stats(bn: nn.BatchNorm2d) -> bool:
-    """Does this BatchNorm normalise with the statistics of the batch (training mode, or no running statistics kept)?"""
-    return bn.training or bn.running_mean is None
-
-
-def bn_coeffs(lib, st, bn, stats, rows, m, kp, dev):
-    """(scale, shift, mean, rstd) per channel: from the producer's partial sums `stats` [2][rows][kp] over m rows (running
-    statistics updated when the module tracks them), or, stats=None, from the running statistics (mean = rstd = None)."""
-    # one allocation for the per-channel vectors (an allocator call costs the launch thread 2-3 us; HRNet-W48 makes 307
-    # of these units per step)
-    vec = torch.empty((4, kp), dtype=F32, device=dev)
-    scale, shift = vec[0], vec[1]
-    if stats is None:
-        _C.check(lib.tok_bn_eval_coeffs(ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
-                                        float(bn.eps), kp, bn.num_features, ptr(scale), ptr(shift), st), 'tok_bn_eval_coeffs')
-        return scale, shift, None, None
-    if bn.momentum is None:
-        raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
-    mean, rstd = vec[2], vec[3]
-    track = bn.training and bn.track_running_stats and bn.running_mean is not None
-    _C.check(lib.tok_bn_finalize(ptr(stats), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(bn.bias),
-                                 ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                                 ptr(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps),
-                                 ptr(mean), ptr(rstd), ptr(scale), ptr(shift), st), 'tok_bn_finalize')
-    return scale, shift, mean, rstd
-
-
-def bn_apply(lib, st, y, scale, shift, act, shortcut, want_mask, m, kp, row_scale=None):
-    """The plain apply pass out = act(y * scale + shift (+ shortcut)) -> (out_data, mask).  `want_mask` is the caller's
-    rule for keeping the ReLU bits; hard-swish and ReLU6 keep none.
-    row_scale (stochastic depth, a ReLU unit with a shortcut): out = relu(s[sample] * (y * scale + shift) + shortcut), the sample
-    of a row being row // (m // len(row_scale))."""
-    out_data = torch.empty_like(y)
-    if act in MASKLESS:
-        fwd, name = _maskless(lib, act, 'fwd')
-        _C.check(fwd(ptr(y), ptr(scale), ptr(shift), ptr(out_data), m, kp, st), name)
-        return out_data, None
-    mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=y.device) if want_mask else None
-    if row_scale is not None:
-        _C.check(lib.tok_bn_droppath_fwd(ptr(y), ptr(scale), ptr(shift), ptr(shortcut.data), ptr(row_scale),
-                                         m // row_scale.numel(), ptr(out_data), ptr(mask), m, kp, st), 'tok_bn_droppath_fwd')
-        return out_data, mask
-    _C.check(lib.tok_bn_act_fwd(ptr(y), ptr(scale), ptr(shift), ptr(shortcut.data) if shortcut is not None else None,
-                                int(act == RELU), ptr(out_data), ptr(mask), m, kp, st), 'tok_bn_act_fwd')
-    return out_data, mask
-
-
 class _ConvBnActNode(Node):
     needs_backward = True
-    act = None                      # None / RELU / HARD_SWISH / RELU6 (the last two: dz is recomputed from y, no mask)
-    relu = property(lambda self: self.act == RELU)
+    sub_capable = False             # this unit's data gradient can absorb a half-resolution contribution to d(x)
 
     def __init__(self):
-        self.x = self.out = self.shortcut = None
-        self.y = self.mask = None
-        self.region = None
+        self.x = self.out = self.shortcut = self.y = self.mask = self.region = None
+        self.form = None            # the form of the BatchNorm stage (bn_stage.choose_form); None: a unit without BatchNorm
         self.fused_partial = None   # (partial, rows) when a consumer's dgrad epilogue did our BN-bwd reduce
-        self.pool = None            # tap indices of the fused 3x3/s2 max-pool: `out` is the POOLED map, z was never stored
-        self.ypool = None           # raw conv output at the winning taps (pooled-domain BatchNorm-backward sums)
-        self.row_scale = None       # per-sample fp32 factor of the BatchNorm output (stochastic depth): the tok_bn_droppath_* trio
 
     def release(self):
-        self.x = self.out = self.shortcut = None
-        self.y = self.pk = self.mask = self.fused_partial = self.pool = self.ypool = None
-        self.mean = self.rstd = self.scale = self.shift = self.row_scale = None
-
-    def wants_fused_bwd_stats(self) -> bool:
-        """Can the kernel that completes d(out) also reduce sum(dz), sum(dz*y) for this unit?"""
-        # (the dgrad epilogues know the ReLU mask only: a hard-swish or ReLU6 producer takes the stand-alone reduce, and so does
-        # a unit with a row scale, whose dz is not mask * d(out))
-        return (self.bn is not None and self.batch_stats and self.pool is None and self.row_scale is None
-                and (self.act is None or (self.act == RELU and self.mask is not None)))
-
-    def _apply_bwd(self, lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp):
-        """dy = c1*dz + c2*y + c3 (and the shortcut's dz) for the unit's activation."""
-        if self.act in MASKLESS:
-            bwd_apply, name = _maskless(lib, self.act, 'bwd_apply')
-            _C.check(bwd_apply(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(coef), ptr(dy), m, kp, st), name)
-        elif self.row_scale is not None:
-            _C.check(lib.tok_bn_droppath_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.row_scale), m // self.row_scale.numel(),
-                                                   ptr(coef), ptr(dy), ds_ptr, ds_acc, m, kp, st), 'tok_bn_droppath_bwd_apply')
-        else:
-            _C.check(lib.tok_bn_bwd_apply(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift), ptr(coef),
-                                          int(self.relu), ptr(dy), ds_ptr, ds_acc, m, kp, st), 'tok_bn_bwd_apply')
-
-    def _finalize_bwd(self, lib, st, g, mask, m, kp, g_need, b_need):
-        """sum(dz), sum(dz*xhat) -> dgamma, dbeta; returns the apply coefficients (stand-alone reduce / finalize launches)."""
-        bn = self.bn
-        dzy = 0
-        if self.fused_partial is not None:
-            partial, rows = self.fused_partial   # reduced by the dgrad that completed d(out)
-            dzy = 1
-        else:
-            rows = lib.tok_bn_bwd_rows(m, kp)
-            if self.pool is not None and self.ypool is not None:
-                # sums over the pooled elements (each feeds exactly one position): 3 pooled-size reads, no gather
-                mp = self.out.data.numel() // kp
-                rows = lib.tok_bn_bwd_rows(mp, kp)
-                partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
-                _C.check(lib.tok_bn_pool_bwd_reduce_pooled(ptr(g), ptr(self.out.data), ptr(self.ypool), ptr(self.mean),
-                                                           ptr(self.rstd), mp, kp, ptr(partial), st),
-                         'tok_bn_pool_bwd_reduce_pooled')
-            elif self.pool is not None:
-                partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
-                n_, h_, w_, _ = self.y.shape
-                _C.check(lib.tok_bn_pool_bwd_reduce(ptr(g), ptr(self.pool), ptr(self.y), ptr(self.scale), ptr(self.shift),
-                                                    ptr(self.mean), ptr(self.rstd), n_, h_, w_, kp, ptr(partial), st),
-                         'tok_bn_pool_bwd_reduce')
-            elif self.act in MASKLESS:
-                partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
-                bwd_reduce, name = _maskless(lib, self.act, 'bwd_reduce')
-                _C.check(bwd_reduce(ptr(g), ptr(self.y), ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.rstd), m, kp,
-                                    ptr(partial), st), name)
-            elif self.row_scale is not None:
-                partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
-                _C.check(lib.tok_bn_droppath_bwd_reduce(ptr(g), ptr(self.y), ptr(mask), ptr(self.row_scale),
-                                                        m // self.row_scale.numel(), ptr(self.mean), ptr(self.rstd), m, kp,
-                                                        ptr(partial), st), 'tok_bn_droppath_bwd_reduce')
-            else:
-                partial = torch.empty((2, rows, kp), dtype=F32, device=g.device)
-                _C.check(lib.tok_bn_bwd_reduce(ptr(g), ptr(self.y), ptr(mask), ptr(self.scale), ptr(self.shift),
-                                               ptr(self.mean), ptr(self.rstd), int(self.relu), m, kp, ptr(partial), st),
-                         'tok_bn_bwd_reduce')
-        coef = torch.empty((3, kp), dtype=F32, device=g.device)
-        gbuf, bbuf, acc, finish = PG.pair_sinks(bn.weight if g_need else None, bn.bias if b_need else None)
-        _C.check(lib.tok_bn_bwd_finalize(ptr(partial), rows, m, kp, bn.num_features, ptr(bn.weight), ptr(self.mean),
-                                         ptr(self.rstd), ptr(gbuf), ptr(bbuf), ptr(coef), acc, dzy, st), 'tok_bn_bwd_finalize')
-        finish()
-        return coef
-
-    def _bn_bwd(self, lib, st, g, m, kp, need_dy, apply=None):
-        """The BatchNorm (+ activation) backward of the unit: dgamma / dbeta, then dy — None when nobody needs it.
-        `apply(mask, coef, dy)` stands in for the plain apply launch (the conv unit's own forms)."""
-        bn = self.bn
-        g_need, b_need = bn.weight.requires_grad, bn.bias.requires_grad
-        mask = self.mask if self.act == RELU else None
-        if self.batch_stats:
-            coef = self._finalize_bwd(lib, st, g, mask, m, kp, g_need, b_need)
-        else:
-            # eval-mode BN: y -> out is a fixed affine map: dy = scale * dz, dgamma/dbeta unsupported
-            if g_need or b_need:
-                raise NotImplementedError('gradients of BatchNorm affine parameters in eval mode')
-            coef = torch.zeros((3, kp), dtype=F32, device=g.device)
-            coef[0] = self.scale
-        if not need_dy:
-            return None
-        dy = torch.empty_like(self.y)
-        if apply is not None:
-            apply(mask, coef, dy)
-        else:
-            self._apply_bwd(lib, st, g, mask, coef, dy, None, 0, m, kp)
-        return dy
+        self.x = self.out = self.shortcut = self.y = self.pk = self.mask = self.fused_partial = self.form = None
+        self.mean = self.rstd = self.scale = self.shift = None
 
     def backward(self):
         lib, st = _C.lib(), stream_ptr()
@@ -437,50 +283,15 @@ class _ConvBnActNode(Node):
         g = out.grad
         if g is None:
             return
-        apply_event = None
-        conv, bn, d = self.conv, self.bn, self.desc
+        conv, d, x = self.conv, self.desc, self.x
         m, kp = self.y.numel() // self.y.shape[-1], self.y.shape[-1]
-        x: TTensor = self.x
-        w_need = conv.weight.requires_grad
-        x_need = x.requires_grad
-        bias_need = conv.bias is not None and conv.bias.requires_grad
-        sc: Optional[TTensor] = self.shortcut
+        w_need, x_need, bias_need = conv.weight.requires_grad, x.requires_grad, conv.bias is not None and conv.bias.requires_grad
+        sc_need = self.shortcut is not None and self.shortcut.requires_grad
         # decided ONCE: the BatchNorm apply launch carries the completion event iff the weight gradient forks behind it
         side = w_need and PG.goes_side(self, g, PG.CONV, m)
-
-        if bn is not None:
-            sc_need = sc is not None and sc.requires_grad
-
-            def apply(mask, coef, dy):
-                nonlocal apply_event
-                if side and self.pool is None and self.act not in MASKLESS:
-                    # the weight gradient will be forked to the side stream behind THIS apply pass: the pass carries the
-                    # completion event itself (no event-record packet on the main queue)
-                    apply_event = self.region.raw_event()     # armed right in front of the launch that carries it (below)
-                ds_ptr, ds_acc = None, 0
-                if sc_need:
-                    if sc.grad is None and out.grad_owned:
-                        # in-place mask of the incoming gradient, then donate it to the shortcut
-                        ds_ptr = ptr(g)
-                        donate_grad(sc, g)
-                    else:
-                        tgt, ds_acc = grad_target(sc)
-                        ds_ptr = ptr(tgt)
-                if self.pool is not None:
-                    n_, h_, w_, _ = self.y.shape
-                    _C.check(lib.tok_bn_pool_bwd_apply(ptr(g), ptr(self.pool), ptr(self.y), ptr(self.scale), ptr(self.shift),
-                                                       ptr(coef), n_, h_, w_, kp, ptr(dy), st), 'tok_bn_pool_bwd_apply')
-                    return
-                if apply_event is not None:
-                    lib.tok_next_launch_event(apply_event)
-                try:
-                    self._apply_bwd(lib, st, g, mask, coef, dy, ds_ptr, ds_acc, m, kp)
-                finally:
-                    if apply_event is not None:
-                        lib.tok_next_launch_event(None)   # never left armed for an unrelated later launch
-            dy = self._bn_bwd(lib, st, g, m, kp, w_need or x_need or bias_need or sc_need, apply)
-        else:
-            dy = g  # plain conv (+bias): the output gradient IS dy
+        dy, event = g, None     # plain conv (+bias): the output gradient IS dy
+        if self.form is not None:
+            dy, event = bn_backward(self, lib, st, g, m, kp, w_need or x_need or bias_need or sc_need, side)
         out.grad = None
         if dy is None:
             return
@@ -497,16 +308,12 @@ class _ConvBnActNode(Node):
         # long-M pointwise ones are HBM-bound themselves and would only fight the chain for bandwidth (PG.CONV)
         if w_need:
             k, _, _, c = _krsc(conv.weight)
-            PG.run_beside(self, side, (x.data, dy), raw_event=apply_event, fn=lambda: PG.weight_grad(
+            PG.run_beside(self, side, (x.data, dy), raw_event=event, fn=lambda: PG.weight_grad(
                 d, x.data, dy, k, c, weight=conv.weight, bias=conv.bias if bias_in_wgrad else None)[1:])
         if x_need:
-            prod = x.node
-            rider = _dgrad_rider(x)
-            sub = x.grad_sub if getattr(self, 'sub_capable', False) else None
+            rider, partial, bn_y, bn_mask = _rider_operands(lib, x, d, x.cp, g.device)
+            sub = x.grad_sub if self.sub_capable else None
             tgt, acc = grad_target(x, sub_ok=sub is not None)
-            partial = _rider_partial(lib, rider, prod, d, x.cp, g.device)
-            bn_y = ptr(prod.y) if rider == BN_SUMS else None
-            bn_mask = ptr(prod.mask) if (rider == MASKED_DZ or (rider == BN_SUMS and prod.relu)) else None
             if sub is not None:
                 # d(x) = this data gradient + the parked gradient of x[:, ::2, ::2] (a strided projection shortcut): one
                 # launch, d(x) written once, with the rider's epilogue
@@ -530,31 +337,27 @@ BN_SUMS = 'bn_sums'          # the BatchNorm-backward sums sum(dz), sum(dz * y) 
 MASKED_DZ = 'masked_dz'      # dz = relu_mask * d(out) and sum(dz) of a fused _Unit3Node (what its backward and its shortcut consume)
 
 
-def _dgrad_rider(x: TTensor):
-    """What rides the next data gradient into `x`: BN_SUMS, MASKED_DZ or None.  Only the last contribution completes d(x), and
-    only once per producer."""
+def _rider_operands(lib, x: TTensor, d, cp: int, dev, masked_ok: bool = True):
+    """(rider, partial, bn_y, bn_mask) of the data gradient of layer `d` into `x`: what rides it, BN_SUMS, MASKED_DZ (masked_ok=False:
+    a launch without the masked-dz store) or None; the (2, rows, cp) partial sums it writes, left on the producer for its backward;
+    the producer's operands of the epilogue (pointers).  Only the last contribution completes d(x), and only once per producer."""
     prod = x.node
-    if (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.wants_fused_bwd_stats()
-            and prod.fused_partial is None):
-        return BN_SUMS
+    if (isinstance(prod, _ConvBnActNode) and is_last_contribution(x) and prod.form is not None and prod.batch_stats
+            and prod.form.rider_ok and (not prod.form.relu or prod.mask is not None) and prod.fused_partial is None):
+        rider = BN_SUMS
     # (a fused unit WITHOUT activation has no ReLU bits: its d(out) is dz itself and takes the plain path)
-    if (isinstance(prod, _Unit3Node) and prod.relu and prod.mask is not None and is_last_contribution(x)
+    elif (masked_ok and isinstance(prod, _Unit3Node) and prod.relu and prod.mask is not None and is_last_contribution(x)
             and prod.masked_partial is None):
-        return MASKED_DZ
-    return None
-
-
-def _rider_partial(lib, rider, prod, d, cp: int, dev) -> Optional[torch.Tensor]:
-    """The (2, rows, cp) partial sums the data gradient of layer `d` writes for `rider`, left on the producer for its backward."""
-    if rider is None:
-        return None
+        rider = MASKED_DZ
+    else:
+        return None, None, None, None
     rows = lib.tok_conv_dgrad_stat_rows(d)
     partial = torch.empty((2, rows, cp), dtype=F32, device=dev)
     if rider == MASKED_DZ:
         prod.masked_partial = (partial, rows)
     else:
         prod.fused_partial = (partial, rows)
-    return partial
+    return rider, partial, ptr(prod.y) if rider == BN_SUMS else None, ptr(prod.mask)   # (a unit without activation kept no mask)
 
 
 # ---- unit 3 of a bottleneck: 1x1 conv -> BatchNorm -> + shortcut -> ReLU without the pre-normalisation tensor ----------
@@ -647,13 +450,9 @@ class _Unit3Node(Node):
         if not x_need:
             return
         # 5. d(x) = dz wa + x wb + cvec  (+ the BatchNorm-backward sums of the unit that produced x)
-        prod = x.node
-        fuse = _dgrad_rider(x) == BN_SUMS        # (the masked-dz store is not an epilogue of these launches)
-        tgt, acc = grad_target(x)
         dpp = _pointwise_desc(x, p)
-        part2 = _rider_partial(lib, BN_SUMS if fuse else None, prod, dpp, p, dev)
-        bn_y = ptr(prod.y) if fuse else None
-        bn_mask = ptr(prod.mask) if (fuse and prod.relu) else None
+        _, part2, bn_y, bn_mask = _rider_operands(lib, x, dpp, p, dev, masked_ok=False)   # (no masked-dz store in these launches)
+        tgt, acc = grad_target(x)
         if lib.tok_conv_dgrad2_ok(d, dpp):
             # both products in one launch of the ring kernel: d(x) is stored once
             _C.check(lib.tok_conv_dgrad2(d, ptr(dz), ptr(wa), dpp, ptr(x.data), ptr(wb), ptr(cvec), ptr(tgt), acc, bn_y, bn_mask,
@@ -670,8 +469,7 @@ def _unit3_forward(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm
                    relu: bool) -> TTensor:
     lib, st = _C.lib(), stream_ptr()
     dev = x.data.device
-    if bn.momentum is None:
-        raise NotImplementedError('BatchNorm momentum=None (cumulative average)')
+    running = running_stat_ptrs(bn)         # (refuses momentum=None before anything is launched)
     d = _pointwise_desc(x, kp)
     p = x.cp
     m = d.n * d.p * d.q
@@ -688,11 +486,9 @@ def _unit3_forward(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm
         zsum = _colsum_f32(x.data, m, p)
     mean, rstd, scale, shift = (torch.empty(kp, dtype=F32, device=dev) for _ in range(4))
     wz = torch.empty((kp, p), dtype=F32, device=dev)       # W Z: the statistics now, the weight gradient later
-    track = bn.training and bn.track_running_stats and bn.running_mean is not None
-    _C.check(lib.tok_bn_gram_finalize(ptr(zz), ptr(zsum), ptr(conv.weight), m, p, kp, ptr(bn.weight), ptr(bn.bias),
-                                      ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                                      ptr(bn.num_batches_tracked) if track else None, float(bn.momentum), float(bn.eps),
-                                      ptr(mean), ptr(rstd), ptr(scale), ptr(shift), ptr(wz), st), 'tok_bn_gram_finalize')
+    _C.check(lib.tok_bn_gram_finalize(ptr(zz), ptr(zsum), ptr(conv.weight), m, p, kp, ptr(bn.weight), ptr(bn.bias), *running,
+                                      float(bn.momentum), float(bn.eps), ptr(mean), ptr(rstd), ptr(scale), ptr(shift), ptr(wz), st),
+             'tok_bn_gram_finalize')
     out_data = torch.empty((d.n, d.p, d.q, kp), dtype=BF16, device=dev)
     training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad
                                      or (shortcut is not None and shortcut.requires_grad))
@@ -703,15 +499,9 @@ def _unit3_forward(region: Region, x: TTensor, conv: nn.Conv2d, bn: nn.BatchNorm
     out = TTensor(out_data, kp, requires_grad=bool(training))
     if training:
         node = _Unit3Node()
-        node.x, node.out, node.shortcut, node.mask, node.relu = x, out, shortcut, mask, relu
-        node.conv, node.bn, node.desc, node.pk = conv, bn, d, pk
+        node.mask, node.relu, node.conv, node.bn, node.desc, node.pk = mask, relu, conv, bn, d, pk
         node.mean, node.rstd, node.wz, node.zsum = mean, rstd, wz, zsum
-        out.node = node
-        if x.requires_grad:
-            x.uses += 1
-        if shortcut is not None and shortcut.requires_grad:
-            shortcut.uses += 1
-        region.add(node)
+        _record_conv_unit(region, node, x, out, shortcut)
     return out
 
 
@@ -729,28 +519,78 @@ STEM_POOLED_STATS = os.environ.get('TOK_STEM_POOLED_STATS', '1') != '0'   # Batc
 def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.BatchNorm2d] = None,
                 relu: bool = False, shortcut: Optional[TTensor] = None, pool: bool = False, defer_apply: bool = False,
                 act: Optional[str] = None, row_scale: Optional[torch.Tensor] = None) -> TTensor:
-    """out = act(bn(conv(x)) (+ shortcut)).  `conv` is an nn.Conv2d or nn.Linear used purely as
-    the parameter container (state_dict names stay those of the reference).
-    act=None: ReLU or no activation, as `relu` says.  act='hard_swish' / 'relu6' (BatchNorm, no shortcut / pool / defer_apply):
-    the activation is hard-swish / ReLU6 and `relu` is not looked at; the unit keeps y and no mask, its backward recomputes z
-    from y, it never becomes the fused unit 3 and its BatchNorm-backward sums are never taken by a consumer's data gradient.
-    pool=True (BatchNorm + ReLU, no shortcut): out = maxpool3x3/s2/p1(act(bn(conv(x)))) with the activated map never
-    stored (the ResNet stem when only the pooled map is consumed).
+    """out = act(bn(conv(x)) (+ shortcut)).  `conv` is an nn.Conv2d or nn.Linear used purely as the parameter container (state_dict
+    names stay those of the reference).  The keywords choose the form of the BatchNorm stage; bn_stage.py says what each form
+    launches and keeps.  Only a ReLU / identity unit can become the fused unit 3 or hand its BatchNorm-backward sums to a consumer.
+    act=None: ReLU or no activation, as `relu` says.  act='hard_swish' / 'relu6' (BatchNorm, no shortcut / pool / defer_apply): that
+    activation, and `relu` is not looked at (bn_stage.Maskless).
+    pool=True (BatchNorm + ReLU on a 4-D input, no shortcut): out = maxpool3x3/s2/p1(act(bn(conv(x)))) with the activated map never
+    stored (bn_stage.StemPool: the ResNet stem when only the pooled map is consumed).
     defer_apply=True (BatchNorm, no activation, no shortcut — the last unit of an HRNet fuse path): the apply pass is NOT run;
     the returned tensor holds the RAW convolution output and carries `.affine = (scale, shift)` for a consumer that applies
-    them itself (resample.fuse_sum_relu: the write and the read of the normalised term are one fma there).  Its backward is
-    the unit's usual one (it never reads the normalised values of a unit without activation).
-    An input in phase layout (phase_split; `bn=None` too): a 1x1 / stride-1 convolution on any phase, or a 3x3 / stride-1
-    nn.Conv2d whose dilation == padding == (x.phase, x.phase), which runs as the padding-1 convolution on x.data (descriptor
-    pad = 1; packs and every backward route are the plain ones).  The output inherits the phase; a shortcut must be in the same
-    phase layout.  A dilation that is not the tensor's phase is refused as it always was; every other layer refuses a phased
-    tensor through await_ready.
+    them itself (resample.fuse_sum_relu: the write and the read of the normalised term are one fma there).
     row_scale (stochastic depth; BatchNorm + ReLU + shortcut on a 4-D input, no pool / defer_apply / act=): an fp32 vector with one
-    factor per SAMPLE, 0 for a dropped sample and 1 / keep for a kept one: out = relu(row_scale[i] * bn(conv(x)) + shortcut) on the
-    tok_bn_droppath_* trio (csrc/bn_droppath.hip).  BatchNorm sees the un-dropped convolution output, with batch or with
-    running statistics.  The unit never becomes the fused unit 3 and never hands its BatchNorm-backward sums to a consumer's
-    data gradient.  In phase layout the phase images of a sample are contiguous, so the rows of a sample are h * w of the merged
-    map.  row_scale=None: every launch is the one it always was."""
+    factor per SAMPLE, 0 for a dropped sample and 1 / keep for a kept one: out = relu(row_scale[i] * bn(conv(x)) + shortcut)
+    (bn_stage.DropPath), BatchNorm on the un-dropped convolution output; in phase layout a sample's rows are h * w of the merged map.
+    An input in phase layout (phase_split; `bn=None` too): a 1x1 / stride-1 convolution on any phase, or a 3x3 / stride-1 nn.Conv2d
+    whose dilation == padding == (x.phase, x.phase), which runs as the padding-1 convolution on x.data (descriptor pad = 1; packs and
+    backward routes are the plain ones).  The output inherits the phase; a shortcut must be in the same phase layout."""
+    _refuse_arguments(x, bn, relu, shortcut, pool, defer_apply, act, row_scale)
+    if isinstance(conv, nn.Conv2d) and _is_grouped(conv) and bn is not None and shortcut is None and not pool and not defer_apply:
+        return gconv_bn_act(region, x, conv, bn, relu=relu, act=act)       # (anything else grouped: _check_conv refuses below)
+    act = _check_act(relu, act, bn, shortcut, pool, defer_apply)
+    relu = act == RELU
+    _await_inputs(conv, x, shortcut, pool, defer_apply)
+    lib, st = _C.lib(), stream_ptr()
+    x, r, s, stride, pad, k_real = _layer_geometry(region, conv, x, pool)
+    kp = pad8(k_real)
+    if bn is not None and bn.num_features != k_real:
+        raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {k_real}')
+    pointwise = r == 1 and s == 1 and stride == 1 and pad == 0 and x.data.dim() == 4
+    if pointwise and _unit3_eligible(x, conv, bn, act, shortcut, pool, row_scale, kp, k_real):
+        # the residual unit of a bottleneck (conv3 + bn3 + shortcut + ReLU) and its stride-1 projection shortcut (conv + bn):
+        # normalise (add, activate) in the GEMM epilogue — the wide pre-BatchNorm tensor is never stored
+        return _inherit_phase(_unit3_forward(region, x, conv, bn, shortcut, kp, relu), x)
+    d = _conv_desc(x, kp, r, s, stride, pad)
+    training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or (bn is not None and bn.weight.requires_grad))
+    pk = get_packs(conv.weight, conv.bias, kp, d.s_pad, x.cp, want_dgrad=region.grad_mode and x.requires_grad, refresh=True)
+    dev, m = x.data.device, d.n * d.p * d.q
+    y = torch.empty((d.n, d.p, d.q, kp), dtype=BF16, device=dev)
+    batch = bn is not None and batch_stats(bn)
+    stats, rows = None, 0
+    if batch:
+        rows = lib.tok_conv_fwd_stat_rows(d)
+        stats = torch.empty((2, rows, kp), dtype=F32, device=dev)
+    _C.check(lib.tok_conv_fwd(d, ptr(x.data), ptr(pk.fwd), ptr(pk.bias), ptr(y), ptr(stats), st), 'tok_conv_fwd')
+    out_data, form, mask, colsums, coeffs = y, None, None, None, (None,) * 4
+    deferred = bool(bn is not None and defer_apply and not relu and shortcut is None and not pool and x.data.dim() == 4)
+    if bn is not None:
+        coeffs = bn_coeffs(lib, st, bn, stats, rows, m, kp, dev)
+        form = choose_form(act, row_scale, pool, keep_ypool=pool and STEM_POOLED_STATS and region.grad_mode and batch,
+                           deferred=deferred, colsums=_leaves_colsums(region, r, relu, shortcut, m, kp, k_real, batch))
+        # ReLU bits for the backward pass whenever gradients are on, running statistics included: the apply kernel's
+        # mask-less fallback recomputes the pattern from y alone and would leave out a shortcut added before the activation
+        out_data, mask, colsums = form.fwd(lib, st, y, coeffs[0], coeffs[1], shortcut, relu and region.grad_mode, m, kp)
+    elif relu or shortcut is not None:
+        raise NotImplementedError('relu / shortcut without BatchNorm')
+    if x.data.dim() == 2:
+        y, out_data = y.view(d.n, kp), out_data.view(d.n, kp)
+    req = bool(training or (shortcut is not None and shortcut.requires_grad and region.grad_mode))
+    out = _inherit_phase(TTensor(out_data, k_real, requires_grad=req), x)
+    if deferred:
+        out.affine = coeffs[:2]
+    if colsums is not None:
+        out.colsum_part = colsums
+    if req:
+        node = _ConvBnActNode()
+        node.y, node.mask, node.conv, node.bn, node.desc, node.pk, node.form, node.batch_stats = y, mask, conv, bn, d, pk, form, batch
+        node.scale, node.shift, node.mean, node.rstd = coeffs
+        _record_conv_unit(region, node, x, out, shortcut, sub_capable=bool(pointwise and x.requires_grad and lib.tok_conv_dgrad_subacc_ok(d)))
+    return out
+
+
+def _refuse_arguments(x, bn, relu, shortcut, pool, defer_apply, act, row_scale):
+    """The combinations of conv_bn_act's keywords that no form serves (its docstring)."""
     if row_scale is not None:
         if pool or defer_apply or act is not None:
             raise NotImplementedError('conv_bn_act(row_scale=...): no pool, defer_apply or act= (a ReLU residual unit only)')
@@ -762,131 +602,65 @@ def conv_bn_act(region: Region, x: TTensor, conv: nn.Module, bn: Optional[nn.Bat
                              f'{row_scale.dtype} {tuple(row_scale.shape)}')
     if pool and (bn is None or not relu or shortcut is not None or x.data.dim() != 4):
         raise ValueError('conv_bn_act(pool=True): BatchNorm + ReLU on a 4-D input, no shortcut')
-    if (isinstance(conv, nn.Conv2d) and _is_grouped(conv) and bn is not None and shortcut is None and not pool
-            and not defer_apply):
-        return gconv_bn_act(region, x, conv, bn, relu=relu, act=act)       # (anything else grouped: _check_conv refuses below)
-    act = _check_act(relu, act, bn, shortcut, pool, defer_apply)
-    relu = act == RELU
-    phase = x.phase
-    if phase != 1:
-        # a dilated stage in phase layout (phase_split): pointwise layers as they are, the dilated 3x3 as the padding-1 one
-        # on the phase images; everything else is refused by await_ready (a dilation that is not the phase: by _check_conv)
-        phased = _phased_conv_ok(conv, phase) and not pool and not defer_apply and x.data.dim() == 4
-        if not phased and isinstance(conv, nn.Conv2d) and tuple(conv.dilation) != (1, 1):
-            _check_conv(conv)
-        await_ready(x, shortcut, phase_ok=phased)
-        if shortcut is not None and shortcut.phase_steps != x.phase_steps:
-            raise ValueError(f'conv_bn_act: the shortcut is in phase layout {shortcut.phase_steps or (1,)}, the unit in '
-                             f'{x.phase_steps}: bring it there with phase_split / to_phase')
-    else:
-        await_ready(x, shortcut)
-    lib, st = _C.lib(), stream_ptr()
+
+
+def _await_inputs(conv, x, shortcut, pool, defer_apply):
+    """Wait for the producers of x and of the shortcut; an input in phase layout only where the layer commutes with it."""
+    if x.phase == 1:
+        return await_ready(x, shortcut)
+    # a dilated stage in phase layout (phase_split): pointwise layers as they are, the dilated 3x3 as the padding-1 one
+    # on the phase images; everything else is refused by await_ready (a dilation that is not the phase: by _check_conv)
+    phased = _phased_conv_ok(conv, x.phase) and not pool and not defer_apply and x.data.dim() == 4
+    if not phased and isinstance(conv, nn.Conv2d) and tuple(conv.dilation) != (1, 1):
+        _check_conv(conv)
+    await_ready(x, shortcut, phase_ok=phased)
+    if shortcut is not None and shortcut.phase_steps != x.phase_steps:
+        raise ValueError(f'conv_bn_act: the shortcut is in phase layout {shortcut.phase_steps or (1,)}, the unit in '
+                         f'{x.phase_steps}: bring it there with phase_split / to_phase')
+
+
+def _layer_geometry(region, conv, x, pool):
+    """(x, r, s, stride, pad, k_real) of the convolution as it is launched."""
     if isinstance(conv, nn.Linear):
-        r = s = 1
-        stride, pad = 1, 0
-        k_real = conv.out_features
-    else:
-        _check_conv(conv, phase)
-        r, s = conv.kernel_size
-        stride, pad = conv.stride[0], conv.padding[0]
-        k_real = conv.out_channels
-        if phase != 1 and r == 3:
-            pad = 1     # dilation == padding == phase on the merged map is padding 1 on every phase image
+        return x, 1, 1, 1, 0, conv.out_features
+    _check_conv(conv, x.phase)
+    r, s = conv.kernel_size
+    stride, pad = conv.stride[0], conv.padding[0]
+    if x.phase != 1 and r == 3:
+        pad = 1     # dilation == padding == phase on the merged map is padding 1 on every phase image
     if (SUBSAMPLE_S2 and r == 1 and s == 1 and stride == 2 and pad == 0 and x.data.dim() == 4 and not pool
             and x.rows() >= SUBSAMPLE_MIN_ROWS):
         # conv1x1/stride2(x) == conv1x1(x[:, ::2, ::2]): one strided copy, then a pointwise layer in all three passes
-        x = subsample2(region, x)
-        stride = 1
-    x4 = x
-    kp = pad8(k_real)
-    if bn is not None and bn.num_features != k_real:
-        raise ValueError(f'BatchNorm num_features {bn.num_features} != conv output channels {k_real}')
-    if (FUSE_UNIT3 and bn is not None and act not in MASKLESS and (relu == (shortcut is not None)) and not pool
-            and row_scale is None and isinstance(conv, nn.Conv2d)
-            and r == 1 and s == 1 and stride == 1 and pad == 0 and conv.bias is None and x.data.dim() == 4
-            and x.c == x.cp and kp == k_real and x.cp <= 1024 and (shortcut is None or shortcut.cp == kp)
-            and x.rows() >= UNIT3_MIN_ROWS and kp >= 2 * x.cp
-            and batch_stats(bn) and conv.weight.permute(0, 2, 3, 1).is_contiguous()):
-        # the residual unit of a bottleneck (conv3 + bn3 + shortcut + ReLU) and its stride-1 projection shortcut (conv + bn):
-        # normalise (add, activate) in the GEMM epilogue — the wide pre-BatchNorm tensor is never stored
-        return _inherit_phase(_unit3_forward(region, x, conv, bn, shortcut, kp, relu), x)
-    d = _conv_desc(x4, kp, r, s, stride, pad)
-    training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or
-                                     (bn is not None and bn.weight.requires_grad))
-    pk = get_packs(conv.weight, conv.bias, kp, d.s_pad, x4.cp, want_dgrad=region.grad_mode and x.requires_grad,
-                   refresh=True)
-    dev = x.data.device
-    y = torch.empty((d.n, d.p, d.q, kp), dtype=BF16, device=dev)
-    m = d.n * d.p * d.q
-    batch = bn is not None and batch_stats(bn)
-    stats, rows = None, 0
-    if batch:
-        rows = lib.tok_conv_fwd_stat_rows(d)
-        stats = torch.empty((2, rows, kp), dtype=F32, device=dev)
-    node = _ConvBnActNode()
-    _C.check(lib.tok_conv_fwd(d, ptr(x4.data), ptr(pk.fwd), ptr(pk.bias), ptr(y), ptr(stats), st), 'tok_conv_fwd')
+        x, stride = subsample2(region, x), 1
+    return x, r, s, stride, pad, conv.out_channels
 
-    if bn is not None:
-        scale, shift, mean, rstd = bn_coeffs(lib, st, bn, stats, rows, m, kp, dev)
-        mask = cs_part = None
-        deferred = bool(defer_apply and not relu and shortcut is None and not pool and x.data.dim() == 4)
-        if deferred:
-            out_data = y
-        elif pool:
-            p2, q2 = (d.p + 2 - 3) // 2 + 1, (d.q + 2 - 3) // 2 + 1
-            out_data = torch.empty((d.n, p2, q2, kp), dtype=BF16, device=dev)
-            node.pool = torch.empty((d.n, p2, q2, kp), dtype=torch.uint8, device=dev)
-            if STEM_POOLED_STATS and region.grad_mode and batch:
-                node.ypool = torch.empty_like(out_data)
-            _C.check(lib.tok_bn_relu_maxpool_fwd(ptr(y), ptr(scale), ptr(shift), d.n, d.p, d.q, kp, ptr(out_data),
-                                                 ptr(node.pool), ptr(node.ypool), st), 'tok_bn_relu_maxpool_fwd')
-        elif (FUSE_UNIT3 and r == 3 and relu and shortcut is None and m >= UNIT3_MIN_ROWS
-              and kp == k_real and kp <= 1024 and region.grad_mode and batch):
-            # a 3x3 unit of a bottleneck feeds the fused residual unit, which wants colsum(z) of its input: the activation pass
-            # has z in registers (saves that unit a stand-alone pass over z)
-            out_data = torch.empty_like(y)
-            mask = torch.empty((m, kp // 8), dtype=torch.uint8, device=dev)
-            cs_rows = lib.tok_bn_act_fwd_colsum_rows(m, kp)
-            cs_part = torch.empty((cs_rows, kp), dtype=F32, device=dev)
-            _C.check(lib.tok_bn_act_fwd_colsum(ptr(y), ptr(scale), ptr(shift), None, 1, ptr(out_data), ptr(mask),
-                                               m, kp, ptr(cs_part), st), 'tok_bn_act_fwd_colsum')
-        else:
-            # ReLU bits for the backward pass whenever gradients are on, running statistics included: the apply kernel's
-            # mask-less fallback recomputes the pattern from y alone and would leave out a shortcut added before the activation
-            out_data, mask = bn_apply(lib, st, y, scale, shift, act, shortcut, relu and region.grad_mode, m, kp, row_scale)
-            node.row_scale = row_scale
-        node.mask = mask
-        node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
-    else:
-        if relu or shortcut is not None:
-            raise NotImplementedError('relu / shortcut without BatchNorm')
-        out_data = y
-    if x.data.dim() == 2:
-        y = y.view(d.n, kp)
-        out_data = out_data.view(d.n, kp)
 
-    req = bool(training or (shortcut is not None and shortcut.requires_grad and region.grad_mode))
-    out = _inherit_phase(TTensor(out_data, k_real, requires_grad=req), x)
-    if bn is not None and deferred:
-        out.affine = (scale, shift)
-    if bn is not None and cs_part is not None:
-        out.colsum_part = (cs_part, cs_rows)
-    if req:
-        node.x, node.out, node.shortcut, node.y = x, out, shortcut, y
-        node.conv, node.bn, node.desc, node.pk = conv, bn, d, pk
-        node.act, node.batch_stats = act, batch
-        out.node = node
-        node.sub_capable = False
-        if x.requires_grad:
-            x.uses += 1
-            if (r == 1 and s == 1 and stride == 1 and pad == 0 and x.data.dim() == 4
-                    and lib.tok_conv_dgrad_subacc_ok(d)):
-                node.sub_capable = True      # this unit's data gradient can absorb a half-resolution contribution to d(x)
-                x.sub_closers += 1
-        if shortcut is not None and shortcut.requires_grad:
-            shortcut.uses += 1
-        region.add(node)
-    return out
+def _unit3_eligible(x, conv, bn, act, shortcut, pool, row_scale, kp, k_real) -> bool:
+    """Does this pointwise layer (1x1, stride 1, no padding, 4-D input) run as the fused unit 3: BatchNorm on batch statistics
+    with ReLU exactly when there is a shortcut, on a large map whose output is at least twice as wide as its input?"""
+    return bool(FUSE_UNIT3 and bn is not None and act in (None, RELU) and ((act == RELU) == (shortcut is not None)) and not pool
+                and row_scale is None and isinstance(conv, nn.Conv2d) and conv.bias is None and x.c == x.cp and kp == k_real
+                and x.cp <= 1024 and (shortcut is None or shortcut.cp == kp) and x.rows() >= UNIT3_MIN_ROWS and kp >= 2 * x.cp
+                and batch_stats(bn) and conv.weight.permute(0, 2, 3, 1).is_contiguous())
+
+
+def _leaves_colsums(region, r, relu, shortcut, m, kp, k_real, batch) -> bool:
+    """Does the activation pass also leave column sums (a 3x3 ReLU unit of a bottleneck: the fused unit 3 wants them of its input)?"""
+    return bool(FUSE_UNIT3 and r == 3 and relu and shortcut is None and m >= UNIT3_MIN_ROWS
+                and kp == k_real and kp <= 1024 and region.grad_mode and batch)
+
+
+def _record_conv_unit(region, node, x, out, shortcut=None, sub_capable=False):
+    """Put a conv unit on the tape.  sub_capable: its data gradient can absorb a half-resolution contribution to d(x)."""
+    node.x, node.out, node.shortcut = x, out, shortcut
+    out.node = node
+    if x.requires_grad:
+        x.uses += 1
+        node.sub_capable = sub_capable
+        x.sub_closers += int(sub_capable)
+    if shortcut is not None and shortcut.requires_grad:
+        shortcut.uses += 1
+    region.add(node)
 
 
 def linear(region: Region, x: TTensor, fc: nn.Linear) -> TTensor:
@@ -1206,8 +980,8 @@ def _check_dwconv(conv: nn.Conv2d, x: TTensor):
 
 class _SameWidthConvBnActNode(_ConvBnActNode):
     """act(bn(conv(x))) for a convolution with as many output as input channels that has kernels of its own (depthwise,
-    grouped 3x3).  The BatchNorm backward is the one of _ConvBnActNode (tok_bn_bwd_*; a consumer conv's data gradient may
-    reduce its sums, see wants_fused_bwd_stats); then the family's weight and data gradient on dy.  A family states its five
+    grouped 3x3).  The BatchNorm backward is the shared one (bn_stage.bn_backward; a consumer conv's data gradient may reduce
+    its sums, see _rider_operands); then the family's weight and data gradient on dy.  A family states its five
     library calls; `geo` is (n, h, w, c, c, kernel size | groups, stride), the sizes every one of them takes."""
 
     # -- what a family provides (the weight is read, and its gradient written, as the master lies in memory) --
@@ -1241,7 +1015,7 @@ class _SameWidthConvBnActNode(_ConvBnActNode):
         geo = self.geo(conv, x)
         m, kp = self.y.numel() // self.y.shape[-1], self.y.shape[-1]
         w_need, x_need = conv.weight.requires_grad, x.requires_grad
-        dy = self._bn_bwd(lib, st, g, m, kp, w_need or x_need)
+        dy, _ = bn_backward(self, lib, st, g, m, kp, w_need or x_need)
         out.grad = None
         if dy is None:
             return
@@ -1279,17 +1053,14 @@ def _same_width_conv_bn_act(node_cls, region: Region, x: TTensor, conv: nn.Conv2
     scale, shift, mean, rstd = bn_coeffs(lib, st, bn, stats, rows, m, c, dev)
     training = region.grad_mode and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad
                                      or bn.bias.requires_grad)
-    out_data, mask = bn_apply(lib, st, y, scale, shift, act, None, act == RELU and training, m, c)
+    form = choose_form(act)
+    out_data, mask, _ = form.fwd(lib, st, y, scale, shift, None, act == RELU and training, m, c)
     out = _inherit_phase(TTensor(out_data, c, requires_grad=bool(training)), x)
     if training:
         node = node_cls()
-        node.x, node.out, node.y, node.mask = x, out, y, mask
-        node.conv, node.bn, node.act, node.batch_stats = conv, bn, act, batch
+        node.y, node.mask, node.conv, node.bn, node.form, node.batch_stats = y, mask, conv, bn, form, batch
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
-        out.node = node
-        if x.requires_grad:
-            x.uses += 1
-        region.add(node)
+        _record_conv_unit(region, node, x, out)
     return out
 
 

@@ -55,7 +55,7 @@ class _CommutedNeckNode(EF._ConvBnActNode):
         n, h, w, _ = self.y.shape
         w_need = conv.weight.requires_grad
         srcs: List[TTensor] = self.srcs
-        dy = self._bn_bwd(lib, st, g, m, kp, w_need or any(t.requires_grad for t in srcs))
+        dy, _ = EF.bn_backward(self, lib, st, g, m, kp, w_need or any(t.requires_grad for t in srcs))
         out.grad = None
         if dy is None:
             return
@@ -144,18 +144,17 @@ def upsample_concat_conv_bn_relu(region: Region, srcs: List[TTensor], size: Tupl
         low += [ptr(ys[j]), descs[j].h, descs[j].w] if j < len(ys) else [None, 1, 1]
     y = ys[0]
     _C.check(lib.tok_bilinear_sum_stats(ptr(y), *low, n, h, w, kp, ptr(y), ptr(stats), st), 'tok_bilinear_sum_stats')
-    act = EF._check_act(relu, None, bn)
     scale, shift, mean, rstd = EF.bn_coeffs(lib, st, bn, stats, rows, m, kp, dev)
-    out_data, mask = EF.bn_apply(lib, st, y, scale, shift, act, None, relu and training, m, kp)
+    form = EF.choose_form(EF._check_act(relu, None, bn))
+    out_data, mask, _ = form.fwd(lib, st, y, scale, shift, None, relu and training, m, kp)
     out = TTensor(out_data, kp, requires_grad=bool(training))
     if training:
         node = _CommutedNeckNode()
         node.x, node.out, node.shortcut, node.y = None, out, None, y
         node.conv, node.bn, node.desc, node.pk = conv, bn, descs[0], pk
-        node.act, node.batch_stats, node.mask = act, True, mask
+        node.form, node.batch_stats, node.mask = form, True, mask
         node.mean, node.rstd, node.scale, node.shift = mean, rstd, scale, shift
         node.srcs, node.descs, node.offs = list(srcs), descs, offs
-        node.sub_capable = False
         out.node = node
         for t in srcs:
             if t.requires_grad:
