@@ -147,6 +147,9 @@ int tok_conv_dgrad_bnstats(const tok_conv_desc* d, const void* dy, const void* w
  * tok_bn_gram_finalize: Z = z^T z (P x P, e.g. from tok_conv_wgrad on (z, z)), zsum = column sums of z, w = fp32 master
  *   filter [k][p] (rounded to bf16 inside, the operand the GEMM uses) -> mean / rstd / scale / shift [k] and the running
  *   statistics update of F.batch_norm (momentum, unbiased variance, num_batches_tracked += 1); count = rows of z.
+ *   Any p > 0 and k > 0 (p in {64, 128, 256}: one launch that centres the variance in fp64; any other p: a tiled fp32 product
+ *   and var = E[y^2] - mean^2 in fp64); the unit as a whole is bounded by tok_bn3_bwd_prepare's p <= 2048.  running_mean and
+ *   running_var go together (both or neither NULL), num_batches_tracked may be NULL; count = 1 takes the unbiased factor 1.
  * tok_conv_fwd_bn_apply: out = act(conv1x1(x) * scale + shift (+ shortcut)) as bf16, act = ReLU or identity (the projection
  *   shortcut conv + BatchNorm of [timm] downsample_conv), mask bit = (out > 0)  (the bits tok_bn_act_fwd writes); replaces
  *   tok_conv_fwd + tok_bn_finalize + tok_bn_act_fwd for such a unit.
@@ -157,6 +160,8 @@ int tok_conv_dgrad_bnstats(const tok_conv_desc* d, const void* dy, const void* w
  * tok_bn3_bwd_prepare: G = dz^T z [k][p], w, wz (from tok_bn_gram_finalize), zsum, the sum(dz) partial rows -> dgamma / dbeta (+= if param_accumulate),
  *   coef [3][k], dw [k][p] (+= if dw_accumulate), wa = bf16 diag(c1) W in dgrad-pack layout [p][k], wb = bf16
  *   W^T diag(c2) W [p][p], cvec = c3^T W [p]:   d(input) = dz wa + z wb + cvec  (tok_conv_dgrad + tok_conv_dgrad_bias).
+ *   p <= 2048, k % 8 == 0, wa 16-byte aligned (it is stored in 16-byte segments), dgamma / dbeta may be NULL; anything else
+ *   is refused with TOK_ERR_INVALID before a launch.
  * tok_conv_dgrad_bias: tok_conv_dgrad / tok_conv_dgrad_bnstats with a per-channel fp32 bias added to the result.          */
 int tok_bn_gram_finalize(const float* Z, const float* zsum, const float* w, int64_t count, int p, int k,
                          const float* gamma, const float* beta, float* running_mean, float* running_var,

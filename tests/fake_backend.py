@@ -332,6 +332,8 @@ class FakeTok:
 
     def tok_bn3_bwd_prepare(self, G, w, wz, zsum, partial, rows, count, p, k, gamma, mean, rstd, dgamma, dbeta, pacc, coef, dw,
                             dw_acc, wa, wb, cvec, ws, st):
+        if wa % 16:
+            return -1     # TOK_ERR_INVALID: wa is stored in 16-byte segments (unit3.hip)
         self.calls.append('bn3_bwd_prepare')
         Gm = _t(G, (k, p), torch.float32).double()
         wq = _t(w, (k, p), torch.float32).to(BF16).double()

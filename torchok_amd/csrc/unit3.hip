@@ -454,6 +454,7 @@ extern "C" int tok_bn3_bwd_prepare(const float* G, const float* w, const float* 
   TOK_CHECK_ARG(G && w && wz && zsum && partial && gamma && mean && rstd && coef && dw && wa && wb && cvec && ws,
                 "tok_bn3_bwd_prepare: null pointer");
   TOK_CHECK_ARG(rows > 0 && count > 0 && p > 0 && p <= 2048 && k > 0 && k % 8 == 0, "tok_bn3_bwd_prepare: bad sizes");
+  TOK_CHECK_ARG(((uintptr_t)wa & 15) == 0, "tok_bn3_bwd_prepare: wa must be 16-byte aligned (stored in 16-byte segments)");
   if (tok_dbg_skip(4)) return TOK_OK;
   hipStream_t st = tok_stream(stream);
   const size_t smem = (size_t)PR_CH * p * sizeof(float);
