@@ -854,8 +854,11 @@ int tok_phase_merge(const void* xs, int n, int h, int w, int c, int ld, int d, v
  *     uses the rows of image u % batch (the reference's `repeat` tiles image-minor), NOT u / nW.
  *   bias fp32 [heads][N][ldb] (tok_relpos_bias_fwd), 16-byte aligned, ldb >= N, ldb % 4 == 0; out bf16 [batch*h*w][ldo] at column
  *   head*32 + d; lse fp32 [batch*nW][heads][N], natural log, of the biased logits.
- * Served: c == heads * 32 (head_dim 32), h % ws == 0, w % ws == 0, N <= 256, pitches multiples of 8 and wide enough; anything
- * else, or a NULL qkv / bias / out / lse, is TOK_ERR_INVALID before any launch.
+ * Served: c == heads * 32 (head_dim 32), h % ws == 0, w % ws == 0, N <= 256, pitches multiples of 8 and wide enough, every
+ * bf16 tensor (qkv, q_global, out, dout, dqkv, dq_global) 16-byte aligned (rows are read in 16-byte pieces); anything else, or
+ * a NULL qkv / bias / out / lse, is TOK_ERR_INVALID before any launch.  Bias values must be finite: the online softmax takes the
+ * running maximum of a key tile to be finite, and a tile whose every bias is -inf would turn its rescale factor into NaN.  A
+ * large finite negative bias (-3e4) is the way to mask a key.
  * tok_gc_attn_bwd: P recomputed from q, k, bias and lse; delta = rowsum(dO o O) is formed as rowsum(P o dP) in fp32 (`out` is
  *   checked but not read: the stored bf16 O would put its rounding into a difference that cancels).  dqkv bf16 [batch*h*w][ldd] in the layout of qkv (global mode: dk | dv;
  *   columns past those never written); global mode: dq_global[img] bf16 [batch*N][lddg] = sum over the windows u % batch == img, in
@@ -877,7 +880,9 @@ int tok_gc_attn_bwd(const void* qkv, int ld, const void* q_global, int ldg, cons
  * tok_global_attn_fwd: per (image, head) O = softmax(Q K^T * 64^-0.5) V over all n tokens.  qkv bf16 [batch*n][ldq], columns
  *   (3, heads, 64) as timm's qkv.reshape(B, N, 3, H, 64); out bf16 [batch*n][ldo] at column h*64 + d (timm's
  *   transpose(1, 2).reshape(B, N, C)); lse fp32 [batch][heads][n] = the natural-log row log-sum-exp of the scaled logits.
- *   head_dim == 64 only, 1 <= n <= TOK_GLOBAL_ATTN_MAX_TOKENS, ldq / ldo multiples of 8 (>= 3C / C): TOK_ERR_INVALID otherwise.
+ *   head_dim == 64 only, 1 <= n <= TOK_GLOBAL_ATTN_MAX_TOKENS, batch * heads <= 65535, ldq / ldo multiples of 8 (>= 3C / C),
+ *   qkv / out (and in the backward dout / dqkv) 16-byte aligned, as rows are read in 16-byte pieces: TOK_ERR_INVALID otherwise,
+ *   with nothing launched or written.
  * tok_global_attn_bwd: dq, dk, dv into dqkv bf16 [batch*n][ldd] (the layout of qkv; columns past 3C untouched), recomputing P
  *   from qkv and lse; out / dout share the pitch ldo.  ws: tok_global_attn_bwd_ws_bytes(...) bytes (row sums of dout * out).
  *   No float atomics: bit-reproducible.                                                                                       */
@@ -889,7 +894,9 @@ int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, const void* d
                         int heads, int head_dim, void* dqkv, int ldd, void* ws, size_t ws_bytes, void* stream);
 /* The same attention with an additive bias on the scaled logits (BEiT: [timm 0.6.13] beit.Attention):
  *   O = softmax(Q K^T * 64^-0.5 + bias[h]) V.  bias fp32 [heads][n][ldb], shared by every image, 16-byte aligned, ldb >= n and
- *   ldb % 4 == 0; columns >= n of a bias row are never read as values.  lse is the log-sum-exp of the biased logits.  Every other
+ *   ldb % 4 == 0; columns >= n of a bias row are never read as values.  Bias values must be finite (the online softmax takes
+ *   the running maximum of a key tile to be finite: a tile of -inf would turn its rescale factor into NaN); a large finite
+ *   negative bias (-3e4) masks a key.  lse is the log-sum-exp of the biased logits.  Every other
  *   argument rule is that of tok_global_attn_fwd / _bwd; an all-zero bias gives their bits.
  * tok_global_attn_bias_bwd: dq / dk / dv from P recomputed with the bias, and (dbias != NULL)
  *   dbias[h][i][j] (= | += with dbias_accumulate) sum_b P_b[i][j] (dP_b[i][j] - delta_b[i]), fp32 [heads][n][ldb], columns >= n

@@ -5,10 +5,13 @@ constant logits, a zero output gradient and the argument refusals.
 Forward: element by element |out - ref| <= 2^-8 |ref| + 2^-7 (P @ |V|) (P is rounded to bf16 before the PV MFMA while the row
 sum stays fp32: about 2^-8 of P @ |V|, doubled for margin).  Backward: the worst per-token-row relative error of dq, dk and dv,
 each row measured against max(|ref row|, |magnitude row| / 4) (one bf16 rounding of the result plus one of P or dS on the
-magnitude: 2^-8 (1 + 4) < 2e-2), gated at the whole-tensor 2e-2 of test_vit_gpu.py."""
+magnitude: 2^-8 (1 + 4) < 2e-2), gated at the whole-tensor 2e-2 of test_vit_gpu.py; and, on top of the row gate, every element
+of out, lse, dq, dk and dv against the bounds derived in tests/attn_tile_ref.py (a row norm lets one wrong element of 768 pass).
+Every launch runs twice and the two runs are compared bit for bit."""
 import pytest
 import torch
 
+import attn_tile_ref as R
 from helpers import Guarded, assert_bounded, record_distance
 from test_vit_gpu import _attn
 from torchok_amd import _C
@@ -19,7 +22,7 @@ BF, F32 = torch.bfloat16, torch.float32
 HD = 64
 
 
-def _launch(qkv, b, n, heads, dout, ldq, ldo, ldd):
+def _launch_once(qkv, b, n, heads, dout, ldq, ldo, ldd):
     """forward + backward on guarded buffers (NaN input pads, sentinel output pads and guard rows)"""
     lib, st = _C.lib(), stream_ptr()
     c = heads * HD
@@ -39,27 +42,39 @@ def _launch(qkv, b, n, heads, dout, ldq, ldo, ldd):
     return og.value(), lg.value(), dg.value()
 
 
+def _launch(qkv, b, n, heads, dout, ldq, ldo, ldd):
+    """every call runs twice: tok.h promises the same bits (no float atomics, every sum in a fixed order)"""
+    first = _launch_once(qkv, b, n, heads, dout, ldq, ldo, ldd)
+    again = _launch_once(qkv, b, n, heads, dout, ldq, ldo, ldd)
+    for x, y, what in zip(first, again, ('out', 'lse', 'dqkv')):
+        assert torch.equal(x.view(torch.int32 if x.dtype == F32 else torch.int16),
+                           y.view(torch.int32 if y.dtype == F32 else torch.int16)), f'{what} differs between two runs'
+    return first
+
+
 class _Ref:
-    """fp64 forward / backward of the same bf16 inputs and the magnitude terms of every result"""
+    """fp64 forward / backward of the same bf16 inputs (tests/attn_tile_ref.py, held to torch's autograd on the CPU) with the
+    element-wise bounds derived there, and the magnitude terms of the row gate"""
 
     def __init__(self, qkv, b, n, heads, dout):
         c = heads * HD
-        x = qkv.double().requires_grad_(True)
-        q, k, v = x.reshape(b, n, 3, heads, HD).permute(2, 0, 3, 1, 4)
-        s = (q @ k.transpose(-2, -1)) * 0.125
-        p = s.softmax(-1)
-        o = p @ v
-        o.transpose(1, 2).reshape(b * n, c).backward(dout.double())
+        q, k, v = R.dense_units(qkv, b, n, heads, 3)
+        go = R.dense_units(dout, b, n, heads, 1)[0]
+        t = self.tile = R.Ref(q, k, v, go)
+        self.shape = (b, n, heads)
         with torch.no_grad():
-            go = dout.double().reshape(b, n, heads, HD).transpose(1, 2)
-            self.out = o.detach().transpose(1, 2).reshape(b * n, c)
-            self.lse = torch.logsumexp(s.detach(), -1)
-            pd, qa, ka, va, ga = p.detach(), q.detach().abs(), k.detach().abs(), v.detach().abs(), go.abs()
-            self.m_out = (pd @ va).transpose(1, 2).reshape(b * n, c)
-            m_ds = pd * (ga @ va.transpose(-2, -1) + (ga * o.detach().abs()).sum(-1, keepdim=True))
-            tok = lambda t: t.transpose(1, 2).reshape(b * n, c)        # noqa: E731
-            self.m_grad = [tok(0.125 * m_ds @ ka), tok(0.125 * m_ds.transpose(-2, -1) @ qa), tok(pd.transpose(-2, -1) @ ga)]
-            self.grad = [x.grad[:, i * c:(i + 1) * c] for i in range(3)]
+            self.out, self.lse = R.dense_rows(t.out), t.lse
+            pd, qa, ka, va, ga = t.p, q.double().abs(), k.double().abs(), v.double().abs(), go.double().abs()
+            self.m_out = R.dense_rows(pd @ va)
+            m_ds = pd * (ga @ va.transpose(-2, -1) + (ga * t.out.abs()).sum(-1, keepdim=True))
+            self.m_grad = [R.dense_rows(0.125 * m_ds @ ka), R.dense_rows(0.125 * m_ds.transpose(-2, -1) @ qa),
+                           R.dense_rows(pd.transpose(-2, -1) @ ga)]
+            self.grad = [R.dense_rows(t.dq), R.dense_rows(t.dk), R.dense_rows(t.dv)]
+        if b * heads * n * n <= 2 ** 22:
+            # torch's own autograd at the tested shape itself, where it is cheap (the long token counts rely on the CPU test)
+            auto = R.autograd(q, k, v, go)
+            for mine, want in zip((t.out, t.lse, t.dq, t.dk, t.dv), auto[:5]):
+                assert float((mine - want).abs().max()) <= 1e-11 * max(float(want.abs().max()), 1e-300)
 
 
 def _check(tag, ref, out, lse, dqkv, heads, gate=2e-2):
@@ -69,6 +84,13 @@ def _check(tag, ref, out, lse, dqkv, heads, gate=2e-2):
     assert_bounded(out, ref.out, ref.m_out, 2.0 ** -8, 2.0 ** -7, 'attn out', tag)
     lse_err = float((lse.double().view(ref.lse.shape) - ref.lse).abs().max())
     assert lse_err < 1e-3, lse_err
+    # element by element, to the bounds derived in tests/attn_tile_ref.py: lse to a few fp32 roundings of itself and of the logits
+    # that carry weight, dq / dk / dv to one bf16 rounding of the result and one of P or dS in front of its MFMA
+    b, n, _ = ref.shape
+    dq, dk, dv = R.dense_units(dqkv, b, n, heads, 3)
+    worst = ref.tile.check({'out': R.dense_units(out, b, n, heads, 1)[0], 'lse': lse.view(ref.lse.shape), 'dq': dq, 'dk': dk, 'dv': dv})
+    for k_, v_ in worst.items():
+        record_distance(tag, k_ + '_elementwise', err_over_bound=v_)
     for i, what in enumerate(('dq', 'dk', 'dv')):
         mine, want, mag = dqkv[:, i * c:(i + 1) * c].double(), ref.grad[i], ref.m_grad[i]
         # (plus 2^-24 of the largest magnitude row: a row of ~e^-120-weighted terms underflows to 0 in fp32)

@@ -202,6 +202,14 @@ int check_geo(const char* who, int ldq, int batch, int n, int heads, int head_di
   return TOK_OK;
 }
 
+// qkv, dout and (in the backward's delta pass) out are read in 16-byte pieces (ldg16): with the pitches multiples of 8 every row
+// is aligned exactly when the base is.  d(qkv) is held to the same rule as the tensor it mirrors.
+int check_aligned(const char* who, const void* qkv, const void* out, const void* dout, const void* dqkv) {
+  TOK_CHECK_ARG(tok_aligned(qkv, 16) && tok_aligned(out, 16) && tok_aligned(dout, 16) && tok_aligned(dqkv, 16),
+                "%s: qkv / out / dout / dqkv must be 16-byte aligned", who);
+  return TOK_OK;
+}
+
 int check_bias(const char* who, const float* bias, int ldb, int n) {
   TOK_CHECK_ARG(bias && ldb >= n && ldb % 4 == 0 && ((uintptr_t)bias & 15) == 0,
                 "%s: bias pointer / row pitch ldb %d (16-byte aligned, >= n, a multiple of 4)", who, ldb);
@@ -223,6 +231,7 @@ extern "C" int tok_global_attn_fwd(const void* qkv, int ldq, int batch, int n, i
   const char* who = "tok_global_attn_fwd";
   if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
   TOK_CHECK_ARG(qkv && out && lse, "%s: null pointer", who);
+  if (int rc = check_aligned(who, qkv, out, nullptr, nullptr)) return rc;
   return launch_fwd(who, qkv, ldq, nullptr, 0, batch, n, heads, out, ldo, lse, stream);
 }
 
@@ -231,6 +240,7 @@ extern "C" int tok_global_attn_bias_fwd(const void* qkv, int ldq, const float* b
   const char* who = "tok_global_attn_bias_fwd";
   if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
   TOK_CHECK_ARG(qkv && out && lse, "%s: null pointer", who);
+  if (int rc = check_aligned(who, qkv, out, nullptr, nullptr)) return rc;
   if (int rc = check_bias(who, bias, ldb, n)) return rc;
   return launch_fwd(who, qkv, ldq, bias, ldb, batch, n, heads, out, ldo, lse, stream);
 }
@@ -291,6 +301,7 @@ extern "C" int tok_global_attn_bwd(const void* qkv, int ldq, const void* out, co
   const char* who = "tok_global_attn_bwd";
   if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
   TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "%s: null pointer", who);
+  if (int rc = check_aligned(who, qkv, out, dout, dqkv)) return rc;
   TOK_CHECK_ARG(ldd >= 3 * heads * HEAD_DIM && ldd % 8 == 0, "%s: ldd %d", who, ldd);
   return launch_bwd(who, qkv, ldq, out, dout, ldo, lse, nullptr, 0, batch, n, heads, dqkv, ldd, nullptr, 0, ws, ws_bytes, stream);
 }
@@ -301,6 +312,7 @@ extern "C" int tok_global_attn_bias_bwd(const void* qkv, int ldq, const void* ou
   const char* who = "tok_global_attn_bias_bwd";
   if (int rc = check_geo(who, ldq, batch, n, heads, head_dim, ldo)) return rc;
   TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws, "%s: null pointer", who);
+  if (int rc = check_aligned(who, qkv, out, dout, dqkv)) return rc;
   if (int rc = check_bias(who, bias, ldb, n)) return rc;
   TOK_CHECK_ARG(ldd >= 3 * heads * HEAD_DIM && ldd % 8 == 0, "%s: ldd %d", who, ldd);
   return launch_bwd(who, qkv, ldq, out, dout, ldo, lse, bias, ldb, batch, n, heads, dqkv, ldd, dbias, dbias_accumulate, ws, ws_bytes,

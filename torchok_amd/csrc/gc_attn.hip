@@ -301,6 +301,9 @@ extern "C" int tok_gc_attn_fwd(const void* qkv, int ld, const void* q_global, in
   Geo g;              // by value: a stored reference to the kernel's Geo cost up to 9 % of the backward (hipcc kept it in memory early on)
   if (int rc = check_geo(who, ld, q_global != nullptr, ldg, bias, ldb, batch, h, w, c, heads, ws, ldo, &g)) return rc;
   TOK_CHECK_ARG(qkv && out && lse, "%s: null pointer", who);
+  // qkv and q_global are read in 16-byte pieces (ldg16): with the pitches multiples of 8 a row is aligned exactly when the base is
+  TOK_CHECK_ARG(tok_aligned(qkv, 16) && tok_aligned(q_global, 16) && tok_aligned(out, 16),
+                "%s: qkv / q_global / out must be 16-byte aligned", who);
   hipLaunchKernelGGL(gc_fwd_kernel, dim3(g.B * g.nW * g.heads, tok_cdiv(g.N, TL)), dim3(256), 0, tok_stream(stream),
                      (const bf16*)qkv, ld, (const bf16*)q_global, ldg, bias, ldb, g, (bf16*)out, ldo, lse);
   return launched(who, "");
@@ -327,6 +330,9 @@ extern "C" int tok_gc_attn_bwd(const void* qkv, int ld, const void* q_global, in
   TOK_CHECK_ARG(qkv && out && dout && lse && dqkv && ws_buf && (!global || dq_global), "%s: null pointer", who);
   TOK_CHECK_ARG(ldd >= (global ? 2 : 3) * c && ldd % 8 == 0 && (!global || (lddg >= c && lddg % 8 == 0)),
                 "%s: gradient row pitches ldd %d / lddg %d", who, ldd, lddg);
+  TOK_CHECK_ARG(tok_aligned(qkv, 16) && tok_aligned(q_global, 16) && tok_aligned(out, 16) && tok_aligned(dout, 16) &&
+                    tok_aligned(dqkv, 16) && tok_aligned(dq_global, 16),
+                "%s: qkv / q_global / out / dout / dqkv / dq_global must be 16-byte aligned", who);
   const size_t need = tok_gc_attn_bwd_ws_bytes(batch, h, w, heads, ws, global, dbias != nullptr);
   if (ws_bytes < need) {
     tok_set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
