@@ -592,6 +592,28 @@ int tok_window_attn_bwd_rows(int batch, int h, int w, int heads, int ws);
 int tok_window_attn_bwd(const void* qkv, const void* dout, int batch, int h, int w, int c, int heads, int ws,
                         int shift, int ld, const float* logit_scale, const float* bias, const float* mask,
                         const float* lse, void* dqkv, float* ds_scratch, float* dscale_part, void* stream);
+/* The same operation for the windows whose backward the scalar kernels cannot hold in LDS (N * 528 B > 160 KiB: ws >= 18, the
+ * 24 x 24 windows of the 384-px SwinV2 variants), on 64-token MFMA tiles with the operand formats of the N <= 64 path,
+ * except that the cosine is formed from qn = q / max(|q|, 1e-12) and kn held as bf16 pairs (value + rounding remainder;
+ * norm in fp32 from the bf16 inputs), so the logit error of that path's single-bf16 operands is absent: logit = (qn . kn) *
+ * exp(min(logit_scale[h], ln 100)) + bias[h][i][j] + mask[win][i][j], softmax in fp32, P to bf16 for P V, lse in natural-log
+ * units [B*nW*heads][N].  No atomics: reruns are bit-identical.  tok_window_attn_fwd and tok_window_attn_bwd_rows route
+ * these windows here by themselves; the backward needs a workspace and is an entry of its own (tok_window_attn_bwd refuses
+ * these windows).  tok_window_attn_tiled_ws_bytes is 0 exactly for the geometries that are NOT served here: it is the
+ * predicate callers route by.  Scratch row r of window win (R = tok_window_attn_tiled_bwd_rows = min(batch, 2) * nW rows)
+ * holds the sum over the images [r * ipr, min(batch, (r + 1) * ipr)), ipr = ceil(batch / 2).  Refused before any launch
+ * (TOK_ERR_INVALID, tok_last_error() names the argument): null pointers, qkv / out / dout / dqkv / ws_buf not 16-byte
+ * aligned, the ld rules above, logit_scale == NULL (plain mode), index ranges past 2^31; ws_bytes too small is
+ * TOK_ERR_WORKSPACE.  Pad columns of dqkv are not written.                                                                 */
+int tok_window_attn_tiled_fwd(const void* qkv, int batch, int h, int w, int c, int heads, int ws, int shift, int ld,
+                              const float* logit_scale, const float* bias, const float* mask, void* out, float* lse,
+                              void* stream);
+int tok_window_attn_tiled_bwd_rows(int batch, int h, int w, int heads, int ws);
+size_t tok_window_attn_tiled_ws_bytes(int batch, int h, int w, int heads, int ws);
+int tok_window_attn_tiled_bwd(const void* qkv, const void* dout, int batch, int h, int w, int c, int heads, int ws,
+                              int shift, int ld, const float* logit_scale, const float* bias, const float* mask,
+                              const float* lse, void* dqkv, float* ds_scratch, float* dscale_part, void* ws_buf,
+                              size_t ws_bytes, void* stream);
 /* bias[h][i][j] = 16 * sigmoid(table[index[i][j]][h]); table bf16 [T][ld] = cpb_mlp(relative_coords_table),
  * index int64 [N][N] = relative_position_index (exact gather); backward = its transpose, ordered.        */
 int tok_cpb_bias_fwd(const void* table, int ld, const int64_t* index, int heads, int n_tokens, float* bias,

@@ -154,6 +154,11 @@ PROTOTYPES = {
     'tok_window_attn_bwd_rows': (c_int, [c_int, c_int, c_int, c_int, c_int]),
     'tok_window_attn_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P,
                                     _P, _P, _P]),
+    'tok_window_attn_tiled_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    'tok_window_attn_tiled_bwd_rows': (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    'tok_window_attn_tiled_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'tok_window_attn_tiled_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, c_size_t, _P]),
     'tok_cpb_bias_fwd': (c_int, [_P, c_int, _P, c_int, c_int, _P, _P]),
     'tok_cpb_bias_bwd': (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P]),
     'tok_patch_merge': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),

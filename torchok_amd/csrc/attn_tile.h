@@ -390,4 +390,69 @@ inline int dbias_per_chunk(long long units, int n, int heads, int max_chunks) {
   return tok_cdiv(units, chunks);
 }
 
+// ---- unit-length rows: cosine attention at head_dim 32 (window_attn_tiled.hip) ------------------------------------------------
+// F.normalize (eps 1e-12) while a row is loaded, not in a pass of its own.  A row of 32 dims is held as four 16-byte pieces by
+// the lanes lane ^ {0, X, 2X, 3X}: stage_tile's four neighbouring threads (X = 1), load_rows16's g = 0..3 of one l15 (X = 16).
+// |x|^2 is the piece's fma chain, then (p0 + p1) + (p2 + p3) in both layouts, so a row gives the same bits whichever piece loads
+// it; 1 / max(|x|, 1e-12) = min(rsqrt(|x|^2), 1e12) as finish_head_row of window_attn.hip.  Returns it; a zero row stays zero.
+// The unit row leaves as a bf16 pair: v = bf16(x / |x|) and lo = bf16(x / |x| - v), what the first rounding dropped.  cos_tile
+// forms the cosine from both; every other product takes v alone.
+template <int X>
+__device__ __forceinline__ float unit_piece(bf16x8& v, bf16x8& lo) {
+  float f[8], ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    f[e] = bf2f(v[e]);
+    ss = fmaf(f[e], f[e], ss);
+  }
+  ss += __shfl_xor(ss, X, 64);
+  ss += __shfl_xor(ss, 2 * X, 64);
+  const float inv = fminf(__builtin_amdgcn_rsqf(ss), 1e12f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float u = mul_rn(f[e], inv);
+    v[e] = f2bf(u);
+    lo[e] = f2bf(sub_rn(u, bf2f(v[e])));
+  }
+  return inv;
+}
+
+// stage_tile at head_dim 32 with every row brought to unit length (all 256 threads take part in the shuffles): row-major v and
+// lo tiles and / or the transposed v tile
+template <class Rows>
+__device__ __forceinline__ void stage_tile_unit(const Rows& src, int r0, int n, bf16* rm, bf16* rm_lo, bf16* tr) {
+  constexpr int PR = HeadDim<32>::PR;
+  const int row = threadIdx.x >> 2, d0 = (threadIdx.x & 3) * 8, t = r0 + row;
+  bf16x8 v = t < n ? ldg16(src.at(t) + d0) : zero8(), lo;
+  unit_piece<1>(v, lo);
+  if (rm) *reinterpret_cast<bf16x8*>(rm + row * PR + d0) = v;
+  if (rm_lo) *reinterpret_cast<bf16x8*>(rm_lo + row * PR + d0) = lo;
+  if (tr) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tr[(d0 + j) * PT + row] = v[j];
+  }
+}
+
+// load_rows16 at head_dim 32 with every row brought to unit length; returns 1 / max(|x|, 1e-12) of the lane's token r0 + l15
+template <class Rows>
+__device__ __forceinline__ float load_rows16_unit(const Rows& src, int r0, int n, int l15, int g, bf16x8 (&f)[1], bf16x8 (&lo)[1]) {
+  const int row = r0 + l15;
+  f[0] = row < n ? ldg16(src.at(row) + 8 * g) : zero8();
+  return unit_piece<16>(f[0], lo[0]);
+}
+
+// acc = the cosines of 16 unit rows (a, alo) against the 64 unit rows of the LDS tiles (tile, tile_lo), both row-major [64][PR]:
+// lo x v + v x lo + v x v on three MFMAs per 16 x 16 block, the small terms first.  What is left out is lo x lo, 2^-18 of a cosine.
+__device__ __forceinline__ void cos_tile(const bf16x8 (&a)[1], const bf16x8 (&alo)[1], const bf16* tile, const bf16* tile_lo, int l15,
+                                         int g, f32x4 (&acc)[4]) {
+  constexpr int PR = HeadDim<32>::PR;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bf16x8 b = lds8(tile + (j * 16 + l15) * PR + 8 * g), blo = lds8(tile_lo + (j * 16 + l15) * PR + 8 * g);
+    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(alo[0], b, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], blo, acc[j], 0, 0, 0);
+    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b, acc[j], 0, 0, 0);
+  }
+}
+
 }  // namespace

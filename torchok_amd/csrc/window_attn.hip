@@ -7,27 +7,15 @@
 // Tokens are rows of a [B*H*W][C] bf16 matrix, head_dim = 32; softmax in fp32.  Deterministic: no atomics.
 // (LayerNorm, column folds, activations: layernorm.hip; the position-bias tables: transformer.hip.)
 #include "tok_common.h"
+#include "window_attn.h"
 #include <math.h>
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
 // window attention.  One wave per (image, window, head); lane = query row (rows loop for N > 64).
-struct AttnArgs {
-  int B, H, W, C, heads, ws, shift, nWx, nW, N, ld;   // ld: row pitch of qkv (>= 3C); head_dim = 32
-  int plain;   // 1: softmax(q k^T / sqrt(head_dim)) v — no cosine normalisation, logit scale, bias (DaViT, davit.py:168-207)
-};
-
-constexpr int HD = 32;
-
-__device__ __forceinline__ int64_t token_row(const AttnArgs& a, int b, int win, int t) {
-  const int wy = win / a.nWx, wx = win - wy * a.nWx;
-  const int iy = t / a.ws, ix = t - iy * a.ws;
-  int oy = wy * a.ws + iy + a.shift, ox = wx * a.ws + ix + a.shift;   // roll(-shift): rolled[i] = x[(i + shift) % H]
-  oy = oy >= a.H ? oy - a.H : oy;
-  ox = ox >= a.W ? ox - a.W : ox;
-  return ((int64_t)b * a.H + oy) * a.W + ox;
-}
+// (AttnArgs, token_row and fill_attn: window_attn.h, shared with the tiled family)
+constexpr int HD = WIN_HEAD_DIM;
 
 // loads q, k, v of one (b, window, head) into LDS as fp32, q and k L2-normalised (F.normalize eps 1e-12)
 __device__ __forceinline__ void load_qkv(const AttnArgs& a, const bf16* __restrict__ qkv, int b, int win, int h,
@@ -653,19 +641,6 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a, const bf16* __
   }
 }
 
-// nullptr when the geometry is accepted, otherwise the reason of the refusal (what tok_last_error() reports)
-const char* fill_attn(AttnArgs& a, int B, int H, int W, int C, int heads, int ws, int shift, int ld) {
-  if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || ws <= 0) return "batch, h, w, heads and ws must be positive";
-  if (C != heads * HD) return "c must be heads * 32 (head_dim 32)";
-  if (H % ws || W % ws) return "h and w must be multiples of the window";
-  if (shift < 0 || shift >= ws) return "shift must be in [0, ws)";
-  if (ld < 3 * C) return "ld must be at least 3c";
-  if (ld & 7) return "ld must be a multiple of 8";
-  a.B = B; a.H = H; a.W = W; a.C = C; a.heads = heads; a.ws = ws; a.shift = shift;
-  a.nWx = W / ws; a.nW = (H / ws) * a.nWx; a.N = ws * ws; a.ld = ld; a.plain = 0;
-  return nullptr;
-}
-
 int attn_bpw(const AttnArgs& a) {     // images per wave on the MFMA path
   const long long units = (long long)a.B * a.nW * a.heads;
   // images a workgroup walks: about 1536 workgroups per launch (three rounds of the backward's 512 resident ones), at most 16
@@ -692,6 +667,9 @@ extern "C" int tok_window_attn_fwd(const void* qkv, int batch, int h, int w, int
   a.plain = logit_scale == nullptr;
   TOK_CHECK_ARG(!a.plain || (a.N <= 64 && !mask && shift == 0),
                 "tok_window_attn_fwd: the plain mode covers unshifted windows of up to 64 tokens");
+  // the windows the scalar pair cannot hold in LDS run on 64-token tiles (window_attn_tiled.hip), which repeats these checks
+  if (attn_tiled(a))
+    return tok_window_attn_tiled_fwd(qkv, batch, h, w, c, heads, ws, shift, ld, logit_scale, bias, mask, out, lse, stream);
   if (a.N <= 64) {
     const int bpw = attn_bpw(a);
     const int groups = tok_cdiv(batch, bpw) * a.nW * heads;
@@ -712,6 +690,7 @@ extern "C" int tok_window_attn_bwd_rows(int batch, int h, int w, int heads, int 
   AttnArgs a;
   if (fill_attn(a, batch, h, w, heads * HD, heads, ws, 0, 3 * heads * HD) != nullptr) return TOK_ERR_INVALID;
   if (a.N <= 64) return tok_cdiv(batch, attn_bpw(a)) * a.nW;
+  if (attn_tiled(a)) return tok_window_attn_tiled_bwd_rows(batch, h, w, heads, ws);
   return batch * a.nW;
 }
 
@@ -736,8 +715,9 @@ extern "C" int tok_window_attn_bwd(const void* qkv, const void* dout, int batch,
     TOK_CHECK_LAUNCH("tok_window_attn_bwd(mfma)");
     return TOK_OK;
   }
-  const size_t smem = ((size_t)a.N * HD * 4 + (size_t)a.N * 4) * sizeof(float);
-  TOK_CHECK_ARG(smem <= 160 * 1024, "tok_window_attn_bwd: window %d too large", ws);
+  const size_t smem = attn_scalar_bwd_lds(a);
+  TOK_CHECK_ARG(!attn_tiled(a), "tok_window_attn_bwd: window %d too large (its backward needs a workspace: "
+                "tok_window_attn_tiled_bwd)", ws);
   tok_launch_lds<&attn_bwd_kernel>(160 * 1024, dim3(batch * a.nW * heads), dim3(64), smem, tok_stream(stream), a,
                                    (const bf16*)qkv, (const bf16*)dout, logit_scale, bias, mask, lse, (bf16*)dqkv, ds_scratch,
                                    dscale_part);

@@ -451,9 +451,21 @@ class _WindowAttnNode(Node):
         rows = lib.tok_window_attn_bwd_rows(b, h, w, heads, ws)
         scratch = torch.empty((rows, heads * n * n), dtype=F32, device=dev)
         dscale = torch.empty((rows, heads), dtype=F32, device=dev)
-        _C.check(lib.tok_window_attn_bwd(ptr(qkv.data), ptr(g), b, h, w, c, heads, ws, shift, qkv.cp,
-                                         ptr(self.logit_scale), ptr(self.bias), ptr(self.mask), ptr(self.lse), ptr(tgt),
-                                         ptr(scratch), ptr(dscale), st), 'tok_window_attn_bwd')
+        # the library routes: a workspace size above zero says the window runs on the tiled family (18 x 18 tokens and up)
+        # (a backend without the entry, the host stand-in of the CPU tests, has no tiled family: every window is the plain call's)
+        tiled_bytes = getattr(lib, 'tok_window_attn_tiled_ws_bytes', None)
+        ws_bytes = int(tiled_bytes(b, h, w, heads, ws)) if tiled_bytes is not None else 0
+        if ws_bytes:
+            wsb = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _C.check(lib.tok_window_attn_tiled_bwd(ptr(qkv.data), ptr(g), b, h, w, c, heads, ws, shift, qkv.cp,
+                                                   ptr(self.logit_scale), ptr(self.bias), ptr(self.mask), ptr(self.lse), ptr(tgt),
+                                                   ptr(scratch), ptr(dscale), ptr(wsb), ws_bytes, st), 'tok_window_attn_tiled_bwd')
+            if self.region is not None:
+                self.region.keep_until_join(wsb)
+        else:
+            _C.check(lib.tok_window_attn_bwd(ptr(qkv.data), ptr(g), b, h, w, c, heads, ws, shift, qkv.cp,
+                                             ptr(self.logit_scale), ptr(self.bias), ptr(self.mask), ptr(self.lse), ptr(tgt),
+                                             ptr(scratch), ptr(dscale), st), 'tok_window_attn_bwd')
         if qkv.cp != 3 * c:
             tgt[:, 3 * c:] = 0
         ls = self.logit_scale
