@@ -384,6 +384,15 @@ int tok_softmax_ce_smooth_bwd(const void* logits, const int64_t* target, const f
                               const float* gscale, int rows, int classes, int ld, int64_t ignore_index,
                               float label_smoothing, void* dlogits, void* stream);
 
+/* the same with torch's class weights (weight fp32 [classes]; NULL = tok_softmax_ce_fwd/_bwd): row loss = w[t] (lse - z_t),
+ * loss[0] = sum of the row losses / sum of w[t] over the valid rows, loss[1] = that sum of weights (the denominator: 'sum'
+ * reduction is loss[0] * loss[1]), dlogits = (softmax - onehot) * w[t] * gscale[0] / loss[1].                                */
+int tok_softmax_ce_weighted_fwd(const void* logits, const int64_t* target, const float* weight, int rows, int classes, int ld,
+                                int64_t ignore_index, float* lse, float* row_loss, float* loss, void* stream);
+int tok_softmax_ce_weighted_bwd(const void* logits, const int64_t* target, const float* weight, const float* lse,
+                                const float* loss, const float* gscale, int rows, int classes, int ld, int64_t ignore_index,
+                                void* dlogits, void* stream);
+
 /* Pixel-wise cross entropy ON the bilinearly upsampled logits without the upsampled tensor: SegmentationHead.forward ends in
  * F.interpolate(segm_logits, size=input.shape[2:], mode='bilinear') (models/heads/segmentation/base.py:31-41, align_corners
  * None == False) and the segmentation recipes put CrossEntropyLoss on the result (losses/__init__.py:26).  low = the
@@ -398,6 +407,17 @@ int tok_upsample_ce_fwd(const void* low, int n, int hs, int ws, int classes, int
 int tok_upsample_ce_bwd(const void* low, int n, int hs, int ws, int classes, int ld, int hd, int wd, const int64_t* target,
                         int64_t ignore_index, const float* lse, const float* loss, const float* gscale, void* dlow,
                         int accumulate, void* stream);
+/* The same for rows of up to 256 channels (ld % 8 == 0, ld <= 256; low / dlow 16-byte aligned; anything else TOK_ERR_INVALID)
+ * and with class weights (weight fp32 [classes] or NULL, the convention of tok_softmax_ce_weighted_fwd): the forward lays a
+ * row across a group of lanes and reads the taps from the tile's low-resolution footprint in LDS, the backward runs per chunk
+ * of 16 channels.  Same arithmetic as tok_upsample_ce_fwd/_bwd; without weights and at ld <= 32 the same bits.  dlow: pad
+ * channels [classes, ld) are 0 (left alone when accumulate).                                                              */
+int tok_upsample_ce_wide_serves(int classes, int ld);
+int tok_upsample_ce_wide_fwd(const void* low, int n, int hs, int ws, int classes, int ld, int hd, int wd, const int64_t* target,
+                             int64_t ignore_index, const float* weight, float* lse, float* row_loss, float* loss, void* stream);
+int tok_upsample_ce_wide_bwd(const void* low, int n, int hs, int ws, int classes, int ld, int hd, int wd, const int64_t* target,
+                             int64_t ignore_index, const float* weight, const float* lse, const float* loss, const float* gscale,
+                             void* dlow, int accumulate, void* stream);
 
 /* DiceLoss (losses/segmentation/dice.py:86-188) on bf16 logits rows [rows][ld] (pixels of the channel-last logits).
  * mode 0 'multiclass': softmax + one_hot(target int64 [rows]); mode 1 'binary': sigmoid of column 0, target float32

@@ -112,6 +112,12 @@ PROTOTYPES = {
     'tok_upsample_ce_serves': (c_int, [c_int, c_int]),
     'tok_upsample_ce_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P, _P]),
     'tok_upsample_ce_bwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P, _P, c_int, _P]),
+    'tok_softmax_ce_weighted_fwd': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int64, _P, _P, _P, _P]),
+    'tok_softmax_ce_weighted_bwd': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64, _P, _P]),
+    'tok_upsample_ce_wide_serves': (c_int, [c_int, c_int]),
+    'tok_upsample_ce_wide_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P, _P, _P]),
+    'tok_upsample_ce_wide_bwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P, _P, _P,
+                                         c_int, _P]),
     'tok_dice_rows': (c_int, [c_int64]),
     'tok_dice_fwd': (c_int, [_P, _P, c_int64, c_int, c_int, c_int, c_float, c_float, c_int, _P, c_int, _P, _P, _P, _P]),
     'tok_dice_bwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P]),

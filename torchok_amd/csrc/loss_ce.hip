@@ -10,7 +10,8 @@ namespace {
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16* __restrict__ logits,
                                                      const int64_t* __restrict__ target, int rows,
                                                      int classes, int ld, int64_t ignore_index, float smooth,
-                                                     float* __restrict__ lse, float* __restrict__ row_loss) {
+                                                     const float* __restrict__ weight, float* __restrict__ lse,
+                                                     float* __restrict__ row_loss) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -30,6 +31,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16* __restrict__ lo
     if (ce_row_valid(t, ignore_index, classes)) {
       rl = l - bf2f(z[t]);
       if (smooth != 0.f) rl = (1.f - smooth) * rl + smooth * (l - zs / (float)classes);
+      if (weight) rl *= weight[t];
     }
     row_loss[row] = rl;
   }
@@ -40,7 +42,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16* __restrict__ lo
 __global__ __launch_bounds__(256) void ce_fwd_small_kernel(const bf16* __restrict__ logits,
                                                            const int64_t* __restrict__ target, int rows, int classes,
                                                            int ld, int64_t ignore_index, float smooth,
-                                                           float* __restrict__ lse, float* __restrict__ row_loss) {
+                                                           const float* __restrict__ weight, float* __restrict__ lse,
+                                                           float* __restrict__ row_loss) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
   const bf16* z = logits + (size_t)row * ld;
@@ -75,6 +78,7 @@ __global__ __launch_bounds__(256) void ce_fwd_small_kernel(const bf16* __restric
       for (int c = 0; c < 64; ++c) zs += (c < classes) ? v[c] : 0.f;
       rl = (1.f - smooth) * rl + smooth * (l - zs / (float)classes);
     }
+    if (weight) rl *= weight[t];
   }
   row_loss[row] = rl;
 }
@@ -83,12 +87,13 @@ __global__ __launch_bounds__(256) void ce_bwd_small_kernel(const bf16* __restric
                                                            const int64_t* __restrict__ target,
                                                            const float* __restrict__ lse, const float* __restrict__ loss,
                                                            const float* __restrict__ gscale, int rows, int classes, int ld,
-                                                           int64_t ignore_index, float smooth, bf16* __restrict__ dlogits) {
+                                                           int64_t ignore_index, float smooth,
+                                                           const float* __restrict__ weight, bf16* __restrict__ dlogits) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
   const int64_t t = target[row];
   const bool valid = ce_row_valid(t, ignore_index, classes);
-  const float g = valid ? (gscale ? gscale[0] : 1.f) / loss[1] : 0.f;
+  const float g = valid ? ce_row_scale((gscale ? gscale[0] : 1.f) / loss[1], weight, t) : 0.f;
   const float l = lse[row];
   const bf16* z = logits + (size_t)row * ld;
   bf16* d = dlogits + (size_t)row * ld;
@@ -116,13 +121,13 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16* __restrict__ lo
                                                      const float* __restrict__ loss,
                                                      const float* __restrict__ gscale, int rows, int classes,
                                                      int ld, int64_t ignore_index, float smooth,
-                                                     bf16* __restrict__ dlogits) {
+                                                     const float* __restrict__ weight, bf16* __restrict__ dlogits) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int64_t t = target[row];
   const bool valid = ce_row_valid(t, ignore_index, classes);
-  const float g = valid ? (gscale ? gscale[0] : 1.f) / loss[1] : 0.f;
+  const float g = valid ? ce_row_scale((gscale ? gscale[0] : 1.f) / loss[1], weight, t) : 0.f;
   const float l = lse[row];
   const bf16* z = logits + (size_t)row * ld;
   bf16* d = dlogits + (size_t)row * ld;
@@ -138,49 +143,71 @@ inline bool ce_small(const void* logits, int rows, int ld) {
   return ld <= 64 && (ld & 7) == 0 && rows >= 16384 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
 }
 
-}  // namespace
-
-extern "C" int tok_softmax_ce_smooth_fwd(const void* logits, const int64_t* target, int rows, int classes, int ld,
-                                         int64_t ignore_index, float label_smoothing, float* lse, float* row_loss,
-                                         float* loss, void* stream) {
+// the forward and the backward behind the three entry pairs: plain, label smoothing (weight null), class weights (smooth 0)
+int ce_fwd_launch(const void* logits, const int64_t* target, int rows, int classes, int ld, int64_t ignore_index, float smooth,
+                  const float* weight, float* lse, float* row_loss, float* loss, void* stream) {
   TOK_CHECK_ARG(logits && target && lse && row_loss && loss, "tok_softmax_ce_fwd: null pointer");
   TOK_CHECK_ARG(rows > 0 && classes > 0 && ld >= classes, "tok_softmax_ce_fwd: bad sizes");
-  TOK_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "tok_softmax_ce_fwd: label_smoothing outside [0, 1]");
+  TOK_CHECK_ARG(smooth >= 0.f && smooth <= 1.f, "tok_softmax_ce_fwd: label_smoothing outside [0, 1]");
   hipStream_t st = tok_stream(stream);
   if (ce_small(logits, rows, ld))
     hipLaunchKernelGGL(ce_fwd_small_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, (const bf16*)logits, target, rows,
-                       classes, ld, ignore_index, label_smoothing, lse, row_loss);
+                       classes, ld, ignore_index, smooth, weight, lse, row_loss);
   else
     hipLaunchKernelGGL(ce_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, (const bf16*)logits, target, rows,
-                       classes, ld, ignore_index, label_smoothing, lse, row_loss);
+                       classes, ld, ignore_index, smooth, weight, lse, row_loss);
   TOK_CHECK_LAUNCH("tok_softmax_ce_fwd");
-  return ce_mean_launch("tok_softmax_ce_fwd", row_loss, target, rows, ignore_index, classes, loss, st);
+  return ce_mean_launch("tok_softmax_ce_fwd", row_loss, target, rows, ignore_index, classes, loss, st, weight);
 }
 
-extern "C" int tok_softmax_ce_fwd(const void* logits, const int64_t* target, int rows, int classes, int ld,
-                                  int64_t ignore_index, float* lse, float* row_loss, float* loss, void* stream) {
-  return tok_softmax_ce_smooth_fwd(logits, target, rows, classes, ld, ignore_index, 0.f, lse, row_loss, loss, stream);
-}
-
-extern "C" int tok_softmax_ce_smooth_bwd(const void* logits, const int64_t* target, const float* lse,
-                                         const float* loss, const float* gscale, int rows, int classes, int ld,
-                                         int64_t ignore_index, float label_smoothing, void* dlogits, void* stream) {
+int ce_bwd_launch(const void* logits, const int64_t* target, const float* lse, const float* loss, const float* gscale, int rows,
+                  int classes, int ld, int64_t ignore_index, float smooth, const float* weight, void* dlogits, void* stream) {
   TOK_CHECK_ARG(logits && target && lse && loss && dlogits, "tok_softmax_ce_bwd: null pointer");
   TOK_CHECK_ARG(rows > 0 && classes > 0 && ld >= classes, "tok_softmax_ce_bwd: bad sizes");
   if (ce_small(logits, rows, ld) && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0)
     hipLaunchKernelGGL(ce_bwd_small_kernel, dim3((rows + 255) / 256), dim3(256), 0, tok_stream(stream),
-                       (const bf16*)logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, label_smoothing,
+                       (const bf16*)logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, smooth, weight,
                        (bf16*)dlogits);
   else
     hipLaunchKernelGGL(ce_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, tok_stream(stream),
-                       (const bf16*)logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, label_smoothing,
+                       (const bf16*)logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, smooth, weight,
                        (bf16*)dlogits);
   TOK_CHECK_LAUNCH("tok_softmax_ce_bwd");
   return TOK_OK;
 }
 
+}  // namespace
+
+extern "C" int tok_softmax_ce_smooth_fwd(const void* logits, const int64_t* target, int rows, int classes, int ld,
+                                         int64_t ignore_index, float label_smoothing, float* lse, float* row_loss,
+                                         float* loss, void* stream) {
+  return ce_fwd_launch(logits, target, rows, classes, ld, ignore_index, label_smoothing, nullptr, lse, row_loss, loss, stream);
+}
+
+extern "C" int tok_softmax_ce_fwd(const void* logits, const int64_t* target, int rows, int classes, int ld,
+                                  int64_t ignore_index, float* lse, float* row_loss, float* loss, void* stream) {
+  return ce_fwd_launch(logits, target, rows, classes, ld, ignore_index, 0.f, nullptr, lse, row_loss, loss, stream);
+}
+
+extern "C" int tok_softmax_ce_weighted_fwd(const void* logits, const int64_t* target, const float* weight, int rows, int classes,
+                                           int ld, int64_t ignore_index, float* lse, float* row_loss, float* loss, void* stream) {
+  return ce_fwd_launch(logits, target, rows, classes, ld, ignore_index, 0.f, weight, lse, row_loss, loss, stream);
+}
+
+extern "C" int tok_softmax_ce_smooth_bwd(const void* logits, const int64_t* target, const float* lse,
+                                         const float* loss, const float* gscale, int rows, int classes, int ld,
+                                         int64_t ignore_index, float label_smoothing, void* dlogits, void* stream) {
+  return ce_bwd_launch(logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, label_smoothing, nullptr, dlogits, stream);
+}
+
 extern "C" int tok_softmax_ce_bwd(const void* logits, const int64_t* target, const float* lse,
                                   const float* loss, const float* gscale, int rows, int classes, int ld,
                                   int64_t ignore_index, void* dlogits, void* stream) {
-  return tok_softmax_ce_smooth_bwd(logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, 0.f, dlogits, stream);
+  return ce_bwd_launch(logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, 0.f, nullptr, dlogits, stream);
+}
+
+extern "C" int tok_softmax_ce_weighted_bwd(const void* logits, const int64_t* target, const float* weight, const float* lse,
+                                           const float* loss, const float* gscale, int rows, int classes, int ld,
+                                           int64_t ignore_index, void* dlogits, void* stream) {
+  return ce_bwd_launch(logits, target, lse, loss, gscale, rows, classes, ld, ignore_index, 0.f, weight, dlogits, stream);
 }

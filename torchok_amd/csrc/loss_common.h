@@ -19,6 +19,10 @@ __device__ __forceinline__ bool ce_row_valid(int64_t t, int64_t ignore_index, in
   return t != ignore_index && t >= 0 && t < (int64_t)classes;
 }
 
+// What the backward multiplies (softmax - onehot) of a VALID row with label t by: g = gscale / loss[1], times w[t] under class
+// weights (loss[1] is then the sum of the weights of the valid rows).
+__device__ __forceinline__ float ce_row_scale(float g, const float* weight, int64_t t) { return weight ? g * weight[t] : g; }
+
 constexpr int CE_PARTS = (TOK_CE_LOSS_FLOATS - 2) / 4;   // (sum, count) doubles
 
 __device__ __forceinline__ void block_reduce2(double& s, double& c) {
@@ -41,15 +45,17 @@ inline int fold_parts(int64_t n, int per_part) {
   return (int)(want < CE_PARTS ? want : CE_PARTS);
 }
 
+// `weight` (class weights, or null): the second accumulator adds w[target] instead of 1, in the same order
 __global__ __launch_bounds__(256) void ce_partial_kernel(const float* __restrict__ row_loss,
                                                          const int64_t* __restrict__ target, int rows,
                                                          int64_t ignore_index, int classes, int chunk,
-                                                         double* __restrict__ part) {
+                                                         const float* __restrict__ weight, double* __restrict__ part) {
   const int r0 = blockIdx.x * chunk;
   const int r1 = min(rows, r0 + chunk);
   double s = 0.0, cnt = 0.0;
   for (int r = r0 + threadIdx.x; r < r1; r += 256) {
-    if (ce_row_valid(target[r], ignore_index, classes)) { s += (double)row_loss[r]; cnt += 1.0; }
+    const int64_t t = target[r];
+    if (ce_row_valid(t, ignore_index, classes)) { s += (double)row_loss[r]; cnt += weight ? (double)weight[t] : 1.0; }
   }
   block_reduce2(s, cnt);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = s; part[2 * blockIdx.x + 1] = cnt; }
@@ -67,13 +73,14 @@ __global__ __launch_bounds__(256) void ce_mean_kernel(const double* __restrict__
 
 // loss[0] = mean of row_loss over the valid rows, loss[1] = their count; 4096 rows per part, the parts in loss[2 ...]
 // (loss holds TOK_CE_LOSS_FLOATS floats, 8-byte aligned).  The tail of tok_softmax_ce_fwd and tok_upsample_ce_fwd (`who`).
+// With class weights (row_loss already carries w[target]): loss[0] = sum row_loss / sum w[target], loss[1] = sum w[target].
 inline int ce_mean_launch(const char* who, const float* row_loss, const int64_t* target, int rows, int64_t ignore_index, int classes,
-                          float* loss, hipStream_t st) {
+                          float* loss, hipStream_t st, const float* weight = nullptr) {
   TOK_CHECK_ARG((reinterpret_cast<uintptr_t>(loss) & 7) == 0, "%s: loss must be 8-byte aligned", who);
   double* part = reinterpret_cast<double*>(loss + 2);
   const int nparts = fold_parts(rows, 4096);
   hipLaunchKernelGGL(ce_partial_kernel, dim3(nparts), dim3(256), 0, st, row_loss, target, rows, ignore_index, classes,
-                     tok_cdiv(rows, nparts), part);
+                     tok_cdiv(rows, nparts), weight, part);
   TOK_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(256), 0, st, part, nparts, loss);
   TOK_CHECK_LAUNCH(who);

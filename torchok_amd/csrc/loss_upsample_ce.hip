@@ -21,7 +21,22 @@ struct UpArgs {
   float sh, sw;     // in / out
 };
 
-// interpolated, bf16-rounded logits of full-resolution pixel (b, y, x): v[0 .. 8 NV)
+// eight interpolated logits from the four corners' vectors, rounded to bf16 as tok_bilinear_fwd stores them: the ONE text of
+// the blend hy (hx a + lx b) + ly (hx c + lx d) for the narrow and the wide kernels, with every rounding written out.  Left to
+// the compiler, the contraction into fused multiply-adds differs from kernel to kernel (the packed form of the wide forward
+// fused the other product of some elements), and at dyadic weights the bf16 rounding behind it sits on ties: the wide entries
+// would not give the narrow entries' bits.  The form below is the one hipcc chose for the narrow kernels.
+__device__ __forceinline__ void up_blend8(float hy, float ly, float hx, float lx, bf16x8 v00, bf16x8 v01, bf16x8 v10, bf16x8 v11,
+                                          float* v) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float u = fmaf(lx, bf2f(v01[e]), hx * bf2f(v00[e])), w = fmaf(lx, bf2f(v11[e]), hx * bf2f(v10[e]));
+    v[e] = bf2f(f2bf(fmaf(hy, u, ly * w)));
+  }
+}
+
+// interpolated, bf16-rounded logits of full-resolution pixel (b, y, x): v[0 .. 8 NV), from channel 0 of `low` on (a chunk of the
+// wide backward hands in low + its first channel)
 template <int NV>
 __device__ __forceinline__ void up_logits(const bf16* __restrict__ low, const UpArgs& a, int b, int y, int x, float* v) {
   int y0, y1, x0, x1;
@@ -36,10 +51,7 @@ __device__ __forceinline__ void up_logits(const bf16* __restrict__ low, const Up
   const bf16* p11 = base + ((size_t)y1 * a.ws + x1) * a.ld;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    const bf16x8 v00 = ldg16(p00 + i * 8), v01 = ldg16(p01 + i * 8), v10 = ldg16(p10 + i * 8), v11 = ldg16(p11 + i * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      v[i * 8 + e] = bf2f(f2bf(hy * (hx * bf2f(v00[e]) + lx * bf2f(v01[e])) + ly * (hx * bf2f(v10[e]) + lx * bf2f(v11[e]))));
+    up_blend8(hy, ly, hx, lx, ldg16(p00 + i * 8), ldg16(p01 + i * 8), ldg16(p10 + i * 8), ldg16(p11 + i * 8), v + i * 8);
   }
 }
 
@@ -73,13 +85,15 @@ __global__ __launch_bounds__(256) void upce_fwd_kernel(const bf16* __restrict__ 
   }
 }
 
+// The gather backward of channels [c0, c0 + 8 NV) (the narrow kernel: the whole row, c0 = 0, no weights; the wide one: one chunk
+// per blockIdx.y).  d(upsampled logits) of a pixel with label t carries w[t] under class weights (ce_row_scale).
 template <int NV>
-__global__ __launch_bounds__(256) void upce_bwd_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target, UpArgs a,
-                                                       int64_t ignore_index, const float* __restrict__ lse,
-                                                       const float* __restrict__ loss, const float* __restrict__ gscale,
-                                                       bf16* dlow, int accumulate) {
+__device__ __forceinline__ void upce_bwd_gather(const bf16* __restrict__ low, const int64_t* __restrict__ target, const UpArgs& a,
+                                                int64_t ignore_index, const float* __restrict__ weight,
+                                                const float* __restrict__ lse, const float* __restrict__ loss,
+                                                const float* __restrict__ gscale, bf16* dlow, int accumulate, int c0) {
   const size_t total = (size_t)a.n * a.hs * a.ws;
-  const float g = (gscale ? gscale[0] : 1.f) / loss[1];
+  const float g0 = (gscale ? gscale[0] : 1.f) / loss[1];
   for (size_t pix = (size_t)blockIdx.x * 256 + threadIdx.x; pix < total; pix += (size_t)gridDim.x * 256) {
     int xs, ys, b;
     split_pixel(pix, a.ws, a.hs, xs, ys, b);
@@ -91,18 +105,27 @@ __global__ __launch_bounds__(256) void upce_bwd_kernel(const bf16* __restrict__ 
       const int64_t t = target[dp];
       if (!ce_row_valid(t, ignore_index, a.classes)) return;
       float v[8 * NV];
-      up_logits<NV>(low, a, b, yd, xd, v);
+      up_logits<NV>(low + c0, a, b, yd, xd, v);
       const float l = lse[dp];
+      const float g = ce_row_scale(g0, weight, t);
 #pragma unroll
       for (int c = 0; c < 8 * NV; ++c) {
         // d(upsampled logits), rounded to bf16 as the unfused tok_softmax_ce_bwd stores it
-        const float w = c < a.classes ? bf2f(f2bf((__expf(v[c] - l) - (c == (int)t ? 1.f : 0.f)) * g)) : 0.f;
+        const float w = c0 + c < a.classes ? bf2f(f2bf((__expf(v[c] - l) - (c0 + c == (int)t ? 1.f : 0.f)) * g)) : 0.f;
         acc[c >> 3][c & 7] = fmaf(wgt, w, acc[c >> 3][c & 7]);
       }
     });
 #pragma unroll
-    for (int i = 0; i < NV; ++i) store_acc<8>(dlow + pix * a.ld + i * 8, acc[i], accumulate);
+    for (int i = 0; i < NV; ++i) store_acc<8>(dlow + pix * a.ld + c0 + i * 8, acc[i], accumulate);
   }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void upce_bwd_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target, UpArgs a,
+                                                       int64_t ignore_index, const float* __restrict__ lse,
+                                                       const float* __restrict__ loss, const float* __restrict__ gscale,
+                                                       bf16* dlow, int accumulate) {
+  upce_bwd_gather<NV>(low, target, a, ignore_index, nullptr, lse, loss, gscale, dlow, accumulate, 0);
 }
 
 // The same adjoint with every full-resolution pixel evaluated ONCE per block instead of once per low-resolution pixel it
@@ -112,11 +135,13 @@ __global__ __launch_bounds__(256) void upce_bwd_kernel(const bf16* __restrict__ 
 // arithmetic, reading LDS (phase 2).  Window = the union of the per-pixel windows of the gather kernel, at most UWIN x UWIN.
 constexpr int UT = 8, UWIN = 40, UPP = 12;     // tile edge, window edge, window of ONE source pixel (2 r + 4 at r <= 4)
 
+// (channels [c0, c0 + 8 NV) and the class weights as in upce_bwd_gather)
 template <int NV>
-__global__ __launch_bounds__(256) void upce_bwd_tiled_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target,
-                                                             UpArgs a, int64_t ignore_index, const float* __restrict__ lse,
-                                                             const float* __restrict__ loss, const float* __restrict__ gscale,
-                                                             bf16* dlow, int accumulate, int tiles_y, int tiles_x) {
+__device__ __forceinline__ void upce_bwd_tiled(const bf16* __restrict__ low, const int64_t* __restrict__ target, const UpArgs& a,
+                                               int64_t ignore_index, const float* __restrict__ weight,
+                                               const float* __restrict__ lse, const float* __restrict__ loss,
+                                               const float* __restrict__ gscale, bf16* dlow, int accumulate, int tiles_y,
+                                               int tiles_x, int c0) {
   extern __shared__ __attribute__((aligned(16))) char up_smem[];
   bf16* win = reinterpret_cast<bf16*>(up_smem);                 // [wh][ww][8 NV]
   const int tile = blockIdx.x;
@@ -133,7 +158,7 @@ __global__ __launch_bounds__(256) void upce_bwd_tiled_kernel(const bf16* __restr
   adj_window(rw, xs0, a.wd, wx0, tmp1);
   adj_window(rw, xs1, a.wd, tmp0, wx1);
   const int wh = wy1 - wy0 + 1, ww = wx1 - wx0 + 1;             // <= UWIN (checked by the launcher for the scale)
-  const float g = (gscale ? gscale[0] : 1.f) / loss[1];
+  const float g0 = (gscale ? gscale[0] : 1.f) / loss[1];
   // ---- phase 1: bf16(d upsampled logits) of the window ----------------------------------------------------------------------
   for (int i = threadIdx.x; i < wh * ww; i += 256) {
     const int yd = wy0 + i / ww, xd = wx0 + i % ww;
@@ -146,15 +171,16 @@ __global__ __launch_bounds__(256) void upce_bwd_tiled_kernel(const bf16* __restr
       continue;
     }
     float v[8 * NV];
-    up_logits<NV>(low, a, b, yd, xd, v);
+    up_logits<NV>(low + c0, a, b, yd, xd, v);
     const float l = lse[dp];
+    const float g = ce_row_scale(g0, weight, t);
 #pragma unroll
     for (int v8 = 0; v8 < NV; ++v8) {
       bf16x8 q;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int c = v8 * 8 + e;
-        q[e] = f2bf(c < a.classes ? (__expf(v[c] - l) - (c == (int)t ? 1.f : 0.f)) * g : 0.f);
+        q[e] = f2bf(c0 + c < a.classes ? (__expf(v[c] - l) - (c0 + c == (int)t ? 1.f : 0.f)) * g : 0.f);
       }
       *reinterpret_cast<bf16x8*>(o + v8 * 8) = q;
     }
@@ -194,8 +220,157 @@ __global__ __launch_bounds__(256) void upce_bwd_tiled_kernel(const bf16* __restr
         for (int e = 0; e < 8; ++e) acc[e] = fmaf(wgt, bf2f(q[e]), acc[e]);
       }
     }
-    store_acc<8>(dlow + (((size_t)b * a.hs + ys) * a.ws + xs) * a.ld + v8 * 8, acc, accumulate);
+    store_acc<8>(dlow + (((size_t)b * a.hs + ys) * a.ws + xs) * a.ld + c0 + v8 * 8, acc, accumulate);
   }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void upce_bwd_tiled_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target,
+                                                             UpArgs a, int64_t ignore_index, const float* __restrict__ lse,
+                                                             const float* __restrict__ loss, const float* __restrict__ gscale,
+                                                             bf16* dlow, int accumulate, int tiles_y, int tiles_x) {
+  upce_bwd_tiled<NV>(low, target, a, ignore_index, nullptr, lse, loss, gscale, dlow, accumulate, tiles_y, tiles_x, 0);
+}
+
+// ---- rows of up to 256 classes (tok_upsample_ce_wide_*) ---------------------------------------------------------------------------
+// A row of 33 .. 256 classes does not fit one thread's registers, so the forward lays the classes ACROSS lanes: a group of G lanes
+// (G = the power of two >= ld / 8, at most 32) owns one full-resolution pixel, lane j holds the 16-byte vector of classes
+// [8 j, 8 j + 8); maximum, sum of exponentials and the target's logit are folded over the group with shuffles, and a wavefront
+// works on 64 / G pixels at once.  A block owns a WT x WT tile of destination pixels and stages the tile's low-resolution
+// footprint in LDS with 16-byte loads (STAGE; at scale 4 about 7 x 7 source pixels, 25 KB at ld = 256), so the four taps of every
+// pixel are LDS reads instead of four global gathers.  Where the footprint does not fit (downsampling, identity at wide rows) the
+// taps come from global memory.  Blend, rounding, __expf / __logf and the validity rule are the narrow kernel's; so is the order of
+// the sum inside every block of 32 classes (group_sum), which makes unweighted results at ld <= 32 the narrow kernel's bits.
+constexpr int WT = 16;
+constexpr int WIDE_LDS = 64 * 1024;
+
+// Sum of the group's exponentials.  Inside a block of 32 classes the four lanes hand a running sum on, lane 0 first, each adding
+// its eight values in class order: the narrow kernel's sequential sum.  The blocks of 32 are folded by a butterfly.
+template <int G>
+__device__ __forceinline__ float group_sum(const float (&ex)[8], int j) {
+  constexpr int Q = G < 4 ? G : 4;
+  float run = 0.f;
+#pragma unroll
+  for (int step = 0; step < Q; ++step) {
+    const float prev = step ? __shfl_up(run, 1, Q) : 0.f;
+    if ((j & (Q - 1)) == step) {
+      float s = prev;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s += ex[e];
+      run = s;
+    }
+  }
+  float s = __shfl(run, Q - 1, Q);
+#pragma unroll
+  for (int off = Q; off < G; off <<= 1) s += __shfl_xor(s, off, G);
+  return s;
+}
+
+template <int G, bool STAGE>
+__global__ __launch_bounds__(256) void upce_wide_fwd_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target,
+                                                            UpArgs a, int64_t ignore_index, const float* __restrict__ weight,
+                                                            float* __restrict__ lse, float* __restrict__ row_loss, int tiles_y,
+                                                            int tiles_x) {
+  extern __shared__ __attribute__((aligned(16))) char up_smem[];
+  const int tile = blockIdx.x;
+  const int tx = tile % tiles_x;
+  const int t2 = tile / tiles_x;
+  const int ty = t2 % tiles_y;
+  const int b = t2 / tiles_y;
+  const int yt0 = ty * WT, xt0 = tx * WT;
+  const int yt1 = min(a.hd, yt0 + WT) - 1, xt1 = min(a.wd, xt0 + WT) - 1;
+  // taps are read at src[((y - sy0) * fw + (x - sx0)) * ld]: the image in global memory, or the footprint [fh][fw][ld] in LDS
+  const bf16* src = low + (size_t)b * a.hs * a.ws * a.ld;
+  int sy0 = 0, sx0 = 0, fw = a.ws;
+  if constexpr (STAGE) {
+    // src_index is monotone in the destination index: the footprint runs from the first pixel's i0 to the last pixel's i1
+    int sy1, sx1, tmp;
+    float l;
+    src_index(a.sh, yt0, a.hs, sy0, tmp, l);
+    src_index(a.sh, yt1, a.hs, tmp, sy1, l);
+    src_index(a.sw, xt0, a.ws, sx0, tmp, l);
+    src_index(a.sw, xt1, a.ws, tmp, sx1, l);
+    fw = sx1 - sx0 + 1;
+    bf16* win = reinterpret_cast<bf16*>(up_smem);
+    const int nv = a.ld >> 3;
+    for (int i = threadIdx.x; i < (sy1 - sy0 + 1) * fw * nv; i += 256) {
+      const int p = i / nv, v8 = i - p * nv;
+      const int fy = p / fw, fx = p - fy * fw;
+      *reinterpret_cast<bf16x8*>(win + (size_t)p * a.ld + v8 * 8) = ldg16(src + ((size_t)(sy0 + fy) * a.ws + sx0 + fx) * a.ld + v8 * 8);
+    }
+    __syncthreads();
+    src = win;
+  }
+  const int j = threadIdx.x & (G - 1);
+  const bool lane_on = j * 8 < a.ld;                             // (idle lanes of a group: ld / 8 is no power of two)
+  for (int p = threadIdx.x / G; p < WT * WT; p += 256 / G) {
+    // every lane of a group stays in the loop for the shuffles: a pixel outside a partial tile is computed at the tile's
+    // edge and not stored
+    const int yy = yt0 + p / WT, xx = xt0 + p % WT;
+    const int y = min(yy, yt1), x = min(xx, xt1);
+    float v[8] = {};
+    if (lane_on) {
+      int y0, y1, x0, x1;
+      float ly, lx;
+      src_index(a.sh, y, a.hs, y0, y1, ly);
+      src_index(a.sw, x, a.ws, x0, x1, lx);
+      const bf16* r0 = src + (size_t)(y0 - sy0) * fw * a.ld + j * 8;
+      const bf16* r1 = src + (size_t)(y1 - sy0) * fw * a.ld + j * 8;
+      const int o0 = (x0 - sx0) * a.ld, o1 = (x1 - sx0) * a.ld;
+      up_blend8(1.f - ly, ly, 1.f - lx, lx, ldg16(r0 + o0), ldg16(r0 + o1), ldg16(r1 + o0), ldg16(r1 + o1), v);
+    }
+    // classes beyond the row (the tail of the last vector, idle lanes) are -inf: never a maximum, exponential 0
+    float mx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      v[e] = (lane_on && j * 8 + e < a.classes) ? v[e] : -INFINITY;
+      mx = fmaxf(mx, v[e]);
+    }
+#pragma unroll
+    for (int off = 1; off < G; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off, G));
+    float ex[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ex[e] = (j * 8 + e < a.classes) ? __expf(v[e] - mx) : 0.f;
+    const float l = mx + __logf(group_sum<G>(ex, j));
+    const size_t pix = ((size_t)b * a.hd + y) * a.wd + x;
+    const int64_t t = target[pix];
+    const bool valid = ce_row_valid(t, ignore_index, a.classes);
+    // the target's logit sits in lane t / 8
+    float mine = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mine = (e == ((int)t & 7)) ? v[e] : mine;
+    const float zt = __shfl(mine, valid ? (int)t >> 3 : 0, G);
+    if (j == 0 && yy <= yt1 && xx <= xt1) {
+      lse[pix] = l;
+      float rl = 0.f;
+      if (valid) {
+        rl = l - zt;
+        if (weight) rl *= weight[t];
+      }
+      row_loss[pix] = rl;
+    }
+  }
+}
+
+// The backward needs no fold over the classes (softmax = exp(v - lse) of the saved lse), so it separates by channel: the narrow
+// kernels' window-and-walk bodies on a grid of (tile or pixel block) x (chunk of 8 NV channels), blockIdx.y the chunk behind `c_base`.
+template <int NV>
+__global__ __launch_bounds__(256) void upce_wide_bwd_tiled_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target,
+                                                                  UpArgs a, int64_t ignore_index, const float* __restrict__ weight,
+                                                                  const float* __restrict__ lse, const float* __restrict__ loss,
+                                                                  const float* __restrict__ gscale, bf16* dlow, int accumulate,
+                                                                  int tiles_y, int tiles_x, int c_base) {
+  upce_bwd_tiled<NV>(low, target, a, ignore_index, weight, lse, loss, gscale, dlow, accumulate, tiles_y, tiles_x,
+                     c_base + blockIdx.y * 8 * NV);
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void upce_wide_bwd_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target,
+                                                            UpArgs a, int64_t ignore_index, const float* __restrict__ weight,
+                                                            const float* __restrict__ lse, const float* __restrict__ loss,
+                                                            const float* __restrict__ gscale, bf16* dlow, int accumulate,
+                                                            int c_base) {
+  upce_bwd_gather<NV>(low, target, a, ignore_index, weight, lse, loss, gscale, dlow, accumulate, c_base + blockIdx.y * 8 * NV);
 }
 
 // window of UT source pixels at destination/source ratio r: (UT - 1) r between first and last pixel + (2 r + 4) per pixel
@@ -204,8 +379,8 @@ bool up_tiled_ok(const UpArgs& a) {
   return (int)ceilf((UT + 1) * r) + 4 <= UWIN;
 }
 
-bool fill_up(UpArgs& a, int n, int hs, int ws, int classes, int ld, int hd, int wd) {
-  if (n <= 0 || hs <= 0 || ws <= 0 || hd <= 0 || wd <= 0 || classes <= 0 || ld < classes || (ld & 7) || ld > 32) return false;
+bool fill_up(UpArgs& a, int n, int hs, int ws, int classes, int ld, int hd, int wd, int max_ld = 32) {
+  if (n <= 0 || hs <= 0 || ws <= 0 || hd <= 0 || wd <= 0 || classes <= 0 || ld < classes || (ld & 7) || ld > max_ld) return false;
   if ((long long)n * hd * wd >= (1ll << 31)) return false;
   a.n = n; a.hs = hs; a.ws = ws; a.classes = classes; a.ld = ld; a.hd = hd; a.wd = wd;
   a.sh = (float)hs / (float)hd; a.sw = (float)ws / (float)wd;
@@ -222,6 +397,27 @@ void with_nv(int nv, F&& f) {
     default: f(std::integral_constant<int, 4>()); break;
   }
 }
+
+// f(G as a compile-time constant): the lane group of the wide forward, the power of two >= nv = ld / 8 = 1 .. 32
+template <class F>
+void with_group(int nv, F&& f) {
+  if (nv <= 1) f(std::integral_constant<int, 1>());
+  else if (nv <= 2) f(std::integral_constant<int, 2>());
+  else if (nv <= 4) f(std::integral_constant<int, 4>());
+  else if (nv <= 8) f(std::integral_constant<int, 8>());
+  else if (nv <= 16) f(std::integral_constant<int, 16>());
+  else f(std::integral_constant<int, 32>());
+}
+
+// Source pixels along one axis that WT destination pixels can touch, scale = in / out: floor(s) moves by at most
+// ceil((WT - 1) scale) + 1 between the first and the last pixel (the +1: fp32 rounding of the coordinate), one more for the last
+// pixel's i1, one for the count.
+int wide_footprint(float scale, int n_src) {
+  const int f = (int)ceilf((WT - 1) * scale) + 3;
+  return f < n_src ? f : n_src;
+}
+
+constexpr int WIDE_NV = 2;     // channel chunk of the wide backward: 16 channels, a UWIN x UWIN window of 51 KB
 }  // namespace
 
 extern "C" int tok_upsample_ce_serves(int classes, int ld) { return classes > 0 && ld >= classes && (ld & 7) == 0 && ld <= 32; }
@@ -268,5 +464,66 @@ extern "C" int tok_upsample_ce_bwd(const void* low, int n, int hs, int ws, int c
                        (const bf16*)low, target, a, ignore_index, lse, loss, gscale, (bf16*)dlow, accumulate);
   });
   TOK_CHECK_LAUNCH("tok_upsample_ce_bwd");
+  return TOK_OK;
+}
+
+extern "C" int tok_upsample_ce_wide_serves(int classes, int ld) { return classes > 0 && ld >= classes && (ld & 7) == 0 && ld <= 256; }
+
+extern "C" int tok_upsample_ce_wide_fwd(const void* low, int n, int hs, int ws, int classes, int ld, int hd, int wd,
+                                        const int64_t* target, int64_t ignore_index, const float* weight, float* lse,
+                                        float* row_loss, float* loss, void* stream) {
+  UpArgs a;
+  TOK_CHECK_ARG(low && target && lse && row_loss && loss && fill_up(a, n, hs, ws, classes, ld, hd, wd, 256),
+                "tok_upsample_ce_wide_fwd: bad args (row pitch a multiple of 8 up to 256 channels, n*hd*wd < 2^31)");
+  TOK_CHECK_ARG((reinterpret_cast<uintptr_t>(low) & 15) == 0 && (reinterpret_cast<uintptr_t>(loss) & 7) == 0,
+                "tok_upsample_ce_wide_fwd: low must be 16-byte, loss 8-byte aligned");
+  hipStream_t st = tok_stream(stream);
+  const int tiles_y = tok_cdiv(hd, WT), tiles_x = tok_cdiv(wd, WT);
+  const size_t bytes = (size_t)wide_footprint(a.sh, hs) * wide_footprint(a.sw, ws) * ld * 2;
+  with_group(ld >> 3, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    if (bytes <= (size_t)WIDE_LDS)
+      tok_launch_lds<&upce_wide_fwd_kernel<G, true>>(WIDE_LDS, dim3(n * tiles_y * tiles_x), dim3(256), bytes, st, (const bf16*)low,
+                                                     target, a, ignore_index, weight, lse, row_loss, tiles_y, tiles_x);
+    else
+      hipLaunchKernelGGL((upce_wide_fwd_kernel<G, false>), dim3(n * tiles_y * tiles_x), dim3(256), 0, st, (const bf16*)low,
+                         target, a, ignore_index, weight, lse, row_loss, tiles_y, tiles_x);
+  });
+  TOK_CHECK_LAUNCH("tok_upsample_ce_wide_fwd");
+  return ce_mean_launch("tok_upsample_ce_wide_fwd", row_loss, target, n * hd * wd, ignore_index, classes, loss, st, weight);
+}
+
+extern "C" int tok_upsample_ce_wide_bwd(const void* low, int n, int hs, int ws, int classes, int ld, int hd, int wd,
+                                        const int64_t* target, int64_t ignore_index, const float* weight, const float* lse,
+                                        const float* loss, const float* gscale, void* dlow, int accumulate, void* stream) {
+  UpArgs a;
+  TOK_CHECK_ARG(low && target && lse && loss && dlow && fill_up(a, n, hs, ws, classes, ld, hd, wd, 256),
+                "tok_upsample_ce_wide_bwd: bad args");
+  TOK_CHECK_ARG((reinterpret_cast<uintptr_t>(low) & 15) == 0 && (reinterpret_cast<uintptr_t>(dlow) & 15) == 0,
+                "tok_upsample_ce_wide_bwd: low / dlow must be 16-byte aligned");
+  hipStream_t st = tok_stream(stream);
+  const bool tiled = up_tiled_ok(a);
+  const int tiles_y = tok_cdiv(hs, UT), tiles_x = tok_cdiv(ws, UT);
+  const unsigned blocks = tiled ? n * tiles_y * tiles_x : grid_for((size_t)n * hs * ws);
+  // chunks of WIDE_NV vectors, then the rest of the row (ld / 8 odd) as one chunk of its own; rows of up to 32 channels whole
+  auto launch = [&](auto nv, int chunks, int c_base) {
+    constexpr int NV = decltype(nv)::value;
+    if (tiled)
+      tok_launch_lds<&upce_wide_bwd_tiled_kernel<NV>>(UWIN * UWIN * NV * 16, dim3(blocks, chunks), dim3(256), UWIN * UWIN * NV * 16,
+                                                      st, (const bf16*)low, target, a, ignore_index, weight, lse, loss, gscale,
+                                                      (bf16*)dlow, accumulate, tiles_y, tiles_x, c_base);
+    else
+      hipLaunchKernelGGL(upce_wide_bwd_kernel<NV>, dim3(blocks, chunks), dim3(256), 0, st, (const bf16*)low, target, a,
+                         ignore_index, weight, lse, loss, gscale, (bf16*)dlow, accumulate, c_base);
+  };
+  const int nvec = ld >> 3, full = nvec / WIDE_NV;
+  if (nvec <= 4) {
+    // a row the narrow kernels hold in registers: one chunk, their instantiation of the body
+    with_nv(nvec, [&](auto nv) { launch(nv, 1, 0); });
+  } else {
+    launch(std::integral_constant<int, WIDE_NV>(), full, 0);
+    if (nvec % WIDE_NV) launch(std::integral_constant<int, 1>(), 1, full * WIDE_NV * 8);
+  }
+  TOK_CHECK_LAUNCH("tok_upsample_ce_wide_bwd");
   return TOK_OK;
 }

@@ -16,7 +16,7 @@ _CHECK_TARGETS = os.environ.get('TOK_CHECK_TARGETS', '0') == '1'
 
 class _SoftmaxCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits: Tensor, target: Tensor, ignore_index: int, smooth: float = 0.0):
+    def forward(ctx, logits: Tensor, target: Tensor, ignore_index: int, smooth: float = 0.0, weight=None):
         require_device(logits)
         ctx.spatial = None
         if logits.dim() == 4:
@@ -48,9 +48,15 @@ class _SoftmaxCE(torch.autograd.Function):
         lse = torch.empty(rows, dtype=torch.float32, device=dev)
         row_loss = torch.empty(rows, dtype=torch.float32, device=dev)
         loss = torch.empty(_C.TOK_CE_LOSS_FLOATS, dtype=torch.float32, device=dev)
-        _C.check(_C.lib().tok_softmax_ce_smooth_fwd(ptr(z), ptr(target), rows, classes, z.stride(0), ignore_index,
-                                                    float(smooth), ptr(lse), ptr(row_loss), ptr(loss), stream_ptr()),
-                 'tok_softmax_ce_smooth_fwd')
+        if weight is None:
+            _C.check(_C.lib().tok_softmax_ce_smooth_fwd(ptr(z), ptr(target), rows, classes, z.stride(0), ignore_index,
+                                                        float(smooth), ptr(lse), ptr(row_loss), ptr(loss), stream_ptr()),
+                     'tok_softmax_ce_smooth_fwd')
+        else:       # class weights (no smoothing: refused at construction); loss[1] is then the sum of the valid rows' weights
+            _C.check(_C.lib().tok_softmax_ce_weighted_fwd(ptr(z), ptr(target), ptr(weight), rows, classes, z.stride(0),
+                                                          ignore_index, ptr(lse), ptr(row_loss), ptr(loss), stream_ptr()),
+                     'tok_softmax_ce_weighted_fwd')
+        ctx.weight = weight
         ctx.z, ctx.target, ctx.lse, ctx.loss, ctx.ignore_index, ctx.smooth = z, target, lse, loss, ignore_index, float(smooth)
         ctx.in_dtype = logits.dtype
         n_valid = loss[1]             # number of non-ignored rows, stays on the device (reduction='sum')
@@ -64,10 +70,15 @@ class _SoftmaxCE(torch.autograd.Function):
         ld = z.stride(0)          # the kernel writes d(logits) in the row pitch of the logits
         gs = g.detach().to(torch.float32).reshape(1).contiguous()
         d = torch.empty((rows, ld), dtype=BF16, device=z.device)
-        _C.check(_C.lib().tok_softmax_ce_smooth_bwd(ptr(z), ptr(target), ptr(ctx.lse), ptr(ctx.loss), ptr(gs), rows,
-                                                    classes, z.stride(0), ctx.ignore_index, ctx.smooth, ptr(d), stream_ptr()),
-                 'tok_softmax_ce_smooth_bwd')
-        ctx.z = ctx.target = ctx.lse = ctx.loss = None
+        if ctx.weight is None:
+            _C.check(_C.lib().tok_softmax_ce_smooth_bwd(ptr(z), ptr(target), ptr(ctx.lse), ptr(ctx.loss), ptr(gs), rows,
+                                                        classes, z.stride(0), ctx.ignore_index, ctx.smooth, ptr(d), stream_ptr()),
+                     'tok_softmax_ce_smooth_bwd')
+        else:
+            _C.check(_C.lib().tok_softmax_ce_weighted_bwd(ptr(z), ptr(target), ptr(ctx.weight), ptr(ctx.lse), ptr(ctx.loss), ptr(gs),
+                                                          rows, classes, z.stride(0), ctx.ignore_index, ptr(d), stream_ptr()),
+                     'tok_softmax_ce_weighted_bwd')
+        ctx.z = ctx.target = ctx.lse = ctx.loss = ctx.weight = None
         if ctx.spatial is not None:
             n, h, w = ctx.spatial
             if ld == pad8(classes) != classes:
@@ -79,7 +90,7 @@ class _SoftmaxCE(torch.autograd.Function):
             d = d[:, :classes]
         if ctx.in_dtype != BF16:
             d = d.to(ctx.in_dtype)
-        return d, None, None, None
+        return d, None, None, None, None
 
 
 class UpsampledLogits(torch.Tensor):
@@ -164,10 +175,11 @@ def materialized(x):
 
 
 class _UpsampleCE(torch.autograd.Function):
-    """CrossEntropyLoss(F.interpolate(low, size, 'bilinear'), target) from the low-resolution logits (csrc/loss_upsample_ce.hip)."""
+    """CrossEntropyLoss(F.interpolate(low, size, 'bilinear'), target) from the low-resolution logits (csrc/loss_upsample_ce.hip).
+    `wide`: the tok_upsample_ce_wide_* entries (rows of up to 256 channels, class weights `weight` or None)."""
 
     @staticmethod
-    def forward(ctx, low: Tensor, target: Tensor, size, ignore_index: int):
+    def forward(ctx, low: Tensor, target: Tensor, size, ignore_index: int, wide: bool = False, weight=None):
         require_device(low)
         n, classes, hs, ws = low.shape
         hd, wd = size
@@ -187,8 +199,14 @@ class _UpsampleCE(torch.autograd.Function):
         lse = torch.empty(rows, dtype=torch.float32, device=dev)
         row_loss = torch.empty(rows, dtype=torch.float32, device=dev)
         loss = torch.empty(_C.TOK_CE_LOSS_FLOATS, dtype=torch.float32, device=dev)
-        _C.check(_C.lib().tok_upsample_ce_fwd(ptr(z), n, hs, ws, classes, ld, hd, wd, ptr(target), ignore_index, ptr(lse),
-                                              ptr(row_loss), ptr(loss), stream_ptr()), 'tok_upsample_ce_fwd')
+        if wide:
+            _C.check(_C.lib().tok_upsample_ce_wide_fwd(ptr(z), n, hs, ws, classes, ld, hd, wd, ptr(target), ignore_index,
+                                                       ptr(weight), ptr(lse), ptr(row_loss), ptr(loss), stream_ptr()),
+                     'tok_upsample_ce_wide_fwd')
+        else:
+            _C.check(_C.lib().tok_upsample_ce_fwd(ptr(z), n, hs, ws, classes, ld, hd, wd, ptr(target), ignore_index, ptr(lse),
+                                                  ptr(row_loss), ptr(loss), stream_ptr()), 'tok_upsample_ce_fwd')
+        ctx.wide, ctx.weight = wide, weight
         ctx.z, ctx.target, ctx.lse, ctx.loss, ctx.ignore_index = z, target, lse, loss, ignore_index
         ctx.geom = (n, hs, ws, classes, ld, hd, wd)
         ctx.in_dtype = low.dtype
@@ -201,16 +219,21 @@ class _UpsampleCE(torch.autograd.Function):
         n, hs, ws, classes, ld, hd, wd = ctx.geom
         gs = g.detach().to(torch.float32).reshape(1).contiguous()
         d = torch.empty((n, hs, ws, ld), dtype=BF16, device=ctx.z.device)
-        _C.check(_C.lib().tok_upsample_ce_bwd(ptr(ctx.z), n, hs, ws, classes, ld, hd, wd, ptr(ctx.target), ctx.ignore_index,
-                                              ptr(ctx.lse), ptr(ctx.loss), ptr(gs), ptr(d), 0, stream_ptr()),
-                 'tok_upsample_ce_bwd')
-        ctx.z = ctx.target = ctx.lse = ctx.loss = None
+        if ctx.wide:
+            _C.check(_C.lib().tok_upsample_ce_wide_bwd(ptr(ctx.z), n, hs, ws, classes, ld, hd, wd, ptr(ctx.target),
+                                                       ctx.ignore_index, ptr(ctx.weight), ptr(ctx.lse), ptr(ctx.loss), ptr(gs),
+                                                       ptr(d), 0, stream_ptr()), 'tok_upsample_ce_wide_bwd')
+        else:
+            _C.check(_C.lib().tok_upsample_ce_bwd(ptr(ctx.z), n, hs, ws, classes, ld, hd, wd, ptr(ctx.target), ctx.ignore_index,
+                                                  ptr(ctx.lse), ptr(ctx.loss), ptr(gs), ptr(d), 0, stream_ptr()),
+                     'tok_upsample_ce_bwd')
+        ctx.z = ctx.target = ctx.lse = ctx.loss = ctx.weight = None
         if ld == pad8(classes) != classes:
             mark_padded(d)
         d = d[..., :classes].permute(0, 3, 1, 2)
         if ctx.in_dtype != BF16:
             d = d.to(ctx.in_dtype)
-        return d, None, None, None
+        return d, None, None, None, None, None
 
 
 # TOK_FUSE_UPSAMPLE_CE=0: SegmentationHead returns the interpolated tensor itself (the round-3 path)
@@ -224,25 +247,45 @@ class CrossEntropyLoss(nn.Module):
     def __init__(self, weight=None, size_average=None, ignore_index: int = -100, reduce=None,
                  reduction: str = 'mean', label_smoothing: float = 0.0):
         super().__init__()
-        if weight is not None or reduction not in ('mean', 'sum') or size_average is not None or reduce is not None:
-            raise NotImplementedError("torchok_amd CrossEntropyLoss: reduction 'mean' or 'sum', no class weights")
+        if reduction not in ('mean', 'sum') or size_average is not None or reduce is not None:
+            raise NotImplementedError("torchok_amd CrossEntropyLoss: reduction 'mean' or 'sum'")
         if not 0.0 <= label_smoothing <= 1.0:
             raise ValueError(f'label_smoothing must be between 0.0 and 1.0. Got: {label_smoothing}')
+        if weight is not None and label_smoothing > 0.0:
+            raise NotImplementedError('torchok_amd CrossEntropyLoss: class weights together with label_smoothing > 0')
         self.ignore_index, self.label_smoothing, self.reduction = ignore_index, label_smoothing, reduction
+        # class weights (tensor, list or tuple): an fp32 buffer that moves with the module
+        self.register_buffer('weight', None if weight is None else
+                             torch.as_tensor(weight, dtype=torch.float32).detach().clone().reshape(-1).contiguous())
+
+    def _weight(self, input: Tensor):
+        """the weights on the device of the logits, their length checked against the class count"""
+        w = self.weight
+        if w is None:
+            return None
+        if w.numel() != input.shape[1]:
+            raise ValueError(f'weight tensor should be defined either for all {input.shape[1]} classes or no classes '
+                             f'but got weight tensor of shape: [{w.numel()}]')
+        return w if w.device == input.device else w.to(input.device)
 
     def forward(self, input: Tensor, target: Tensor) -> Tensor:
+        weight = self._weight(input)
         if isinstance(input, UpsampledLogits):
             low, size = input._low, input._size
             ld = low.permute(0, 2, 3, 1).stride(2) if low.dim() == 4 else 0
-            if (self.label_smoothing == 0.0 and input._full is None and target.shape == (low.shape[0],) + size
-                    and _C.lib().tok_upsample_ce_serves(low.shape[1], max(ld, pad8(low.shape[1])))):
-                loss, n_valid = _UpsampleCE.apply(low, target, size, self.ignore_index)
-                return loss if self.reduction == 'mean' else loss * n_valid
+            if self.label_smoothing == 0.0 and input._full is None and target.shape == (low.shape[0],) + size:
+                # rows of up to 32 channels without weights: the narrow kernels; up to 256 channels, or weighted: the wide ones
+                lib, width = _C.lib(), (low.shape[1], max(ld, pad8(low.shape[1])))
+                wide_serves = getattr(lib, 'tok_upsample_ce_wide_serves', None)
+                wide = not (weight is None and lib.tok_upsample_ce_serves(*width))
+                if not wide or (wide_serves is not None and wide_serves(*width)):
+                    loss, n_valid = _UpsampleCE.apply(low, target, size, self.ignore_index, wide, weight)
+                    return loss if self.reduction == 'mean' else loss * n_valid
             input = input.materialize()
         if input.dim() not in (2, 4):
             raise NotImplementedError('torchok_amd CrossEntropyLoss: (N, C) or (N, C, H, W) logits')
         if input.dim() == 4 and target.shape != (input.shape[0],) + tuple(input.shape[2:]):
             raise ValueError(f'Expected target of shape (N, H, W) for (N, C, H, W) logits, got {tuple(target.shape)}')
-        loss, n_valid = _SoftmaxCE.apply(input, target, self.ignore_index, self.label_smoothing)
-        # 'sum' = mean over the non-ignored rows * their number
+        loss, n_valid = _SoftmaxCE.apply(input, target, self.ignore_index, self.label_smoothing, weight)
+        # 'sum' = mean over the non-ignored rows * their number (their weights' sum under class weights)
         return loss if self.reduction == 'mean' else loss * n_valid
