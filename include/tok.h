@@ -430,6 +430,22 @@ int tok_dice_fwd(const void* logits, const void* target, int64_t rows, int class
                  float* coef, void* stream);
 int tok_dice_bwd(const void* logits, const void* target, const float* coef, const float* gscale, int64_t rows,
                  int classes, int ld, int mode, void* dlogits, void* stream);
+/* Multiclass DiceLoss ON the bilinearly upsampled logits without the upsampled tensor (the Dice half of the segmentation recipes'
+ * CrossEntropyLoss + DiceLoss pair): low, target and the geometry as tok_upsample_ce_fwd, ld % 8 == 0, classes <= ld <= 64, low /
+ * dlow 16-byte aligned, anything else TOK_ERR_INVALID with nothing launched.  The interpolated logits are tok_bilinear_fwd's
+ * stored bf16 values, y = (target == class) (a label outside [0, classes) adds to sum p only), so loss and coef are tok_dice_fwd's
+ * on the interpolated tensor up to summation order.  Forward: lse fp32 [n*hd*wd] (saved for the backward), partial fp32
+ * [tok_upsample_dice_rows(n, hd, wd)][3][classes] (scratch), loss fp32 [1], coef fp32 [2][classes]; smooth, eps, log_loss and
+ * class_sel as tok_dice_fwd.  Backward: dlow bf16 [n][hs][ws][ld] (+)= adjoint of the interpolation applied to
+ * bf16(p (dp - sum_k p_k dp_k) gscale[0]), dp = coef[0][c] y + coef[1][c] — the values of tok_dice_bwd + tok_bilinear_bwd;
+ * deterministic, no atomics; pad channels [classes, ld) are 0 (left alone when accumulate).                               */
+int tok_upsample_dice_serves(int classes, int ld);
+int tok_upsample_dice_rows(int n, int hd, int wd);
+int tok_upsample_dice_fwd(const void* low, int n, int hs, int ws, int classes, int ld, int hd, int wd, const int64_t* target,
+                          float smooth, float eps, int log_loss, const int64_t* class_sel, int n_sel, float* lse, float* partial,
+                          float* loss, float* coef, void* stream);
+int tok_upsample_dice_bwd(const void* low, int n, int hs, int ws, int classes, int ld, int hd, int wd, const int64_t* target,
+                          const float* lse, const float* coef, const float* gscale, void* dlow, int accumulate, void* stream);
 
 /* BCEWithLogitsLoss with an ignore value (losses/classification/binary_cross_entropy.py:13-59; its forward :50-59 drops
  * the elements whose target equals ignore_index, then F.binary_cross_entropy_with_logits over the rest, 'mean' or 'sum';

@@ -121,6 +121,11 @@ PROTOTYPES = {
     'tok_dice_rows': (c_int, [c_int64]),
     'tok_dice_fwd': (c_int, [_P, _P, c_int64, c_int, c_int, c_int, c_float, c_float, c_int, _P, c_int, _P, _P, _P, _P]),
     'tok_dice_bwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P]),
+    'tok_upsample_dice_serves': (c_int, [c_int, c_int]),
+    'tok_upsample_dice_rows': (c_int, [c_int, c_int, c_int]),
+    'tok_upsample_dice_fwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_float, c_float, c_int, _P, c_int,
+                                      _P, _P, _P, _P, _P]),
+    'tok_upsample_dice_bwd': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P]),
     'tok_bce_logits_fwd': (c_int, [_P, _P, c_int64, c_int, c_int, c_float, c_int, _P, _P]),
     'tok_bce_logits_bwd': (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_float, c_int, _P, _P]),
     'tok_relevance_matrix_multilabel': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),

@@ -2,7 +2,7 @@
 // mode 0 (multiclass): p = softmax(logits) per pixel row, y = one_hot(target);  mode 1 (binary): p = sigmoid(logit 0),
 // y = target (float);  mode 2 (multilabel): p = sigmoid(logit c), y = target[row][c] (float).  Per class: I = sum p*y, P = sum p, Y = sum y.  One wave per pixel row, lane = class; every lane
 // keeps its class's three sums in registers over all the rows of its wave; waves -> block partial row (fixed order).
-#include "tok_common.h"
+#include "loss_dice.h"
 #include <stdlib.h>
 #include <math.h>
 
@@ -131,6 +131,14 @@ extern "C" int tok_dice_rows(int64_t rows) {
   return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
+// the finalize of `nparts` partial rows [3][classes]: the tail of tok_dice_fwd and tok_upsample_dice_fwd (`who`)
+int dice_finalize_launch(const char* who, const float* partial, int nparts, int classes, float smooth, float eps, int log_loss,
+                         const int64_t* class_sel, int n_sel, float* loss, float* coef, hipStream_t st) {
+  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, st, partial, nparts, classes, smooth, eps, log_loss, class_sel,
+                     n_sel, loss, coef);
+  return launched(who, "(finalize)");
+}
+
 extern "C" int tok_dice_fwd(const void* logits, const void* target, int64_t rows, int classes, int ld, int mode,
                             float smooth, float eps, int log_loss, const int64_t* class_sel, int n_sel, float* partial,
                             float* loss, float* coef, void* stream) {
@@ -142,10 +150,7 @@ extern "C" int tok_dice_fwd(const void* logits, const void* target, int64_t rows
   hipLaunchKernelGGL(dice_fwd_kernel, dim3(g), dim3(256), 0, st, (const bf16*)logits, target, rows, classes, ld, mode,
                      partial);
   TOK_CHECK_LAUNCH("tok_dice_fwd");
-  hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, st, partial, g, classes, smooth, eps, log_loss, class_sel,
-                     n_sel, loss, coef);
-  TOK_CHECK_LAUNCH("tok_dice_fwd(finalize)");
-  return TOK_OK;
+  return dice_finalize_launch("tok_dice_fwd", partial, g, classes, smooth, eps, log_loss, class_sel, n_sel, loss, coef, st);
 }
 
 extern "C" int tok_dice_bwd(const void* logits, const void* target, const float* coef, const float* gscale, int64_t rows,

@@ -9,51 +9,10 @@
 // full-resolution pixels whose footprint contains it, recomputes their softmax from the saved log-sum-exp and sums
 // weight * bf16(d logits) — deterministic, no atomics, nothing full-resolution in HBM except lse / row_loss (4 bytes per pixel each).
 #include "loss_common.h"
-#include "resample.h"
+#include "loss_upsample.h"
 #include <stdlib.h>
-#include <math.h>
-#include <type_traits>
 
 namespace {
-
-struct UpArgs {
-  int n, hs, ws, classes, ld, hd, wd;
-  float sh, sw;     // in / out
-};
-
-// eight interpolated logits from the four corners' vectors, rounded to bf16 as tok_bilinear_fwd stores them: the ONE text of
-// the blend hy (hx a + lx b) + ly (hx c + lx d) for the narrow and the wide kernels, with every rounding written out.  Left to
-// the compiler, the contraction into fused multiply-adds differs from kernel to kernel (the packed form of the wide forward
-// fused the other product of some elements), and at dyadic weights the bf16 rounding behind it sits on ties: the wide entries
-// would not give the narrow entries' bits.  The form below is the one hipcc chose for the narrow kernels.
-__device__ __forceinline__ void up_blend8(float hy, float ly, float hx, float lx, bf16x8 v00, bf16x8 v01, bf16x8 v10, bf16x8 v11,
-                                          float* v) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float u = fmaf(lx, bf2f(v01[e]), hx * bf2f(v00[e])), w = fmaf(lx, bf2f(v11[e]), hx * bf2f(v10[e]));
-    v[e] = bf2f(f2bf(fmaf(hy, u, ly * w)));
-  }
-}
-
-// interpolated, bf16-rounded logits of full-resolution pixel (b, y, x): v[0 .. 8 NV), from channel 0 of `low` on (a chunk of the
-// wide backward hands in low + its first channel)
-template <int NV>
-__device__ __forceinline__ void up_logits(const bf16* __restrict__ low, const UpArgs& a, int b, int y, int x, float* v) {
-  int y0, y1, x0, x1;
-  float ly, lx;
-  src_index(a.sh, y, a.hs, y0, y1, ly);
-  src_index(a.sw, x, a.ws, x0, x1, lx);
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  const bf16* base = low + (size_t)b * a.hs * a.ws * a.ld;
-  const bf16* p00 = base + ((size_t)y0 * a.ws + x0) * a.ld;
-  const bf16* p01 = base + ((size_t)y0 * a.ws + x1) * a.ld;
-  const bf16* p10 = base + ((size_t)y1 * a.ws + x0) * a.ld;
-  const bf16* p11 = base + ((size_t)y1 * a.ws + x1) * a.ld;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    up_blend8(hy, ly, hx, lx, ldg16(p00 + i * 8), ldg16(p01 + i * 8), ldg16(p10 + i * 8), ldg16(p11 + i * 8), v + i * 8);
-  }
-}
 
 template <int NV>
 __global__ __launch_bounds__(256) void upce_fwd_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target, UpArgs a,
@@ -133,8 +92,6 @@ __global__ __launch_bounds__(256) void upce_bwd_kernel(const bf16* __restrict__ 
 // low-resolution pixels, stages bf16(d upsampled logits) of the full-resolution window that can touch them in LDS (phase 1),
 // then every (low-resolution pixel, 8-channel group) walks its footprint with tok_bilinear_bwd's exact index / weight
 // arithmetic, reading LDS (phase 2).  Window = the union of the per-pixel windows of the gather kernel, at most UWIN x UWIN.
-constexpr int UT = 8, UWIN = 40, UPP = 12;     // tile edge, window edge, window of ONE source pixel (2 r + 4 at r <= 4)
-
 // (channels [c0, c0 + 8 NV) and the class weights as in upce_bwd_gather)
 template <int NV>
 __device__ __forceinline__ void upce_bwd_tiled(const bf16* __restrict__ low, const int64_t* __restrict__ target, const UpArgs& a,
@@ -144,20 +101,8 @@ __device__ __forceinline__ void upce_bwd_tiled(const bf16* __restrict__ low, con
                                                int tiles_x, int c0) {
   extern __shared__ __attribute__((aligned(16))) char up_smem[];
   bf16* win = reinterpret_cast<bf16*>(up_smem);                 // [wh][ww][8 NV]
-  const int tile = blockIdx.x;
-  const int tx = tile % tiles_x;
-  const int t2 = tile / tiles_x;
-  const int ty = t2 % tiles_y;
-  const int b = t2 / tiles_y;
-  const int ys0 = ty * UT, xs0 = tx * UT;
-  const int ys1 = min(a.hs, ys0 + UT) - 1, xs1 = min(a.ws, xs0 + UT) - 1;
-  const float rh = 1.f / a.sh, rw = 1.f / a.sw;
-  int wy0, wy1, wx0, wx1, tmp0, tmp1;
-  adj_window(rh, ys0, a.hd, wy0, tmp1);
-  adj_window(rh, ys1, a.hd, tmp0, wy1);
-  adj_window(rw, xs0, a.wd, wx0, tmp1);
-  adj_window(rw, xs1, a.wd, tmp0, wx1);
-  const int wh = wy1 - wy0 + 1, ww = wx1 - wx0 + 1;             // <= UWIN (checked by the launcher for the scale)
+  const UpTile tl = up_tile<UT>(a, tiles_y, tiles_x);
+  const int b = tl.b, wy0 = tl.wy0, wx0 = tl.wx0, wh = tl.wh, ww = tl.ww;             // wh, ww <= UWIN
   const float g0 = (gscale ? gscale[0] : 1.f) / loss[1];
   // ---- phase 1: bf16(d upsampled logits) of the window ----------------------------------------------------------------------
   for (int i = threadIdx.x; i < wh * ww; i += 256) {
@@ -187,41 +132,7 @@ __device__ __forceinline__ void upce_bwd_tiled(const bf16* __restrict__ low, con
   }
   __syncthreads();
   // ---- phase 2: the adjoint of the interpolation, one (low-resolution pixel, 8-channel group) per thread ------------------------
-  for (int i = threadIdx.x; i < UT * UT * NV; i += 256) {
-    const int v8 = i % NV;
-    const int p = i / NV;
-    const int ys = ys0 + p / UT, xs = xs0 + p % UT;
-    if (ys > ys1 || xs > xs1) continue;
-    int yd0, yd1, xd0, xd1;
-    adj_window(rh, ys, a.hd, yd0, yd1);
-    adj_window(rw, xs, a.wd, xd0, xd1);
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    // the column weights of this pixel once (the window of one source pixel is at most UPP wide at the scales the tiled
-    // kernel serves), then rows x columns of LDS reads
-    float wxs[UPP];
-#pragma unroll
-    for (int j = 0; j < UPP; ++j) {
-      const int xd = xd0 + j;
-      const float wx = adj_weight(a.sw, xd <= xd1 ? xd : xd1, a.ws, xs);
-      wxs[j] = xd <= xd1 ? wx : 0.f;
-    }
-    for (int yd = yd0; yd <= yd1; ++yd) {
-      const float wy = adj_weight(a.sh, yd, a.hs, ys);
-      if (wy == 0.f) continue;
-      const bf16* rowp = win + ((size_t)(yd - wy0) * ww + (xd0 - wx0)) * (8 * NV) + v8 * 8;
-#pragma unroll
-      for (int j = 0; j < UPP; ++j) {
-        if (wxs[j] == 0.f) continue;
-        const bf16x8 q = *reinterpret_cast<const bf16x8*>(rowp + (size_t)j * (8 * NV));
-        const float wgt = wy * wxs[j];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = fmaf(wgt, bf2f(q[e]), acc[e]);
-      }
-    }
-    store_acc<8>(dlow + (((size_t)b * a.hs + ys) * a.ws + xs) * a.ld + c0 + v8 * 8, acc, accumulate);
-  }
+  up_adjoint_tile<UT>(win, a, tl, NV, dlow, accumulate, c0);
 }
 
 template <int NV>
@@ -241,30 +152,7 @@ __global__ __launch_bounds__(256) void upce_bwd_tiled_kernel(const bf16* __restr
 // pixel are LDS reads instead of four global gathers.  Where the footprint does not fit (downsampling, identity at wide rows) the
 // taps come from global memory.  Blend, rounding, __expf / __logf and the validity rule are the narrow kernel's; so is the order of
 // the sum inside every block of 32 classes (group_sum), which makes unweighted results at ld <= 32 the narrow kernel's bits.
-constexpr int WT = 16;
 constexpr int WIDE_LDS = 64 * 1024;
-
-// Sum of the group's exponentials.  Inside a block of 32 classes the four lanes hand a running sum on, lane 0 first, each adding
-// its eight values in class order: the narrow kernel's sequential sum.  The blocks of 32 are folded by a butterfly.
-template <int G>
-__device__ __forceinline__ float group_sum(const float (&ex)[8], int j) {
-  constexpr int Q = G < 4 ? G : 4;
-  float run = 0.f;
-#pragma unroll
-  for (int step = 0; step < Q; ++step) {
-    const float prev = step ? __shfl_up(run, 1, Q) : 0.f;
-    if ((j & (Q - 1)) == step) {
-      float s = prev;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += ex[e];
-      run = s;
-    }
-  }
-  float s = __shfl(run, Q - 1, Q);
-#pragma unroll
-  for (int off = Q; off < G; off <<= 1) s += __shfl_xor(s, off, G);
-  return s;
-}
 
 template <int G, bool STAGE>
 __global__ __launch_bounds__(256) void upce_wide_fwd_kernel(const bf16* __restrict__ low, const int64_t* __restrict__ target,
@@ -283,21 +171,8 @@ __global__ __launch_bounds__(256) void upce_wide_fwd_kernel(const bf16* __restri
   const bf16* src = low + (size_t)b * a.hs * a.ws * a.ld;
   int sy0 = 0, sx0 = 0, fw = a.ws;
   if constexpr (STAGE) {
-    // src_index is monotone in the destination index: the footprint runs from the first pixel's i0 to the last pixel's i1
-    int sy1, sx1, tmp;
-    float l;
-    src_index(a.sh, yt0, a.hs, sy0, tmp, l);
-    src_index(a.sh, yt1, a.hs, tmp, sy1, l);
-    src_index(a.sw, xt0, a.ws, sx0, tmp, l);
-    src_index(a.sw, xt1, a.ws, tmp, sx1, l);
-    fw = sx1 - sx0 + 1;
     bf16* win = reinterpret_cast<bf16*>(up_smem);
-    const int nv = a.ld >> 3;
-    for (int i = threadIdx.x; i < (sy1 - sy0 + 1) * fw * nv; i += 256) {
-      const int p = i / nv, v8 = i - p * nv;
-      const int fy = p / fw, fx = p - fy * fw;
-      *reinterpret_cast<bf16x8*>(win + (size_t)p * a.ld + v8 * 8) = ldg16(src + ((size_t)(sy0 + fy) * a.ws + sx0 + fx) * a.ld + v8 * 8);
-    }
+    up_stage_footprint(src, a, yt0, yt1, xt0, xt1, win, sy0, sx0, fw);
     __syncthreads();
     src = win;
   }
@@ -373,20 +248,6 @@ __global__ __launch_bounds__(256) void upce_wide_bwd_kernel(const bf16* __restri
   upce_bwd_gather<NV>(low, target, a, ignore_index, weight, lse, loss, gscale, dlow, accumulate, c_base + blockIdx.y * 8 * NV);
 }
 
-// window of UT source pixels at destination/source ratio r: (UT - 1) r between first and last pixel + (2 r + 4) per pixel
-bool up_tiled_ok(const UpArgs& a) {
-  const float r = fmaxf(1.f / a.sh, 1.f / a.sw);
-  return (int)ceilf((UT + 1) * r) + 4 <= UWIN;
-}
-
-bool fill_up(UpArgs& a, int n, int hs, int ws, int classes, int ld, int hd, int wd, int max_ld = 32) {
-  if (n <= 0 || hs <= 0 || ws <= 0 || hd <= 0 || wd <= 0 || classes <= 0 || ld < classes || (ld & 7) || ld > max_ld) return false;
-  if ((long long)n * hd * wd >= (1ll << 31)) return false;
-  a.n = n; a.hs = hs; a.ws = ws; a.classes = classes; a.ld = ld; a.hd = hd; a.wd = wd;
-  a.sh = (float)hs / (float)hd; a.sw = (float)ws / (float)wd;
-  return true;
-}
-
 // f(NV as a compile-time constant) for a row of nv = ld / 8 = 1 .. 4 16-byte vectors: the kernels keep the row in registers
 template <class F>
 void with_nv(int nv, F&& f) {
@@ -396,25 +257,6 @@ void with_nv(int nv, F&& f) {
     case 3: f(std::integral_constant<int, 3>()); break;
     default: f(std::integral_constant<int, 4>()); break;
   }
-}
-
-// f(G as a compile-time constant): the lane group of the wide forward, the power of two >= nv = ld / 8 = 1 .. 32
-template <class F>
-void with_group(int nv, F&& f) {
-  if (nv <= 1) f(std::integral_constant<int, 1>());
-  else if (nv <= 2) f(std::integral_constant<int, 2>());
-  else if (nv <= 4) f(std::integral_constant<int, 4>());
-  else if (nv <= 8) f(std::integral_constant<int, 8>());
-  else if (nv <= 16) f(std::integral_constant<int, 16>());
-  else f(std::integral_constant<int, 32>());
-}
-
-// Source pixels along one axis that WT destination pixels can touch, scale = in / out: floor(s) moves by at most
-// ceil((WT - 1) scale) + 1 between the first and the last pixel (the +1: fp32 rounding of the coordinate), one more for the last
-// pixel's i1, one for the count.
-int wide_footprint(float scale, int n_src) {
-  const int f = (int)ceilf((WT - 1) * scale) + 3;
-  return f < n_src ? f : n_src;
 }
 
 constexpr int WIDE_NV = 2;     // channel chunk of the wide backward: 16 channels, a UWIN x UWIN window of 51 KB

@@ -8,7 +8,7 @@ from torch import Tensor, nn
 
 from .. import _C
 from ..constructor import LOSSES
-from .cross_entropy import materialized
+from .cross_entropy import UpsampledLogits, materialized
 from ..engine.core import BF16, mark_padded, pad8, ptr, require_device, stream_ptr
 
 BINARY_MODE, MULTICLASS_MODE, MULTILABEL_MODE = 'binary', 'multiclass', 'multilabel'
@@ -89,8 +89,57 @@ class _Dice(torch.autograd.Function):
         return d, None, None, None, None, None, None
 
 
+class _UpsampleDice(torch.autograd.Function):
+    """DiceLoss('multiclass')(F.interpolate(low, size, 'bilinear'), target) from the low-resolution logits
+    (csrc/loss_upsample_dice.hip): the full-resolution logits and their gradient are never written."""
+
+    @staticmethod
+    def forward(ctx, low: Tensor, target: Tensor, size, smooth: float, eps: float, log_loss: bool, sel):
+        require_device(low)
+        n, classes, hs, ws = low.shape
+        hd, wd = size
+        zp = low.detach().permute(0, 2, 3, 1)
+        ld = zp.stride(2)
+        if not (zp.dtype == BF16 and zp.stride(3) == 1 and classes <= ld <= 64 and ld % 8 == 0 and zp.stride(1) == ws * ld
+                and zp.stride(0) == hs * ws * ld and zp.data_ptr() % 16 == 0):
+            ld = pad8(classes)
+            buf = torch.zeros((n, hs, ws, ld), dtype=BF16, device=low.device)
+            buf[..., :classes] = zp
+            zp = buf[..., :classes]
+        z = torch.as_strided(zp, (n, hs, ws, ld), (hs * ws * ld, ws * ld, ld, 1))
+        if target.dtype != torch.int64 or not target.is_contiguous():
+            target = target.to(torch.int64).contiguous()
+        dev, lib = z.device, _C.lib()
+        lse = torch.empty(n * hd * wd, dtype=torch.float32, device=dev)
+        partial = torch.empty((lib.tok_upsample_dice_rows(n, hd, wd), 3, classes), dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        coef = torch.empty((2, classes), dtype=torch.float32, device=dev)
+        _C.check(lib.tok_upsample_dice_fwd(ptr(z), n, hs, ws, classes, ld, hd, wd, ptr(target), float(smooth), float(eps),
+                                           int(log_loss), ptr(sel), 0 if sel is None else sel.numel(), ptr(lse), ptr(partial),
+                                           ptr(loss), ptr(coef), stream_ptr()), 'tok_upsample_dice_fwd')
+        ctx.saved = (z, target, lse, coef, (n, hs, ws, classes, ld, hd, wd), low.dtype)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        z, target, lse, coef, (n, hs, ws, classes, ld, hd, wd), in_dtype = ctx.saved
+        gs = g.detach().to(torch.float32).reshape(1).contiguous()
+        d = torch.empty((n, hs, ws, ld), dtype=BF16, device=z.device)
+        _C.check(_C.lib().tok_upsample_dice_bwd(ptr(z), n, hs, ws, classes, ld, hd, wd, ptr(target), ptr(lse), ptr(coef), ptr(gs),
+                                                ptr(d), 0, stream_ptr()), 'tok_upsample_dice_bwd')
+        ctx.saved = None
+        if ld == pad8(classes) != classes:
+            mark_padded(d)
+        d = d[..., :classes].permute(0, 3, 1, 2)
+        if in_dtype != BF16:
+            d = d.to(in_dtype)
+        return d, None, None, None, None, None, None
+
+
 @LOSSES.register_class
 class DiceLoss(nn.Module):
+    consumes_lazy_logits = True     # JointLoss hands the UpsampledLogits through instead of materialising it
+
     def __init__(self, mode: str, classes: List[int] = None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0, eps: float = 1e-7):
         if mode not in {BINARY_MODE, MULTILABEL_MODE, MULTICLASS_MODE}:
@@ -106,6 +155,14 @@ class DiceLoss(nn.Module):
         self.from_logits, self.smooth, self.eps, self.log_loss = from_logits, smooth, eps, log_loss
 
     def forward(self, input: Tensor, target: Tensor) -> Tensor:
+        if isinstance(input, UpsampledLogits) and input._full is None and self.mode == MULTICLASS_MODE:
+            # the fused kernels on the low-resolution logits, where the library has them and serves the row pitch
+            low, size = input._low, input._size
+            serves = getattr(_C.lib(), 'tok_upsample_dice_serves', None)
+            if serves is not None and low.dim() == 4 and target.shape == (low.shape[0],) + size \
+                    and serves(low.shape[1], max(low.permute(0, 2, 3, 1).stride(2), pad8(low.shape[1]))):
+                sel = None if self.classes is None else self.classes.to(low.device)
+                return _UpsampleDice.apply(low, target, size, self.smooth, self.eps, self.log_loss, sel)
         input = materialized(input)   # an UpsampledLogits would hide the autograd edge from Function.apply
         if self.mode in (BINARY_MODE, MULTILABEL_MODE) and input.shape != target.shape:
             raise ValueError(f"Shapes of input {input.shape} and target {target.shape} tensors don't match!")
